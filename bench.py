@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — k-mers/s hashed+sketched at k=32 on 150 bp reads (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--reads-per-step R] [--dist g|u]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--reads-per-step R] [--dist g|u] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (ntc_submit_device / ntc_submit_tiled_device: ntHash -> sample -> count into
 the device-resident t_Counter sketch) over one batch of synthetic reads that is already resident in HBM.
@@ -13,8 +13,13 @@ the 16-bit counter slices, wrapping local sums, per-rank value histograms of the
 
 One JSON line on rank 0: value = total k-mers (sum of F1 over ranks) / max-over-ranks wall time.
 Extra objects: "roofline" (ALL kernels of a step — hash kernels and the deferred sketch update —, HIP-event timed,
-algorithmic bytes; "roofline_hash" prices the hash kernels alone against the bytes they move) and "cpu_baseline" (the
-reference's own ntRead compiled from /root/reference by oracle/Makefile, on a bounded sample, rank 0 / N=1 only).
+algorithmic bytes; "roofline_hash" prices the hash kernels alone against the bytes they move).
+
+A plain run sets up, warms up, times ONE region of exactly K steps and prints the line.  `--full` adds what takes runs
+of its own: the timed region repeated nine times in-process (median repeat + spread; `--repeats` overrides), the shader
+clock before / after, "roofline_nodefer" (a second engine without NTC_FLAG_DEFER_REDO), live rocprofv3 PMC passes for
+roofline.traffic / valu, and "cpu_baseline" (the reference's own ntRead built by oracle/Makefile, on a bounded sample,
+rank 0 / N=1 only).  `--dump-outputs DIR` writes what the timed path computed (dump_outputs).
 """
 import argparse
 import json
@@ -26,6 +31,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+RAMP_S = 1.0  # seconds of untimed load behind the warm-up steps before the first timed region (ramp() in main)
 
 
 def klist_of(args):
@@ -35,7 +41,7 @@ def klist_of(args):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 10; --config 3: 1 B reads in total over the ranks)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reads-per-step", type=int, default=10_000_000)
     ap.add_argument("--read-len", type=int, default=150)
@@ -50,11 +56,16 @@ def parse():
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5],
                     help="BASELINE.json config: 2 (default) 100 M reads k=32 sBits=7; 3: 1 B reads in total, sBits=11, read-index ranges split "
                          "over the ranks (strong scaling); 4: k=32,64,96,128 in one run; 5: spaced seed k=12 g=2")
-    ap.add_argument("--repeats", type=int, default=9, help="the timed region (K steps + flush + merge) is run this many times in-process; ms_per_step / value "
-                                                            "are the MEDIAN repeat's, ms_per_step_min / _max give the spread (the clocks differ from lease to lease and ramp)")
-    ap.add_argument("--no-nodefer", action="store_true", help="skip the extra run without NTC_FLAG_DEFER_REDO (\"roofline_nodefer\": the default buffer contract of ntc_submit*_device)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not re-run this command under rocprofv3 --pmc for roofline.traffic / valu "
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: nine repeats of the timed region (unless --repeats), "
+                                                        "sclk_mhz, roofline_nodefer, live PMC passes, cpu_baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed as DIR/<name>.npy (float64 / float32, < 64 MB; see dump_outputs)")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region (K steps + flush + merge) is run this many times in-process (default 1; 9 with "
+                                                               "--full); ms_per_step / value are the MEDIAN repeat's, ms_per_step_min / _max give the spread "
+                                                               "(the clocks differ from machine to machine and ramp)")
+    ap.add_argument("--no-nodefer", action="store_true", help="--full: skip the extra run without NTC_FLAG_DEFER_REDO (\"roofline_nodefer\": the default buffer contract of ntc_submit*_device)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full: do not re-run this command under rocprofv3 --pmc for roofline.traffic / valu "
                                                                "(the committed table profiles/traffic_pmc.json is looked up instead)")
     ap.add_argument("--direct-atomics", action="store_true", help="A/B: one device atomic per sampled k-mer instead of the hit log")
     ap.add_argument("--always-log", action="store_true", help="A/B: never switch from the hit log to direct atomics")
@@ -72,7 +83,12 @@ def parse():
                          "steps); auto = owner for sBits >= 11 (fewer hits than counter bytes: BASELINE config 3), slices otherwise")
     ap.add_argument("--lib", type=str, default="", help="A/B: load this build of libntcard_hip.so instead of the in-tree one")
     ap.add_argument("--cpu-sample-reads", type=int, default=0, help="0 = auto (about 10-20 s of CPU work)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
+    return args
 
 
 def host_cpu():
@@ -236,7 +252,7 @@ def read_sclk_mhz(device_index=0):
     import shutil
     import subprocess
     smi = shutil.which("rocm-smi") or "/opt/rocm/bin/rocm-smi"
-    if not os.access(smi, os.X_OK):
+    if not os.access(smi, os.X_OK) or under_profiler():  # (under rocprofv3 the profiler's preload would come along into rocm-smi)
         return None
     try:
         r = subprocess.run([smi, "-d", str(device_index), "--showclocks"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=20)
@@ -246,10 +262,61 @@ def read_sclk_mhz(device_index=0):
         return None
 
 
+def strip_option(argv, name):
+    """argv without the option `name` and its value (`name VALUE` or `name=VALUE`)"""
+    out, skip = [], False
+    for a in argv:
+        if skip:
+            skip = False
+        elif a == name:
+            skip = True
+        elif not a.startswith(name + "="):
+            out.append(a)
+    return out
+
+
+DUMP_SAMPLE = 1 << 21  # t_Counter entries in the dump's sample (8 MB as float32)
+
+
+def dump_outputs(out_dir, ph, f1, nk, r_bits, s_bits, sketch=None):
+    """--dump-outputs DIR: what a caller of the timed path receives after its last step (the sketch is final: the timed region ends with the
+    flush), as .npy files in float64 / float32 — at most nk MB + 8 MB + a little (nk <= 32, so < 64 MB in all):
+      f1.npy       float64 [nk]             F1 per k (ntc_finish; after a multi-GPU merge, the sum over the ranks)
+      p_hist.npy   float64 [nk, 2, 65536]   the value histograms of the t_Counter planes (ntc_finish; compEst's input)
+      F0.npy       float64 [nk]             compEst's F0 per k (ntc_estimate)
+      f_est.npy    float64 [nk, 1001]       compEst's f[0..1000] per k (ntc_estimate; f[0] is unused)
+      t_counter.npy (float32 [nk, 2, 2^r]) when the t_Counter has at most 2^21 entries, else t_counter_sample.npy: float32 [2^21], the
+                   t_Counter (low 16 bits of the device sketch) at 2^21 flat indices drawn from numpy's default_rng(0), sorted — single
+                   process only (after a multi-GPU merge no rank holds the whole sketch)
+    """
+    import numpy as np
+    import ntcard_amd as nt
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"f1": np.asarray(f1, dtype=np.float64), "p_hist": np.asarray(ph, dtype=np.float64).reshape(nk, 2, 65536)}
+    est = [nt.estimate(arrays["p_hist"][ki].astype(np.uint32), r_bits, s_bits, 1000) for ki in range(nk)]
+    arrays["F0"] = np.array([F0 for F0, _ in est], dtype=np.float64)
+    arrays["f_est"] = np.stack([f for _, f in est]).astype(np.float64)
+    if sketch is not None:
+        import torch
+        n = sketch.numel()
+        if n <= DUMP_SAMPLE:
+            arrays["t_counter"] = (sketch & 0xFFFF).cpu().numpy().astype(np.float32).reshape(nk, 2, 1 << r_bits)
+        else:
+            idx = np.sort(np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+            arrays["t_counter_sample"] = (sketch[torch.from_numpy(idx).to(sketch.device)] & 0xFFFF).cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise RuntimeError(f"bench.py --dump-outputs: {total} bytes exceed 64 MB")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def relaunch_under_torchrun(args):
-    """`python bench.py --gpus N` with N > 1 outside torch.distributed.run: become `python -m torch.distributed.run --nnodes=1
-    --nproc-per-node N ... bench.py <same flags>` (one rank per GPU over RCCL).  Fails loudly when the node has fewer GPUs."""
+    """`python bench.py --gpus N` with N > 1 outside torch.distributed.run: run `python -m torch.distributed.run --nnodes=1
+    --nproc-per-node N ... bench.py <same flags>` (one rank per GPU over RCCL) as a child process and exit with its status.
+    Fails loudly when the node has fewer GPUs."""
     import socket
+    import subprocess
     import torch
     have = torch.cuda.device_count()
     if have < args.gpus:
@@ -260,7 +327,7 @@ def relaunch_under_torchrun(args):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(sys.executable, cmd, env)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def main():
@@ -271,14 +338,17 @@ def main():
     if "WORLD_SIZE" in os.environ and args.gpus != world_env and os.environ.get("RANK", "0") == "0":
         print(f"bench.py: --gpus {args.gpus} ignored, running with WORLD_SIZE={world_env} ranks", file=sys.stderr)
     strong_total = None
-    if args.config == 3:  # 1 B reads in total over the ranks, sBits = 11 (the >= 50 GB branch of ntcard.cpp:427-431)
+    if args.config == 3:  # 1 B reads in total over the ranks, sBits = 11 (the >= 50 GB branch of ntcard.cpp:427-431); an explicit --steps holds
         args.s_bits = 11
         strong_total = 1_000_000_000
-        args.steps = max(1, strong_total // (world_env * args.reads_per_step))
+        if args.steps is None:
+            args.steps = max(1, strong_total // (world_env * args.reads_per_step))
     elif args.config == 4:
         args.klist = "32,64,96,128"
     elif args.config == 5:
         args.k, args.gap = 12, 2
+    if args.steps is None:
+        args.steps = 10
     if args.layout == "auto":
         kl = klist_of(args)
         k1h_gap = len(kl) == 1 and (kl[0], args.gap) in ((12, 2), (32, 8))  # K1h's spaced-seed variants (config 5 in both forms of SURVEY 8(d))
@@ -385,6 +455,21 @@ def main():
             parallel.merge_to_value_histograms(sketch, f1_dev, nk, args.r_bits, dst=0)
         e.sync()
 
+    def ramp(e):
+        """untimed steps over the resident batches (at least one pass, eight per flush) until the device has been loaded for RAMP_S: the shader clock
+        ramps over the first ~100 ms of sustained load, which one timed region right behind W warm-up steps would pay
+        (measured: the first of nine regions of 20 steps ~10 % slower than the median).  timed_region resets the engine: nothing is counted.
+        Not under a profiler: the PMC passes and the kernel traces (live_pmc, tools/prof.sh) divide the dispatches by steps + warm-up."""
+        t0, i = time.perf_counter(), 0
+        while i < nb or time.perf_counter() - t0 < RAMP_S:
+            submit_to(e, batches[i % nb])
+            i += 1
+            if i % 8 == 0:
+                e.flush()
+                e.sync()
+        e.flush()
+        e.sync()
+
     def timed_region(e):
         """EXACTLY K steps + the flush (+ the multi-GPU merge), bracketed by barrier + synchronize on both sides; max over ranks"""
         e.reset()
@@ -418,11 +503,13 @@ def main():
                 "merged": merged, "merge_t": merge_t}
 
     merge_mode = args.merge if args.merge != "auto" else ("owner" if args.s_bits >= 11 else "slices")
-    sclk_before = read_sclk_mhz(local_rank) if rank == 0 else None
+    sclk_before = read_sclk_mhz(local_rank) if rank == 0 and args.full else None
     warm(eng)
+    if W > 0 and not under_profiler():
+        ramp(eng)
     n_rep = max(1, args.repeats)
     runs = [timed_region(eng) for _ in range(n_rep)]
-    sclk_after = read_sclk_mhz(local_rank) if rank == 0 else None
+    sclk_after = read_sclk_mhz(local_rank) if rank == 0 and args.full else None
     order = sorted(range(n_rep), key=lambda i: runs[i]["dt"])
     med = runs[order[(n_rep - 1) // 2]]  # the median repeat (the lower one of an even count): every per-step figure below is THIS repeat's
     dt_max = med["dt"]
@@ -435,6 +522,8 @@ def main():
     else:
         _, ph, f1 = eng.finish(counters=False, p_hist=True)
     total_kmers = int(sum(int(x) for x in f1))  # after the reduce rank 0 holds the sum over ranks (and over the k list)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ph, f1, nk, args.r_bits, args.s_bits, None if use_dist else sketch)
     if args.k1h_timers:
         tm = [int(x) for x in f1_big.cpu().numpy()[nk:nk + 4]]
         tot = max(sum(tm), 1)
@@ -520,7 +609,8 @@ def main():
             "ms_per_step_max": runs[order[-1]]["dt"] * 1e3 / K,
             "ms_per_step_all": [r["dt"] * 1e3 / K for r in runs],
             "kernel_ms_per_step_all": [{"hash": r["ker_ms"] / K, "fixup": r["fix_ms"] / K, "apply": r["apply_ms"] / K} for r in runs],
-            "sclk_mhz": {"before": sclk_before, "after": sclk_after, "source": "rocm-smi --showclocks (current sclk level), read before the warm-up and right behind the last repeat"},
+            "sclk_mhz": ({"before": sclk_before, "after": sclk_after, "source": "rocm-smi --showclocks (current sclk level), read before the warm-up and right behind the last repeat"}
+                         if args.full else None),
             "higher_is_better": True,
             "scaling": "strong" if strong_total is not None else "weak",
             "vs_baseline": None,
@@ -566,7 +656,7 @@ def main():
         out["roofline"]["traffic_source"] = "profiles/traffic_pmc.json" if out["roofline"]["traffic"] is not None else None
         # the same workload with the DEFAULT buffer contract of ntc_submit*_device (no NTC_FLAG_DEFER_REDO: the fix-up kernels follow every
         # launch in stream order, the caller may refill a buffer as soon as its own stream-ordered work allows)
-        if world == 1 and not use_dist and not args.no_nodefer:
+        if args.full and world == 1 and not use_dist and not args.no_nodefer:
             eng.close()
             e2 = make_engine(base_flags)
             warm(e2)
@@ -579,11 +669,12 @@ def main():
                                        "fixup_ms": m2["fix_ms"] / max(K, 1), "repeats": len(r2),
                                        "note": "engine without NTC_FLAG_DEFER_REDO: one K1f launch behind every K1h launch, in stream order (fixup_ms), instead of one per 8 batches"}
             e2.close()
-        if world == 1 and not use_dist and not args.no_live_pmc and not under_profiler():
+        if args.full and world == 1 and not use_dist and not args.no_live_pmc and not under_profiler():
             eng.close()
             del batches, wb
             torch.cuda.empty_cache()
-            inner = [a for a in sys.argv[1:] if a not in ("--no-cpu-baseline", "--no-live-pmc", "--no-nodefer")] + ["--no-cpu-baseline", "--no-live-pmc", "--no-nodefer", "--repeats", "1"]
+            # the passes re-run this command as a plain run of one timed region (no --full, no output dump)
+            inner = [a for a in strip_option(sys.argv[1:], "--dump-outputs") if a not in ("--full", "--no-cpu-baseline", "--no-live-pmc", "--no-nodefer")] + ["--repeats", "1"]
             live = live_pmc(inner, K + W)
             if live is not None:
                 # MI355X_MICROARCH.md (HBM / rocprofv3): FETCH_SIZE and WRITE_SIZE are in KB; wide streaming reads are
@@ -596,7 +687,7 @@ def main():
                                     "wave_insts_per_s": (v / (step_ms * 1e-3)) if step_ms > 0 else None,
                                     "frac": (v / (step_ms * 1e-3) / peak_valu) if step_ms > 0 else None,
                                     "hash_kernels_only": live["SQ_INSTS_VALU_hash"], "source": "live: rocprofv3 --pmc SQ_INSTS_VALU"})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, stride)
             except Exception as ex:  # the checker is optional for the measurement itself

@@ -836,6 +836,36 @@ def test_bench_gpus_flag_launches_real_ranks(tmp_path):
     assert too_many.returncode != 0 and b"HIP device" in too_many.stderr
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: a plain run (one timed region of exactly --steps steps, none of --full's extras) writes the arrays of the
+    timed path; two runs with the same arguments write the same arrays, and they agree with the line's F1 and sampled increments"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--reads-per-step", "1000000"]
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + ["--dump-outputs", str(tmp_path / d)], stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.decode().strip().splitlines()[-1]))
+    j = lines[0]
+    assert j["steps"] == 3 and j["repeats"] == 1 and len(j["ms_per_step_all"]) == 1
+    assert not any(key in j for key in ("cpu_baseline", "roofline_nodefer")) and j["sclk_mhz"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["F0.npy", "f1.npy", "f_est.npy", "p_hist.npy", "t_counter_sample.npy"]
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n
+    f1, ph = np.load(tmp_path / "a" / "f1.npy"), np.load(tmp_path / "a" / "p_hist.npy")
+    assert f1.dtype == np.float64 and int(f1.sum()) == j["f1_total"] == lines[1]["f1_total"]
+    assert ph.shape == (1, 2, 65536) and int(ph.sum()) == 2 << 27  # every counter of both planes (rBits = 27) in some bin
+    assert int((ph[0] * np.arange(65536)).sum()) == j["sampled_increments"]
+    sample = np.load(tmp_path / "a" / "t_counter_sample.npy")
+    assert sample.dtype == np.float32 and sample.shape == (1 << 21,) and 0 < sample.sum() and sample.max() <= 65535
+    assert np.load(tmp_path / "a" / "f_est.npy").shape == (1, 1001)
+
+
 def test_randomised_shapes_small():
     """a short run of the randomised sweep (tools/fuzz_parity.py: random k lists, gaps, lengths, dirt, submit patterns)"""
     import subprocess

@@ -2,7 +2,7 @@
 # tools/k1h_ab.sh "<lib> <lib> ..." [bench args] — the in-tree library against experiment builds (tools/k1h_variant.sh -> tools/lib_k1h_<name>.so) inside
 # ONE lease, interleaved, two rounds: hash / fix-up / apply ms per step of the median repeat
 LIBS=$1; shift
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-live-pmc --no-nodefer $*"
+ARGS="--steps 20 --warmup 5 --full --no-cpu-baseline --no-live-pmc --no-nodefer $*"
 for i in 1 2; do
   for lib in "" $LIBS; do
     if [ -n "$lib" ]; then L="--lib $lib"; else L=""; fi

@@ -7,8 +7,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-# PROF_DEFAULT=1: profile exactly the default bench command (what BENCH_rNN.json is measured with)
-if [ "${PROF_DEFAULT:-0}" = 1 ]; then ARGS="--no-cpu-baseline --no-live-pmc $*"; else ARGS="--steps 4 --warmup 1 --reads-per-step 4000000 --no-cpu-baseline --no-live-pmc $*"; fi
+# PROF_DEFAULT=1: profile the default bench command (what BENCH_rNN.json is measured with), with --full's nine repeats and roofline_nodefer
+if [ "${PROF_DEFAULT:-0}" = 1 ]; then ARGS="--full --no-cpu-baseline --no-live-pmc $*"; else ARGS="--steps 4 --warmup 1 --reads-per-step 4000000 --full --no-cpu-baseline --no-live-pmc $*"; fi
 # PROF_PHASE=bench: only the unprofiled bench line; PROF_PHASE=counters: only the rocprofv3 passes (a bench run right behind PMC passes of
 # another command has measured up to 30 % slow — the clocks stay in the profiling state for a while — so the lines of all tags are taken first)
 if [ "${PROF_PHASE:-all}" != counters ]; then
