@@ -95,6 +95,28 @@ const char *ntc_last_error(void);
 
 /* ntcard.cpp:437-439 (allocate + zero t_Counter), :433-435 (zero F1) */
 int ntc_create(const ntc_config *cfg, ntc_engine **out);
+
+/* An engine whose planes are SPACED SEEDS given as masks: seeds[i] is a string of k_i characters '0' / '1'
+ * (1 <= k_i <= ntc_max_k(), at least one '1'); offset 0 is the leftmost base of the window.  This is the seed
+ * syntax of the reference's hash library (stHashIterator::parseSeed, stHashIterator.hpp:23-33; NTMSM64,
+ * nthash.hpp:620-678), which ntcard itself only uses for the one shape 1^a 0^g 1^a of -g (ntcard.cpp:407-413).
+ * For every window of k_i bases of a read:
+ *   - the window counts (F1 of the plane, t_Counter) only when ALL k_i bytes are bases, those under a '0' included
+ *     (the -g path's rule: stHashIterator::next, NTMSM64);
+ *   - its value starts from the plain ntHash fh / rh of the window (nthash.hpp:220-239); for every i with mask[i] == '0'
+ *       fs ^= srol^(k-1-i)(seed[b_i]),   rs ^= srol^i(seed[b_i & cpOff])
+ *     and the canonical value is rs < fs ? rs : fs (NTMSM64 with m = m2 = 1);
+ *   - ntComp (ntcard.cpp:132-145) counts it into the plane of that mask.
+ * Planes follow the order of `seeds` like a k list: t_counter[n_seeds][2][1 << r_bits], f1[n_seeds]; the engine's k list
+ * is the masks' lengths, so ntc_finish, ntc_merge_counters, the log calls and ntc_merge_devices (which refuses engines
+ * whose seed lists differ) work unchanged.  A mask of '1's only is a plain k-mer plane, 1^a 0^g 1^a is ntcard's -g g
+ * seed (bit-identical results to ntc_create with gap = g); one list may mix masks of any length and shape.
+ * cfg->n_k == 0, cfg->k == NULL, cfg->gap == 0; everything else of cfg as for ntc_create.  1 <= n_seeds <= NTC_MAX_K_LIST.
+ * NTC_FLAG_SIMPLE_KERNEL with a mask that has a '0' is an argument error.  Every argument is checked before a device
+ * is looked for.  Tiled batches: the tiled kernels take the plain planes and ntcard's two tiled -g seeds (k 12 / g 2,
+ * k 32 / g 8); every other spaced plane is counted from a row-slot copy of the batch (NTC_FLAG_REQUIRE_TILED: an error,
+ * before anything is counted). */
+int ntc_create_seeded(const ntc_config *cfg, uint32_t n_seeds, const char *const *seeds, ntc_engine **out);
 void ntc_destroy(ntc_engine *e);                 /* ntcard.cpp:474 */
 int ntc_reset(ntc_engine *e);                    /* re-zero sketch and F1 */
 
@@ -245,6 +267,10 @@ int ntc_hash_dump_device(int32_t device, void *stream, const void *d_slots, uint
 int ntc_hash_dump_k1_device(int32_t device, void *stream, const void *d_slots, uint64_t n_reads,
                             uint32_t read_len, uint32_t stride, uint32_t k, uint32_t gap,
                             uint32_t max_win, void *d_hash_out, void *d_count_out);
+/* The same for a spaced seed given as a mask (ntc_create_seeded: k = strlen(seed)); a mask of '1's only dumps plain k-mers.
+ * The arguments are checked before the device is touched. */
+int ntc_hash_dump_seed_device(int32_t device, void *stream, const void *d_slots, uint64_t n_reads, uint32_t read_len,
+                              uint32_t stride, const char *seed, uint32_t max_win, void *d_hash_out, void *d_count_out);
 
 /* Synthetic workload generator (K0), bit-identical to oracle/orc_gen_reads; DESIGN.md
  * "Synthetic workloads".  Fills d_slots[n_reads*stride].                                         */

@@ -139,14 +139,30 @@ void fill_hfk(ntc::HfK& o, uint32_t k, uint32_t* sketch, unsigned long long* f1,
 	}
 }
 // block shape only (no device call): waves per CU and waves per block for a slot stride, 0 waves = does not fit
-void hf_shape(uint32_t stride, const uint32_t* ks, uint32_t n_k, uint32_t gap, HfPlan& p, size_t& shared_out);
+// seed_lds: the LDS a spaced seed adds (seed_lds(SeedPlan)), 0 for plain k-mers
+void hf_shape(uint32_t stride, const uint32_t* ks, uint32_t n_k, uint32_t seed_lds, HfPlan& p, size_t& shared_out);
 
-int hf_plan(int dev, uint64_t n_slots, uint32_t stride, const uint32_t* ks, uint32_t n_k, uint32_t gap, HfPlan& p)
+// LDS bytes a spaced seed adds to K1's tables: SeedPlan::blob, and 16 B behind the last slot (the rolling form's toggle reads fetch the
+// dword behind the 4 bytes they use, which for the incoming base of a read's last group lies behind the wave's last slot)
+uint32_t seed_lds(const ntc::SeedPlan& sp) { return sp.k ? (uint32_t)sp.blob.size() * 4u + 16u : 0u; }
+
+// K1's arguments of a spaced-seed plane (a launch of its own: HfArgs holds one seed)
+void set_seed_args(ntc::HfArgs& a, const ntc::SeedPlan& sp, const void* d_blob)
+{
+	a.gap = sp.n_dc;
+	a.gapt = d_blob;
+	a.seed_nroll = sp.n_roll;
+	a.seed_extra = sp.extra_bytes();
+	std::memcpy(a.tabg, sp.tabg, sizeof a.tabg);
+	std::memcpy(a.roll_t, sp.roll_t, sizeof a.roll_t);
+}
+
+int hf_plan(int dev, uint64_t n_slots, uint32_t stride, const uint32_t* ks, uint32_t n_k, uint32_t seed_lds, HfPlan& p)
 {
 	DevInfo di;
 	if (int rc = device_info(dev, di)) return rc;
 	size_t shared = 0;
-	hf_shape(stride, ks, n_k, gap, p, shared);
+	hf_shape(stride, ks, n_k, seed_lds, p, shared);
 	if (p.waves_per_cu == 0)
 		return fail(NTC_ERR_ARG, "slot stride %u with k=%u needs more than 160 KiB of LDS per wave", stride, ks[0]);
 	p.smem = shared + p.wpb * (64u * (size_t)stride);
@@ -157,10 +173,10 @@ int hf_plan(int dev, uint64_t n_slots, uint32_t stride, const uint32_t* ks, uint
 	return 0;
 }
 
-void hf_shape(uint32_t stride, const uint32_t* ks, uint32_t n_k, uint32_t gap, HfPlan& p, size_t& shared_out)
+void hf_shape(uint32_t stride, const uint32_t* ks, uint32_t n_k, uint32_t seed_lds, HfPlan& p, size_t& shared_out)
 {
 	const size_t per_wave = 64u * (size_t)stride; // the wave's 64 decoded slots; hit masks and the compaction queue are registers
-	size_t shared = 16 + (size_t)((gap + 1u) / 2u) * 256u;
+	size_t shared = 16 + (size_t)seed_lds;
 	for (uint32_t j = 0; j < n_k; ++j)
 		shared += (size_t)ntc::t2_pairs(ks[j]) * 256u; // the closed-form tables of every fused k are resident
 	// A workgroup's LDS (dynamic + the kernel's static tables) is allocated in granules of 1280 B, 128 of them per
@@ -190,14 +206,14 @@ void hf_shape(uint32_t stride, const uint32_t* ks, uint32_t n_k, uint32_t gap, H
 // Slot stride the host packer uses for reads of up to `maxlen` bytes: a multiple of 4; an ODD number of dwords keeps
 // the 64 lanes of a wave on distinct LDS banks when they read the same column of their slots (160 B = 40 dwords is
 // an 8-way conflict, measured 8 % slower than 156 B), taken whenever it does not cost a wave of occupancy.
-uint32_t pick_stride(uint64_t maxlen, const std::vector<uint32_t>& klist, uint32_t gap)
+uint32_t pick_stride(uint64_t maxlen, const std::vector<uint32_t>& klist, uint32_t seed_lds)
 {
 	const uint32_t s0 = (uint32_t)((maxlen + 3) & ~3ull);
 	if ((s0 / 4) & 1u) return s0;
 	HfPlan a, b;
 	size_t sh;
-	hf_shape(s0, klist.data(), (uint32_t)std::min<size_t>(klist.size(), ntc::kMaxFusedK), gap, a, sh);
-	hf_shape(s0 + 4, klist.data(), (uint32_t)std::min<size_t>(klist.size(), ntc::kMaxFusedK), gap, b, sh);
+	hf_shape(s0, klist.data(), (uint32_t)std::min<size_t>(klist.size(), ntc::kMaxFusedK), seed_lds, a, sh);
+	hf_shape(s0 + 4, klist.data(), (uint32_t)std::min<size_t>(klist.size(), ntc::kMaxFusedK), seed_lds, b, sh);
 	return b.waves_per_cu >= a.waves_per_cu && b.waves_per_cu > 0 ? s0 + 4 : s0;
 }
 
@@ -240,7 +256,7 @@ struct ntc_engine {
 	int device = 0;
 	hipStream_t stream = nullptr;
 	std::vector<uint32_t> klist;
-	uint32_t gap = 0, r_bits = 27, s_bits = 7;
+	uint32_t r_bits = 27, s_bits = 7;
 	std::vector<ntc::HfK> hfk;    // per-k argument blocks of K1 (tables derived once at create)
 	uint32_t* d_sketch = nullptr; // [nk][2][1<<r_bits]
 	unsigned long long* d_f1 = nullptr;
@@ -330,6 +346,7 @@ struct ntc_engine {
 	bool ts_all = false;            // ... for every k (then nothing of a tiled batch is left to K1)
 	std::vector<uint8_t> k_tiled;   // per k of the list: K1h + K1f take it from tiled batches (the others are K1's, which stages the same tiles: round 5)
 	bool ts_required = false;       // NTC_FLAG_REQUIRE_TILED
+	bool seeded = false;            // ntc_create_seeded (a ragged tiled batch of a list no plane of which is K1h's goes to row slots, instead of being refused)
 	bool defer_redo = false;        // NTC_FLAG_DEFER_REDO
 	unsigned char* d_untile = nullptr; // row-major scratch for tiled batches of configurations K1h is not built for
 	size_t untile_cap = 0;
@@ -340,7 +357,14 @@ struct ntc_engine {
 	uint32_t hll_bits = 0;       // != 0: nthll engine (d_sketch holds uint32 M[1<<hll_bits])
 	uint32_t* d_hll_thr = nullptr;
 	uint64_t hll_reads_seen = 0;
-	void* d_gapt = nullptr;      // spaced seed: filter table of the don't-care positions
+	// Spaced seeds, per plane of the list (ntc_create with a gap: its one plane's -g mask; ntc_create_seeded: the caller's masks).  A plane with an
+	// empty mask counts plain k-mers; kgap != 0 marks ntcard's symmetric seed 1^a 0^g 1^a (ntcard.cpp:407-413), which K1h is built for at (12, 2), (32, 8).
+	std::vector<std::string> masks;
+	std::vector<uint32_t> kgap;
+	std::vector<ntc::SeedPlan> seeds; // K1's tables of each spaced plane (k == 0: plain)
+	std::vector<void*> d_seedt;       // SeedPlan::blob on device, per plane (nullptr: plain)
+	uint32_t max_seed_lds = 0;        // the largest seed_lds of the list (pick_stride)
+	bool plain(size_t ki) const { return masks[ki].empty(); }
 	std::vector<void*> d_t1;     // per k: closed-form table of the H-filter kernel's resolve stage
 	// host-submit staging (grow-only)
 	// ntc_submit staging: a small pool of pinned host + device buffer pairs.  A caller packs its reads into a free
@@ -717,7 +741,7 @@ int run_batch(ntc_engine* e, const unsigned char* d_slots, const uint32_t* d_met
 		std::function<int(size_t, size_t, const unsigned char*, uint64_t)> launch_group =
 		    [&](size_t b, size_t n, const unsigned char* slots, uint64_t ns) -> int {
 			HfPlan hp;
-			if (int rc = hf_plan(e->device, ns, stride, &e->klist[b], (uint32_t)n, e->gap, hp)) {
+			if (int rc = hf_plan(e->device, ns, stride, &e->klist[b], (uint32_t)n, seed_lds(e->seeds[b]), hp)) {
 				if (n == 1) return rc;
 				hp.waves_per_cu = 0;
 			}
@@ -725,7 +749,7 @@ int run_batch(ntc_engine* e, const unsigned char* d_slots, const uint32_t* d_met
 			for (size_t j = 0; n > 1 && j < n; ++j) {
 				HfPlan one;
 				size_t sh;
-				hf_shape(stride, &e->klist[b + j], 1, e->gap, one, sh);
+				hf_shape(stride, &e->klist[b + j], 1, seed_lds(e->seeds[b + j]), one, sh);
 				worst_single = std::min(worst_single, one.waves_per_cu);
 			}
 			if (n > 1 && hp.waves_per_cu < 12 && hp.waves_per_cu < worst_single) {
@@ -743,10 +767,7 @@ int run_batch(ntc_engine* e, const unsigned char* d_slots, const uint32_t* d_met
 			a.r_bits = e->r_bits;
 			a.s_bits = e->s_bits;
 			a.n_k = (uint32_t)n;
-			a.gap = e->gap;
-			a.gap_first = (e->klist[b] - e->gap) / 2;
-			a.gapt = e->d_gapt;
-			if (e->gap) ntc::build_gap_roll_table(e->klist[b], a.gap_first, e->gap, a.tabg);
+			if (!e->plain(b)) set_seed_args(a, e->seeds[b], e->d_seedt[b]);
 			for (size_t j = 0; j < n; ++j)
 				a.ks[j] = e->hfk[b + j];
 			if (e->d_log) {
@@ -761,13 +782,13 @@ int run_batch(ntc_engine* e, const unsigned char* d_slots, const uint32_t* d_met
 			HIP_TRY(ntc::launch_sketch_hf(a, hp.grid, hp.wpb, hp.smem, e->stream));
 			return 0;
 		};
-		for (size_t b = 0; b < e->klist.size();) { // runs of this call's k, up to kMaxFusedK per launch
+		for (size_t b = 0; b < e->klist.size();) { // runs of this call's k, up to kMaxFusedK per launch (a spaced seed: a launch of its own)
 			if (!mine(b)) {
 				++b;
 				continue;
 			}
 			size_t n = 1;
-			while (n < ntc::kMaxFusedK && b + n < e->klist.size() && mine(b + n))
+			while (n < ntc::kMaxFusedK && b + n < e->klist.size() && mine(b + n) && e->plain(b) && e->plain(b + n))
 				++n;
 			if (int rc = launch_group(b, n, d_slots, n_slots)) return rc;
 			b += n;
@@ -804,10 +825,7 @@ int run_batch(ntc_engine* e, const unsigned char* d_slots, const uint32_t* d_met
 			HIP_TRY(hipEventCreate(&ev1));
 			HIP_TRY(hipEventRecord(ev0, e->stream));
 		}
-		a.t1 = e->d_t1[ki];
-		a.gapt = e->d_gapt;
-		a.gap = e->gap;
-		a.gap_first = (a.k - e->gap) / 2;
+		a.t1 = e->d_t1[ki]; // (the simple kernel has no spaced seeds: ntc_create refuses them with NTC_FLAG_SIMPLE_KERNEL)
 		HIP_TRY(ntc::launch_hash(0, a, grid, smem, e->stream));
 		if (e->profiling) {
 			HIP_TRY(hipEventRecord(ev1, e->stream));
@@ -817,10 +835,12 @@ int run_batch(ntc_engine* e, const unsigned char* d_slots, const uint32_t* d_met
 	return 0;
 }
 
-// a tiled batch for K1: re-laid out as row-major slots on the device (exact; not a fast path)
-int run_tiled_as_rows(ntc_engine* e, const unsigned char* d_tiles, uint64_t n_reads, uint32_t read_len)
+// a tiled batch for K1: re-laid out as row-major slots on the device (exact; not a fast path).  d_meta: the reads' lengths of a ragged batch
+// (launch_tails_to_meta); skip: the k of the list that are not this call's
+int run_tiled_as_rows(ntc_engine* e, const unsigned char* d_tiles, uint64_t n_reads, uint32_t read_len, const uint32_t* d_meta = nullptr,
+                      const std::vector<uint8_t>* skip = nullptr)
 {
-	const uint32_t stride = pick_stride(read_len, e->klist, e->gap);
+	const uint32_t stride = pick_stride(read_len, e->klist, e->max_seed_lds);
 	const size_t need = (size_t)n_reads * stride + 16;
 	if (need > e->untile_cap) {
 		HIP_TRY(hipStreamSynchronize(e->stream));
@@ -831,7 +851,7 @@ int run_tiled_as_rows(ntc_engine* e, const unsigned char* d_tiles, uint64_t n_re
 		e->untile_cap = need;
 	}
 	HIP_TRY(ntc::launch_untile(d_tiles, e->d_untile, n_reads, read_len, stride, e->stream));
-	return run_batch(e, e->d_untile, nullptr, n_reads, read_len, stride);
+	return run_batch(e, e->d_untile, d_meta, n_reads, read_len, stride, false, skip);
 }
 
 // K1h + K1f over one device-resident batch in the tiled layout (include/ntcard_hip.h: ntc_submit_tiled_device)
@@ -843,6 +863,7 @@ struct TiledSeg {
 	const uint32_t* d_tails;
 };
 int run_tiled_segs(ntc_engine* e, const TiledSeg* segs_in, uint32_t n_in, uint64_t n_submits = 1);
+int tiled_meta(ntc_engine* e, const TiledSeg& sg, const uint32_t** d_meta);
 
 // A list of which a part is K1's: K1 stages the SAME tiles, 64 slots of 16 x ceil(len / 16) bytes per wave next to its closed-form tables.  Does that fit the
 // CU's LDS for every such k on its own (run_batch splits a fused group that does not fit; a single k has to)?  Equal-length reads beyond ~2.4 kb do not:
@@ -853,10 +874,10 @@ bool k1_fits_tiles(const ntc_engine* e, uint32_t read_len)
 	if (e->ts_all) return true;
 	const uint32_t stride = 16u * ((read_len + 15u) / 16u);
 	for (size_t ki = 0; ki < e->klist.size(); ++ki) {
-		if (e->k_tiled[ki]) continue;
+		if (e->k_tiled[ki] || !e->plain(ki)) continue; // (K1's spaced planes take the batch as row slots)
 		HfPlan p;
 		size_t shared = 0;
-		hf_shape(stride, &e->klist[ki], 1, e->gap, p, shared);
+		hf_shape(stride, &e->klist[ki], 1, 0, p, shared);
 		if (p.waves_per_cu == 0 || shared + p.wpb * (64u * (size_t)stride) > kMaxDynLds) return false;
 	}
 	return true;
@@ -880,10 +901,14 @@ int run_tiled_segs(ntc_engine* e, const TiledSeg* segs_in, uint32_t n_in, uint64
 	for (const auto& sg : segs)
 		any_tails |= sg.d_tails != nullptr;
 	if (!e->ts_all && e->ts_required) return fail(NTC_ERR_ARG, "ntc_submit_tiled_device: the tiled kernel is not available for this configuration (NTC_FLAG_REQUIRE_TILED)");
-	if (!e->ts_ok && any_tails) return fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: the tiled kernels are not built for any k of this configuration");
+	if (!e->ts_ok && any_tails && !e->seeded) return fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: the tiled kernels are not built for any k of this configuration");
 	if (!e->ts_ok) { // this configuration is K1's
-		for (const auto& sg : segs)
-			if (int rc = run_tiled_as_rows(e, sg.d_tiles, sg.n_reads, sg.read_len)) return rc;
+		for (const auto& sg : segs) {
+			const uint32_t* d_meta = nullptr;
+			if (sg.d_tails)
+				if (int rc = tiled_meta(e, sg, &d_meta)) return rc;
+			if (int rc = run_tiled_as_rows(e, sg.d_tiles, sg.n_reads, sg.read_len, d_meta)) return rc;
+		}
 		return 0;
 	}
 	if (e->ts_ok && !e->ts_all)
@@ -1122,7 +1147,7 @@ int run_tiled_segs(ntc_engine* e, const TiledSeg* segs_in, uint32_t n_in, uint64
 		ntc::K1hArgs launched[ntc::kK1hSegs];
 		uint32_t n_waves = 0;
 		if (int rc = open_run()) return rc; // (a K1f above may have closed the bracket)
-		HIP_TRY(ntc::launch_sketch_k1h_multi(hs, na, k, e->gap, (unsigned)di.cus, e->stream, launched, &n_waves));
+		HIP_TRY(ntc::launch_sketch_k1h_multi(hs, na, k, e->kgap[ki], (unsigned)di.cus, e->stream, launched, &n_waves));
 		launched_any = true;
 		for (uint32_t i = 0; i < na; ++i) {
 			auto& it = e->k1f_batch.item[e->k1f_n++];
@@ -1140,26 +1165,47 @@ int run_tiled_segs(ntc_engine* e, const TiledSeg* segs_in, uint32_t n_in, uint64
 	}
 	if (!e->profiling)
 		if (int rc = close_run(e)) return rc; // (profiling was switched off inside a run)
-	if (!e->ts_all) // the k of the list K1h is not built for: K1 over the same tiles (staged straight from the tiled layout)
+	if (!e->ts_all) { // the k of the list K1h is not built for: K1 over the same tiles (staged straight from the tiled layout)
+		// K1's spaced planes stage row slots (a re-layout pass, as a -g engine's whole batch before): their skip list is everything but them
+		std::vector<uint8_t> skip_tiles(e->k_tiled), skip_rows(e->klist.size(), 1);
+		bool any_tiles = false, any_rows = false;
+		for (size_t ki = 0; ki < e->klist.size(); ++ki)
+			if (!e->k_tiled[ki] && !e->plain(ki)) {
+				skip_tiles[ki] = 1;
+				skip_rows[ki] = 0;
+				any_rows = true;
+			} else {
+				any_tiles |= !e->k_tiled[ki];
+			}
 		for (const auto& sg : segs) {
 			const uint32_t* d_meta = nullptr;
-			if (sg.d_tails) {
-				// a ragged batch (round 6): K1 takes every read's length from a slot table, built here from the tiles' prefix tables — the batch stays on tiles,
-				// K1h + K1f serve their k from it and K1 the rest (before: the whole batch went to row slots and K1 for every k)
-				if (sg.n_reads > e->tmeta_cap) {
-					HIP_TRY(hipStreamSynchronize(e->stream));
-					if (e->d_tmeta) (void)hipFree(e->d_tmeta);
-					e->d_tmeta = nullptr;
-					e->tmeta_cap = 0;
-					const size_t cap = std::max<size_t>((size_t)sg.n_reads, 1u << 20);
-					if (hipMalloc((void**)&e->d_tmeta, cap * 4) != hipSuccess) return fail(NTC_ERR_MEMORY, "cannot allocate the slot table of a ragged tiled batch on device");
-					e->tmeta_cap = cap;
-				}
-				HIP_TRY(ntc::launch_tails_to_meta(sg.d_tails, sg.n_reads, (sg.read_len + 15u) / 16u, e->d_tmeta, e->stream));
-				d_meta = e->d_tmeta;
-			}
-			if (int rc = run_batch(e, sg.d_tiles, d_meta, sg.n_reads, sg.read_len, 16u * ((sg.read_len + 15u) / 16u), true, &e->k_tiled)) return rc;
+			// a ragged batch (round 6): K1 takes every read's length from a slot table, built here from the tiles' prefix tables — the batch stays on tiles,
+			// K1h + K1f serve their k from it and K1 the rest (before: the whole batch went to row slots and K1 for every k)
+			if (sg.d_tails)
+				if (int rc = tiled_meta(e, sg, &d_meta)) return rc;
+			if (any_tiles)
+				if (int rc = run_batch(e, sg.d_tiles, d_meta, sg.n_reads, sg.read_len, 16u * ((sg.read_len + 15u) / 16u), true, &skip_tiles)) return rc;
+			if (any_rows)
+				if (int rc = run_tiled_as_rows(e, sg.d_tiles, sg.n_reads, sg.read_len, d_meta, &skip_rows)) return rc;
 		}
+	}
+	return 0;
+}
+
+// the slot table (len | len << 16 per read) of a ragged tiled batch, for K1
+int tiled_meta(ntc_engine* e, const TiledSeg& sg, const uint32_t** d_meta)
+{
+	if (sg.n_reads > e->tmeta_cap) {
+		HIP_TRY(hipStreamSynchronize(e->stream));
+		if (e->d_tmeta) (void)hipFree(e->d_tmeta);
+		e->d_tmeta = nullptr;
+		e->tmeta_cap = 0;
+		const size_t cap = std::max<size_t>((size_t)sg.n_reads, 1u << 20);
+		if (hipMalloc((void**)&e->d_tmeta, cap * 4) != hipSuccess) return fail(NTC_ERR_MEMORY, "cannot allocate the slot table of a ragged tiled batch on device");
+		e->tmeta_cap = cap;
+	}
+	HIP_TRY(ntc::launch_tails_to_meta(sg.d_tails, sg.n_reads, (sg.read_len + 15u) / 16u, e->d_tmeta, e->stream));
+	*d_meta = e->d_tmeta;
 	return 0;
 }
 
@@ -1186,6 +1232,19 @@ int defer_or_run_tiled(ntc_engine* e, const unsigned char* d_tiles, uint64_t n_r
 	return 0;
 }
 
+// ntcard's -g seed 1^a 0^g 1^a (a, g >= 1) -> g; any other mask -> 0
+uint32_t symmetric_gap(const std::string& m)
+{
+	const size_t a = m.find('0');
+	if (a == 0 || a == std::string::npos || m.size() < 2 * a + 1) return 0;
+	const size_t g = m.size() - 2 * a;
+	return m == std::string(a, '1') + std::string(g, '0') + std::string(a, '1') ? (uint32_t)g : 0u;
+}
+int check_config(const ntc_config* cfg);
+int dump_k1(int32_t device, void* stream, const void* d_slots, uint64_t n_reads, uint32_t read_len, uint32_t stride, uint32_t k, const std::string& mask,
+            uint32_t max_win, void* d_hash_out, void* d_count_out);
+int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, bool seeded, ntc_engine** out);
+
 } // namespace
 
 extern "C" {
@@ -1200,6 +1259,48 @@ int ntc_create(const ntc_config* cfg, ntc_engine** out)
 	*out = nullptr;
 	if (cfg->n_k == 0 || cfg->n_k > NTC_MAX_K_LIST || !cfg->k)
 		return fail(NTC_ERR_ARG, "ntc_create: need 1..%d k values", NTC_MAX_K_LIST);
+	if (int rc = check_config(cfg)) return rc;
+	std::vector<std::string> masks(cfg->n_k);
+	if (cfg->gap != 0) masks[0] = ntc::gap_mask(cfg->k[0], cfg->gap); // "1"x(k-g)/2 "0"xg "1"x(k-g)/2, ntcard.cpp:407-413
+	return create_engine(cfg, masks, false, out);
+}
+
+int ntc_create_seeded(const ntc_config* cfg, uint32_t n_seeds, const char* const* seeds, ntc_engine** out)
+{
+	if (!cfg || !out || !seeds) return fail(NTC_ERR_ARG, "ntc_create_seeded: null argument");
+	*out = nullptr;
+	if (cfg->n_k != 0 || cfg->k != nullptr || cfg->gap != 0)
+		return fail(NTC_ERR_ARG, "ntc_create_seeded: n_k, k and gap of the config must be 0 (the k list is the seeds' lengths)");
+	if (n_seeds == 0 || n_seeds > NTC_MAX_K_LIST) return fail(NTC_ERR_ARG, "ntc_create_seeded: need 1..%d seeds", NTC_MAX_K_LIST);
+	std::vector<std::string> masks(n_seeds);
+	std::vector<uint32_t> ks(n_seeds);
+	bool spaced = false;
+	for (uint32_t i = 0; i < n_seeds; ++i) {
+		if (!seeds[i]) return fail(NTC_ERR_ARG, "ntc_create_seeded: seed %u is null", i + 1);
+		const size_t len = strnlen(seeds[i], (size_t)kMaxK + 1);
+		if (len < 1 || len > kMaxK) return fail(NTC_ERR_ARG, "ntc_create_seeded: seed %u: length outside 1..%u", i + 1, kMaxK);
+		for (size_t j = 0; j < len; ++j)
+			if (seeds[i][j] != '0' && seeds[i][j] != '1')
+				return fail(NTC_ERR_ARG, "ntc_create_seeded: seed %u: character %zu is neither '0' nor '1'", i + 1, j + 1);
+		masks[i].assign(seeds[i], len);
+		if (masks[i].find('1') == std::string::npos) return fail(NTC_ERR_ARG, "ntc_create_seeded: seed %u has no '1'", i + 1);
+		spaced |= masks[i].find('0') != std::string::npos;
+		ks[i] = (uint32_t)len;
+	}
+	ntc_config c = *cfg;
+	c.n_k = n_seeds;
+	c.k = ks.data();
+	if (int rc = check_config(&c)) return rc;
+	if (spaced && (c.flags & NTC_FLAG_SIMPLE_KERNEL)) return fail(NTC_ERR_ARG, "ntc_create_seeded: spaced seeds need the production kernel");
+	return create_engine(&c, masks, true, out);
+}
+
+} // extern "C"
+
+namespace {
+// the checks ntc_create and ntc_create_seeded share (cfg->k holds n_k values)
+int check_config(const ntc_config* cfg)
+{
 	constexpr uint32_t kKnownFlags = NTC_FLAG_SIMPLE_KERNEL | NTC_FLAG_DIRECT_ATOMICS | NTC_FLAG_ALWAYS_LOG | NTC_FLAG_PARTITION_ALWAYS | NTC_FLAG_LANE_KERNEL |
 	                                 NTC_FLAG_REQUIRE_TILED | NTC_FLAG_DEFER_REDO;
 	if (cfg->flags & ~kKnownFlags) // (ABI 4's NTC_FLAG_BITSLICE_KERNEL = 4 and NTC_FLAG_TILED_TEAMS = 256 selected kernels that no longer exist)
@@ -1217,6 +1318,12 @@ int ntc_create(const ntc_config* cfg, ntc_engine** out)
 	if (cfg->r_bits < 8 || cfg->r_bits > 30) return fail(NTC_ERR_ARG, "ntc_create: r_bits %u outside 8..30", cfg->r_bits);
 	if (cfg->s_bits < 2 || cfg->s_bits > 24) return fail(NTC_ERR_ARG, "ntc_create: s_bits %u outside 2..24", cfg->s_bits);
 	if (cfg->log_entries > (1ull << 32)) return fail(NTC_ERR_ARG, "ntc_create: log_entries %llu above 2^32", (unsigned long long)cfg->log_entries);
+	return 0;
+}
+
+// ntc_create / ntc_create_seeded past their argument checks; masks[i]: the spaced seed of plane i (empty: plain k-mers)
+int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, bool seeded, ntc_engine** out)
+{
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
 		return fail(NTC_ERR_DEVICE, "ntc_create: no HIP device available (this library has no CPU fallback)");
@@ -1228,7 +1335,18 @@ int ntc_create(const ntc_config* cfg, ntc_engine** out)
 	e->device = cfg->device;
 	e->stream = (hipStream_t)cfg->stream;
 	e->klist.assign(cfg->k, cfg->k + cfg->n_k);
-	e->gap = cfg->gap;
+	e->seeded = seeded;
+	e->masks.assign(cfg->n_k, std::string());
+	e->kgap.assign(cfg->n_k, 0u);
+	e->seeds.assign(cfg->n_k, ntc::SeedPlan());
+	for (size_t ki = 0; ki < masks.size(); ++ki) {
+		const std::string& m = masks[ki];
+		if (m.find('0') == std::string::npos) continue; // every position cared for: plain k-mers (K1h / K1 exactly as a k list)
+		e->masks[ki] = m;
+		e->kgap[ki] = symmetric_gap(m);
+		ntc::build_seed_plan(m, e->seeds[ki]);
+		e->max_seed_lds = std::max(e->max_seed_lds, seed_lds(e->seeds[ki]));
+	}
 	e->r_bits = cfg->r_bits;
 	e->s_bits = cfg->s_bits;
 	e->kernel_kind = (cfg->flags & NTC_FLAG_SIMPLE_KERNEL) ? KIND_SIMPLE : KIND_HF;
@@ -1261,8 +1379,7 @@ int ntc_create(const ntc_config* cfg, ntc_engine** out)
 	}
 	for (size_t ki = 0; ki < e->klist.size(); ++ki) {
 		std::vector<uint32_t> t1((size_t)ntc::t2_pairs(e->klist[ki]) * 64);
-		const uint32_t gap_first = (e->klist[ki] - e->gap) / 2; // "1"x(k-g)/2 "0"xg "1"x(k-g)/2, ntcard.cpp:407-413
-		ntc::build_t2(e->klist[ki], t1.data(), gap_first, e->gap);
+		ntc::build_t2(e->klist[ki], t1.data(), e->plain(ki) ? nullptr : e->masks[ki].c_str());
 		void* d = nullptr;
 		if (hipMalloc(&d, t1.size() * 4) != hipSuccess || hipMemcpy(d, t1.data(), t1.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
 			ntc_destroy(e);
@@ -1270,10 +1387,11 @@ int ntc_create(const ntc_config* cfg, ntc_engine** out)
 		}
 		e->d_t1.push_back(d);
 	}
-	if (e->gap) {
-		std::vector<uint32_t> gt((size_t)((e->gap + 1) / 2) * 64);
-		ntc::build_gap_table(e->klist[0], (e->klist[0] - e->gap) / 2, e->gap, gt.data());
-		if (hipMalloc(&e->d_gapt, gt.size() * 4) != hipSuccess || hipMemcpy(e->d_gapt, gt.data(), gt.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+	e->d_seedt.assign(e->klist.size(), nullptr);
+	for (size_t ki = 0; ki < e->klist.size(); ++ki) {
+		if (e->plain(ki)) continue;
+		const auto& blob = e->seeds[ki].blob;
+		if (hipMalloc(&e->d_seedt[ki], blob.size() * 4) != hipSuccess || hipMemcpy(e->d_seedt[ki], blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
 			ntc_destroy(e);
 			return fail(NTC_ERR_MEMORY, "ntc_create: cannot allocate the spaced-seed table on device");
 		}
@@ -1323,7 +1441,7 @@ int ntc_create(const ntc_config* cfg, ntc_engine** out)
 	e->ts_ok = false;
 	e->ts_all = ts_pre;
 	for (size_t ki = 0; ki < e->klist.size(); ++ki) {
-		e->k_tiled[ki] = ts_pre && ntc::sketch_k1h_supports(e->klist[ki], e->gap, e->s_bits, e->r_bits) ? 1 : 0;
+		e->k_tiled[ki] = ts_pre && (e->plain(ki) || e->kgap[ki] != 0) && ntc::sketch_k1h_supports(e->klist[ki], e->kgap[ki], e->s_bits, e->r_bits) ? 1 : 0;
 		e->ts_ok = e->ts_ok || e->k_tiled[ki];
 		e->ts_all = e->ts_all && e->k_tiled[ki];
 	}
@@ -1333,9 +1451,9 @@ int ntc_create(const ntc_config* cfg, ntc_engine** out)
 		if (!e->k_tiled[ki]) continue;
 		const uint32_t k = e->klist[ki];
 		std::vector<uint32_t> t4((size_t)ntc::t4_groups(k) * 256 * 4); // K1f: both strands' 64-bit terms, 4 bases per entry
-		ntc::build_t4(k, t4.data(), (k - e->gap) / 2, e->gap);
+		ntc::build_t4(k, t4.data(), e->plain(ki) ? nullptr : e->masks[ki].c_str());
 		std::vector<uint32_t> tab((size_t)2 * ((k + 2) / 3) * 64);     // K1h's resolve pass: the low r_bits + sample bits, 3 bases per entry
-		ntc::build_k1h_table(k, e->gap, e->r_bits, e->s_bits, tab.data());
+		ntc::build_k1h_table(k, e->kgap[ki], e->r_bits, e->s_bits, tab.data());
 		void* d4 = nullptr;
 		uint32_t* d3 = nullptr;
 		if (hipMalloc(&d4, t4.size() * 4) != hipSuccess || hipMemcpy(d4, t4.data(), t4.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -1361,6 +1479,10 @@ int ntc_create(const ntc_config* cfg, ntc_engine** out)
 	*out = e;
 	return 0;
 }
+
+} // namespace
+
+extern "C" {
 
 void ntc_destroy(ntc_engine* e)
 {
@@ -1408,7 +1530,8 @@ void ntc_destroy(ntc_engine* e)
 		(void)hipEventDestroy(pr.second);
 	}
 	for (void* d : e->d_t1) (void)hipFree(d);
-	if (e->d_gapt) (void)hipFree(e->d_gapt);
+	for (void* d : e->d_seedt)
+		if (d) (void)hipFree(d);
 	if (e->d_hll_thr) (void)hipFree(e->d_hll_thr);
 	for (auto& sl : e->stage) {
 		if (sl.d_stage) (void)hipFree(sl.d_stage);
@@ -1661,7 +1784,7 @@ template <class LenFn, class PtrFn> int submit_rows(ntc_engine* e, uint64_t n_re
 	if (maxlen < kmin) return 0; // nothing can produce a k-mer (ntHashIterator.hpp:61-64)
 	const uint32_t cap_chunk = std::max<uint32_t>(kSlotCapMin, ((2 * kmax + 64) + 3) & ~3u);
 	const bool chunked = maxlen > cap_chunk;
-	const uint32_t stride = pick_stride(chunked ? cap_chunk : maxlen, e->klist, e->gap);
+	const uint32_t stride = pick_stride(chunked ? cap_chunk : maxlen, e->klist, e->max_seed_lds);
 	const uint32_t ch = cap_chunk - (kmax - 1); // window starts per chunk
 	uint64_t n_slots = 0;
 	if (!chunked) {
@@ -2097,7 +2220,7 @@ int ntc_merge_devices(ntc_engine* const* engines, int32_t n_engines)
 	if (!root) return fail(NTC_ERR_ARG, "ntc_merge_devices: null engine");
 	for (int32_t i = 0; i < n_engines; ++i) {
 		ntc_engine* e = engines[i];
-		if (!e || e->klist != root->klist || e->gap != root->gap || e->r_bits != root->r_bits || e->s_bits != root->s_bits || e->hll_bits != root->hll_bits)
+		if (!e || e->klist != root->klist || e->masks != root->masks || e->r_bits != root->r_bits || e->s_bits != root->s_bits || e->hll_bits != root->hll_bits)
 			return fail(NTC_ERR_ARG, "ntc_merge_devices: engine %d is not configured like engine 0", i);
 		for (int32_t j = 0; j < i; ++j)
 			if (engines[j] == e) return fail(NTC_ERR_ARG, "ntc_merge_devices: engine %d listed twice", i);
@@ -2344,15 +2467,43 @@ int ntc_hash_dump_k1_device(int32_t device, void* stream, const void* d_slots, u
 	if (gap != 0 && (gap % 2 != k % 2 || gap >= k)) return fail(NTC_ERR_ARG, "ntc_hash_dump_k1_device: gap size and kmer must have the same modulus");
 	if ((stride & 3u) || stride < read_len || ((uintptr_t)d_slots & 15u))
 		return fail(NTC_ERR_ARG, "ntc_hash_dump_k1_device: need 16-byte aligned slots, stride %% 4 == 0, stride >= read_len");
+	return dump_k1(device, stream, d_slots, n_reads, read_len, stride, k, gap ? ntc::gap_mask(k, gap) : std::string(), max_win, d_hash_out, d_count_out);
+}
+
+int ntc_hash_dump_seed_device(int32_t device, void* stream, const void* d_slots, uint64_t n_reads, uint32_t read_len,
+                              uint32_t stride, const char* seed, uint32_t max_win, void* d_hash_out, void* d_count_out)
+{
+	if (!d_slots || !d_hash_out || !d_count_out || !seed) return fail(NTC_ERR_ARG, "ntc_hash_dump_seed_device: null argument");
+	const size_t k = strnlen(seed, (size_t)kMaxK + 1);
+	if (k < 1 || k > kMaxK) return fail(NTC_ERR_ARG, "ntc_hash_dump_seed_device: seed length outside 1..%u", kMaxK);
+	for (size_t j = 0; j < k; ++j)
+		if (seed[j] != '0' && seed[j] != '1') return fail(NTC_ERR_ARG, "ntc_hash_dump_seed_device: character %zu of the seed is neither '0' nor '1'", j + 1);
+	const std::string mask(seed, k);
+	if (mask.find('1') == std::string::npos) return fail(NTC_ERR_ARG, "ntc_hash_dump_seed_device: the seed has no '1'");
+	if ((stride & 3u) || stride < read_len || ((uintptr_t)d_slots & 15u))
+		return fail(NTC_ERR_ARG, "ntc_hash_dump_seed_device: need 16-byte aligned slots, stride %% 4 == 0, stride >= read_len");
+	return dump_k1(device, stream, d_slots, n_reads, read_len, stride, (uint32_t)k, mask.find('0') == std::string::npos ? std::string() : mask, max_win,
+	               d_hash_out, d_count_out);
+}
+
+} // extern "C"
+
+namespace {
+// K1's validation build over a batch: mask empty = plain k-mers (the arguments are checked)
+int dump_k1(int32_t device, void* stream, const void* d_slots, uint64_t n_reads, uint32_t read_len, uint32_t stride, uint32_t k, const std::string& mask,
+            uint32_t max_win, void* d_hash_out, void* d_count_out)
+{
 	if (n_reads == 0) return 0;
 	HIP_TRY(hipSetDevice(device));
 	if (int rc = ensure_kernel_attrs(device)) return rc;
 	hipStream_t st = (hipStream_t)stream;
 	const uint32_t n_win = read_len >= k ? read_len - k + 1 : 1;
-	const uint32_t gap_first = (k - gap) / 2;
-	std::vector<uint32_t> t1((size_t)ntc::t2_pairs(k) * 64), gt((size_t)((gap + 1) / 2) * 64);
-	ntc::build_t2(k, t1.data(), gap_first, gap);
-	if (gap) ntc::build_gap_table(k, gap_first, gap, gt.data());
+	std::vector<uint32_t> t1((size_t)ntc::t2_pairs(k) * 64);
+	ntc::build_t2(k, t1.data(), mask.empty() ? nullptr : mask.c_str());
+	ntc::SeedPlan sp;
+	if (!mask.empty()) ntc::build_seed_plan(mask, sp);
+	const std::vector<uint32_t>& gt = sp.blob;
+	const bool gap = !mask.empty();
 	void *d_t1 = nullptr, *d_gt = nullptr;
 	uint64_t* d_full = nullptr;
 	uint32_t* d_valid = nullptr;
@@ -2383,16 +2534,13 @@ int ntc_hash_dump_k1_device(int32_t device, void* stream, const void* d_slots, u
 		a.r_bits = 27;
 		a.s_bits = 7;
 		a.n_k = 1;
-		a.gap = gap;
-		a.gap_first = gap_first;
-		a.gapt = d_gt;
-		if (gap) ntc::build_gap_roll_table(k, gap_first, gap, a.tabg);
+		if (gap) set_seed_args(a, sp, d_gt);
 		fill_hfk(a.ks[0], k, nullptr, d_f1, d_t1);
 		a.dump = d_full;
 		a.dump_valid = d_valid;
 		a.dump_win = n_win;
 		HfPlan hp;
-		if (int r = hf_plan(device, n_reads, stride, &k, 1, gap, hp)) return r;
+		if (int r = hf_plan(device, n_reads, stride, &k, 1, seed_lds(sp), hp)) return r;
 		HIP_TRY(ntc::launch_sketch_hf(a, hp.grid, hp.wpb, hp.smem, st));
 		HIP_TRY(ntc::launch_compact_dump(d_full, d_valid, n_reads, n_win, max_win, (uint64_t*)d_hash_out, (uint32_t*)d_count_out, st));
 		HIP_TRY(hipStreamSynchronize(st));
@@ -2402,6 +2550,10 @@ int ntc_hash_dump_k1_device(int32_t device, void* stream, const void* d_slots, u
 	cleanup();
 	return rc;
 }
+
+} // namespace
+
+extern "C" {
 
 int ntc_gen_reads_device(int32_t device, void* stream, void* d_slots, uint64_t seed, uint64_t first_read,
                          uint64_t n_reads, uint32_t read_len, uint32_t stride, uint32_t dist, uint64_t genome_len)
@@ -2433,6 +2585,9 @@ int ntc_hll_create(uint32_t k, uint32_t n_bits, int32_t device, void* stream, nt
 	e->device = device;
 	e->stream = (hipStream_t)stream;
 	e->klist.assign(1, k);
+	e->masks.assign(1, std::string());
+	e->kgap.assign(1, 0u);
+	e->seeds.assign(1, ntc::SeedPlan());
 	e->r_bits = 27;
 	e->s_bits = 7;
 	e->hll_bits = n_bits;

@@ -54,7 +54,7 @@ struct HfArgs {
 	uint32_t stride, read_len;
 	uint32_t r_bits, s_bits;
 	uint32_t n_k;               // 1..kMaxFusedK
-	uint32_t gap, gap_first;    // spaced seed: single k only
+	uint32_t gap;               // spaced seed (single k only): number of don't-care positions of the mask (SeedPlan::n_dc)
 	uint32_t hll_bits;          // nthll mode: single k only
 	uint32_t log_regions, log_region_cap; // hit log geometry (0 regions: ntComp's increment is a direct device atomic)
 	uint32_t* log;              // [log_regions][log_region_cap] counter indices of sampled k-mers, relative to sketch0
@@ -66,10 +66,13 @@ struct HfArgs {
 	uint32_t* dump_valid;       //   [n_slots][ceil(dump_win / 32)] bit set where a hash was written (window without a non-ACGTU byte)
 	uint32_t dump_win;
 	uint32_t tiled;             // the batch is in the TILED layout below (stride = 16 n_chunks is the LDS slot size): the wave's 64 reads are one lane group of a tile
-	const void* gapt;
+	const void* gapt;           // spaced seed: SeedPlan::blob (XOR-out tables, further toggle tables, position words), staged in LDS
 	const uint32_t* hll_thr;
-	uint32_t tabg[kMainSlots][2]; // spaced seed, rolling form: per (leaving, entering) base pair of the don't-care block
+	uint32_t tabg[kMainSlots][2]; // spaced seed, rolling form: toggle pair 0 (SeedPlan::tabg)
 	HfK ks[kMaxFusedK];
+	uint32_t seed_nroll;        // spaced seed: toggle pairs of the rolling form (0: every wave takes the closed-form XOR-out)
+	uint32_t seed_extra;        // spaced seed: bytes of the blob behind its XOR-out tables (SeedPlan::extra_bytes)
+	uint32_t roll_t[kMaxRollPairs]; // spaced seed: toggle pair p = t_a | t_b << 16 (bytes q - k + t of step q)
 };
 
 // TILED slot layout (ntc_submit_tiled_device): tile t = reads [2048 t, 2048 t + 2048); the 16 raw bytes of bases [16 c, 16 c + 16) of read r

@@ -105,7 +105,7 @@ __device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_bal
 } // namespace
 
 // kMulti = false: exactly one k (the loop over the k list folds away and every per-k value is a launch constant)
-// kMode: 0 plain k-mers, 1 spaced seed (-g), 2 nthll — separate instantiations keep each one's register budget
+// kMode: 0 plain k-mers, 1 spaced seed (any mask; ntcard's -g seed is the one-run case), 2 nthll — separate instantiations keep each one's register budget
 // free of the other modes' state (the spaced-seed walks cost the plain kernel 5 spilled VGPRs otherwise)
 // kPref: 1 KiB chunks of the NEXT batch a wave keeps in flight in registers (10 covers slots of up to 160 B at 16 waves
 // per CU; 16 covers 256 B slots, whose LDS footprint allows 12 waves at most, hence the smaller launch bound)
@@ -146,8 +146,10 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 	for (uint32_t j = 0; j < (uint32_t)kMaxFusedK; ++j)
 		t1_off[j + 1] = t1_off[j] + (j < n_k ? ((a.ks[j].k + 1u) >> 1) * 256u : 0u);
 	// dynamic LDS: [closed-form tables of every fused k][gap table][16 B pad][waves x 64 slots].  The tables come first:
-	// with 1280 B of static LDS in front they start 256-byte aligned, so `index | base` addresses them.
-	const uint32_t tables_bytes = t1_off[kMaxFusedK] + ((a.gap + 1u) >> 1) * 256u;
+	// with 1280 B of static LDS in front they start 256-byte aligned, so `index | base` addresses them.  The gap table of a
+	// spaced seed is SeedPlan::blob: XOR-out pair tables, the toggle tables beyond pair 0, the XOR-out position words.
+	const uint32_t seed_extra = kMode == 1 ? a.seed_extra : 0u;
+	const uint32_t tables_bytes = t1_off[kMaxFusedK] + ((a.gap + 1u) >> 1) * 256u + seed_extra;
 	unsigned char* const wdata = smem + tables_bytes + 16 + (size_t)wave * 64u * stride;
 	const unsigned char* const mine = wdata + (size_t)lane * stride;
 	unsigned char* const t1_base = smem;
@@ -156,6 +158,9 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 	// spaced seed (stRead, ntcard.cpp:160-171): per pair of don't-care positions, the H halves of the terms to XOR out
 	const uint32_t ngp = (a.gap + 1u) >> 1;
 	unsigned char* const gapT = t1_base + t1_off[kMaxFusedK];
+	const uint32_t nroll = kMode == 1 ? a.seed_nroll : 0u;
+	const unsigned char* const rollT = gapT + ngp * 256u; // toggle tables of pairs 1 .. nroll-1 (pair 0: tabG)
+	const uint32_t* const dcw = reinterpret_cast<const uint32_t*>(rollT + (nroll > 1u ? nroll - 1u : 0u) * 256u); // [ngp] d | d' << 16
 	// Sample 0 of ntComp wants the top sBits+1 bits of min(fh,rh) to be 0..01.  Both strands are carried with
 	// that one bit flipped (folded into the step table: x' = x ^ c rolls with the term t ^ c ^ rotl(c)), so the
 	// test becomes min(f',r') < c: a superset (extra: one strand 0..01 while the other is 0..00, p = 2^-2(sBits+1)),
@@ -178,7 +183,7 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 			for (int i = tid; i < kMainSlots * 4; i += (int)blockDim.x)
 				tabG[i] = (i & 3) < 2 ? a.tabg[i >> 2][i & 3] : 0u;
 		const uint4* gsrc = reinterpret_cast<const uint4*>(a.gapt);
-		for (uint32_t i = tid; i < ngp * 16u; i += blockDim.x)
+		for (uint32_t i = tid; i < ngp * 16u + seed_extra / 16u; i += blockDim.x)
 			reinterpret_cast<uint4*>(gapT)[i] = gsrc[i];
 	}
 	__syncthreads();
@@ -360,7 +365,8 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 		// wave classes: CLEAN (equal lengths, no dirty byte), DIRTY (equal lengths, some non-ACGTU byte),
 		// RAGGED (lanes end at different steps, e.g. the last partial batch or a ragged host batch)
 		constexpr int CLEAN = 0, DIRTY = 1, RAGGED = 2;
-		const int wclass = minq != maxq ? RAGGED : (wave_dirty ? DIRTY : CLEAN);
+		// (a mask with more toggle pairs than the rolling form takes walks every wave as RAGGED: the closed-form XOR-out)
+		const int wclass = minq != maxq || (kMode == 1 && nroll == 0u) ? RAGGED : (wave_dirty ? DIRTY : CLEAN);
 
 		// The walk starts from the H halves of the hash of k virtual 'A's and feeds 'A' as the outgoing
 		// base of the first k steps, so ONE step body serves window filling and steady state.
@@ -539,7 +545,17 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 		// Sampled steps are recorded without a branch: every step from the first non-FILL group on shifts
 		// the lane's mask left and shifts the wave's "sampled" condition in as carry (one v_addc_co_u32);
 		// after 32 steps the mask is compacted into the resolve queue.  The block's last step sits at bit 0.
-		auto push = [&](uint64_t m) { asm volatile("v_addc_co_u32_e64 %0, %1, %0, %0, %1" : "+v"(hmask), "+s"(m)); };
+		auto push = [&](uint64_t m) {
+			if constexpr (kDump) {
+				// the validation build's m is ballot(true), i.e. EXEC itself: with a tied in/out operand the compiler wrote the carry-out over EXEC
+				// (v_addc_co_u32_e64 v, exec, v, v, exec), which switched off every lane whose mask had no carry — in a DIRTY wave, after the
+				// first recorded step.  Carry in from m, carry out to a register of its own.
+				uint64_t co;
+				asm volatile("v_addc_co_u32_e64 %0, %1, %0, %0, %2" : "+v"(hmask), "=&s"(co) : "s"(m));
+			} else {
+				asm volatile("v_addc_co_u32_e64 %0, %1, %0, %0, %1" : "+v"(hmask), "+s"(m));
+			}
+		};
 		const int32_t qs = e0 << 2; // first step that is recorded
 		uint32_t f1_lane = 0;       // DIRTY / RAGGED: clean windows of this lane (accumulated on the rare path)
 
@@ -562,10 +578,11 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 				if (emitting) {
 					uint32_t fs = fHd, rs = rHd;
 					if (gapped.value && wc.value == RAGGED) {
-						// NTMSM64 (nthash.hpp:641-646,665-670): XOR the don't-care bases' rotated seeds back out
-						const unsigned char* gp = mine + (q - (int32_t)k + 1 + (int32_t)a.gap_first);
+						// NTMSM64 (nthash.hpp:641-646,665-670): XOR the don't-care bases' rotated seeds back out, two positions per lookup
+						const unsigned char* gp = mine + (q - (int32_t)k + 1);
 						for (uint32_t p = 0; p < ngp; ++p) {
-							const uint32_t off = (gp[2 * p] & 0xc0u) | ((gp[2 * p + 1] >> 2) & 0x30u);
+							const uint32_t dw = dcw[p];
+							const uint32_t off = (gp[dw & 0xffffu] & 0xc0u) | ((gp[dw >> 16] >> 2) & 0x30u);
 							const uint2 g = *reinterpret_cast<const uint2*>(gapT + p * 256u + off);
 							fs ^= g.x;
 							rs ^= g.y;
@@ -590,18 +607,32 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 					issue(group_idx(kind, q0, ain), T);
 					constexpr bool kGapRoll = gapped.value && wc.value != RAGGED; // equal lengths: the spaced value itself rolls
 					if (kGapRoll) {
-						// the bases leaving / entering the don't-care block during the 4 steps of this group
-						const int32_t o1 = q0 - (int32_t)k + (int32_t)a.gap_first, o2 = o1 + (int32_t)a.gap;
-						const uint32_t* p1 = reinterpret_cast<const uint32_t*>(mine + (o1 & ~3));
-						const uint32_t* p2 = reinterpret_cast<const uint32_t*>(mine + (o2 & ~3));
-						const uint32_t w1 = alignbyte(p1[1], p1[0], (uint32_t)o1 & 3u);
-						const uint32_t w2 = alignbit(p2[1], p2[0], 8u * ((uint32_t)o2 & 3u) + 2u); // aligned and >> 2 in one funnel shift
-						uint32_t ig = (w1 & 0xc0c0c0c0u) | (w2 & 0x3f3f3f3fu);
-						asm volatile("" : "+v"(ig));
-						TG.t[0] = *reinterpret_cast<const uint2*>(tabGb + (ig & 0xffu));
-						TG.t[1] = *reinterpret_cast<const uint2*>(tabGb + ((ig >> 8) & 0xffu));
-						TG.t[2] = *reinterpret_cast<const uint2*>(tabGb + ((ig >> 16) & 0xffu));
-						TG.t[3] = *reinterpret_cast<const uint2*>(tabGb + (ig >> 24));
+						// the bases whose term toggles during the 4 steps of this group, two per lookup (SeedPlan: the boundaries of
+						// the mask's runs of '0's, and the window's ends where such a run touches them); ntcard's -g seed: one pair,
+						// the bases leaving / entering its don't-care block
+#pragma unroll
+						for (uint32_t p = 0; p < kMaxRollPairs; ++p) {
+							if (p > 0 && p >= nroll) break;
+							const uint32_t tw = a.roll_t[p];
+							const int32_t o1 = q0 - (int32_t)k + (int32_t)(tw & 0xffffu), o2 = q0 - (int32_t)k + (int32_t)(tw >> 16);
+							const uint32_t* p1 = reinterpret_cast<const uint32_t*>(mine + (o1 & ~3));
+							const uint32_t* p2 = reinterpret_cast<const uint32_t*>(mine + (o2 & ~3));
+							const uint32_t w1 = alignbyte(p1[1], p1[0], (uint32_t)o1 & 3u);
+							const uint32_t w2 = alignbit(p2[1], p2[0], 8u * ((uint32_t)o2 & 3u) + 2u); // aligned and >> 2 in one funnel shift
+							uint32_t ig = (w1 & 0xc0c0c0c0u) | (w2 & 0x3f3f3f3fu);
+							asm volatile("" : "+v"(ig));
+							const unsigned char* tg = p == 0 ? tabGb : rollT + (p - 1u) * 256u;
+							uint2 v[4];
+							v[0] = *reinterpret_cast<const uint2*>(tg + (ig & 0xffu));
+							v[1] = *reinterpret_cast<const uint2*>(tg + ((ig >> 8) & 0xffu));
+							v[2] = *reinterpret_cast<const uint2*>(tg + ((ig >> 16) & 0xffu));
+							v[3] = *reinterpret_cast<const uint2*>(tg + (ig >> 24));
+#pragma unroll
+							for (int b = 0; b < 4; ++b) {
+								TG.t[b].x = p == 0 ? v[b].x : TG.t[b].x ^ v[b].x;
+								TG.t[b].y = p == 0 ? v[b].y : TG.t[b].y ^ v[b].y;
+							}
+						}
 					}
 					auto step = [&](int b) {
 						if (kGapRoll)
@@ -657,9 +688,16 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 				}
 				const uint32_t off = (ain & 0xc0u) | (q >= (int32_t)k ? ((mine[q - (int32_t)k] >> 2) & 0x30u) : 0u);
 				if (gapped.value && wc.value != RAGGED) { // only reached with q >= k (closed-form start)
-					const int32_t o1 = q - (int32_t)k + (int32_t)a.gap_first;
-					const uint32_t og = (mine[o1] & 0xc0u) | ((mine[o1 + (int32_t)a.gap] >> 2) & 0x30u);
-					roll2(*reinterpret_cast<const uint2*>(tabHb + off), *reinterpret_cast<const uint2*>(tabGb + og));
+					uint2 g = make_uint2(0u, 0u);
+					for (uint32_t p = 0; p < nroll; ++p) {
+						const uint32_t tw = a.roll_t[p];
+						const int32_t o1 = q - (int32_t)k + (int32_t)(tw & 0xffffu), o2 = q - (int32_t)k + (int32_t)(tw >> 16);
+						const uint32_t og = (mine[o1] & 0xc0u) | ((mine[o2] >> 2) & 0x30u);
+						const uint2 v = *reinterpret_cast<const uint2*>((p == 0 ? tabGb : rollT + (p - 1u) * 256u) + og);
+						g.x ^= v.x;
+						g.y ^= v.y;
+					}
+					roll2(*reinterpret_cast<const uint2*>(tabHb + off), g);
 				} else {
 					roll(*reinterpret_cast<const uint2*>(tabHb + off));
 				}

@@ -44,6 +44,8 @@ void usage(std::ostream& os)
 	   << "  -c, --cov=N\tlargest coverage reported [1000]\n"
 	   << "  -p, --pref=STRING\tprefix of the per-k output files <STRING>_k<k>.hist\n"
 	   << "  -o, --output=STRING\tsingle tab separated output file (k, f, n)\n"
+	   << "      --seed=MASK[,MASK...]\tspaced seeds instead of -k / -g: strings of 0 (don't care) and 1 (counted), one spectrum each;\n"
+	   << "\t\toutput files <STRING>_seed<i>_k<length>.hist, or -o rows (seed, f, n) with i = 1, 2, ...\n"
 	   << "      --help\tdisplay this help and exit\n"
 	   << "      --version\toutput version information and exit\n";
 }
@@ -56,6 +58,8 @@ struct Options {
 	unsigned cov_max = 1000;
 	std::string prefix, output;
 	std::vector<unsigned> klist;
+	bool gap_given = false;
+	std::vector<std::string> seeds; // --seed: masks of '0' / '1' (include/ntcard_hip.h: ntc_create_seeded)
 };
 
 void process_file(const std::string& path, ntc_engine* eng)
@@ -85,7 +89,7 @@ int main(int argc, char** argv)
 {
 	const auto t_start = std::chrono::steady_clock::now();
 	static const char shortopts[] = "t:s:r:k:c:l:p:f:o:g:";
-	enum { OPT_HELP = 1, OPT_VERSION };
+	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED };
 	static const struct option longopts[] = { { "threads", required_argument, nullptr, 't' },
 		                                      { "kmer", required_argument, nullptr, 'k' },
 		                                      { "gap", required_argument, nullptr, 'g' },
@@ -96,6 +100,7 @@ int main(int argc, char** argv)
 		                                      { "pref", required_argument, nullptr, 'p' },
 		                                      { "help", no_argument, nullptr, OPT_HELP },
 		                                      { "version", no_argument, nullptr, OPT_VERSION },
+		                                      { "seed", required_argument, nullptr, OPT_SEED },
 		                                      { nullptr, 0, nullptr, 0 } };
 	Options opt;
 	bool die = false;
@@ -112,7 +117,20 @@ int main(int argc, char** argv)
 			break;
 		case 'p': clean = parse_value(optarg, opt.prefix); break;
 		case 'o': clean = parse_value(optarg, opt.output); break;
-		case 'g': clean = parse_value(optarg, opt.gap); break;
+		case 'g':
+			clean = parse_value(optarg, opt.gap);
+			opt.gap_given = true;
+			break;
+		case OPT_SEED: {
+			const std::string arg(optarg ? optarg : "");
+			for (size_t b = 0;;) { // every comma-separated field, empty ones included (reported below)
+				const size_t e = arg.find(',', b);
+				opt.seeds.push_back(arg.substr(b, e == std::string::npos ? std::string::npos : e - b));
+				if (e == std::string::npos) break;
+				b = e + 1;
+			}
+			break;
+		}
 		case 'k': {
 			std::istringstream arg(optarg ? optarg : "");
 			std::string token;
@@ -144,7 +162,25 @@ int main(int argc, char** argv)
 		std::cerr << PROGRAM << "Gap size and kmer must have the same modulus\n";
 		die = true;
 	}
-	if (opt.klist.empty()) {
+	const bool seeded = !opt.seeds.empty();
+	if (seeded && (!opt.klist.empty() || opt.gap_given)) {
+		std::cerr << PROGRAM << ": --seed cannot be combined with -k or -g\n";
+		die = true;
+	}
+	for (const std::string& m : opt.seeds) {
+		if (m.empty() || m.find_first_not_of("01") != std::string::npos || m.find('1') == std::string::npos) {
+			std::cerr << PROGRAM << ": --seed: `" << m << "' is not a mask of 0 and 1 with at least one 1\n";
+			die = true;
+		} else if (m.size() > ntc_max_k()) {
+			std::cerr << PROGRAM << ": --seed: a mask of " << m.size() << " positions is longer than the " << ntc_max_k() << " this GPU engine supports\n";
+			die = true;
+		}
+	}
+	if (opt.seeds.size() > NTC_MAX_K_LIST) {
+		std::cerr << PROGRAM << ": at most " << NTC_MAX_K_LIST << " seeds per run\n";
+		die = true;
+	}
+	if (opt.klist.empty() && !seeded) {
 		std::cerr << PROGRAM << ": missing argument -k ... \n";
 		die = true;
 	}
@@ -193,10 +229,16 @@ int main(int argc, char** argv)
 	}
 	if (total < 50000000000ULL) opt.s_bits = 7;
 
+	std::vector<const char*> seed_ptrs;
+	if (seeded) // one spectrum per seed; its k is the mask's length (output file names)
+		for (const auto& m : opt.seeds) {
+			opt.klist.push_back((unsigned)m.size());
+			seed_ptrs.push_back(m.c_str());
+		}
 	ntc_config cfg;
 	std::memset(&cfg, 0, sizeof cfg);
-	cfg.n_k = (uint32_t)opt.klist.size();
-	cfg.k = opt.klist.data();
+	cfg.n_k = seeded ? 0u : (uint32_t)opt.klist.size();
+	cfg.k = seeded ? nullptr : opt.klist.data();
 	cfg.gap = opt.gap;
 	cfg.r_bits = opt.r_bits;
 	cfg.s_bits = opt.s_bits;
@@ -214,7 +256,8 @@ int main(int argc, char** argv)
 	std::vector<ntc_engine*> engines(devices.size(), nullptr);
 	for (size_t d = 0; d < devices.size(); ++d) {
 		cfg.device = devices[d];
-		if (ntc_create(&cfg, &engines[d]) != 0) die_engine();
+		const int rc = seeded ? ntc_create_seeded(&cfg, (uint32_t)seed_ptrs.size(), seed_ptrs.data(), &engines[d]) : ntc_create(&cfg, &engines[d]);
+		if (rc != 0) die_engine();
 	}
 	ntc_engine* eng = engines[0];
 
@@ -249,7 +292,9 @@ int main(int argc, char** argv)
 			double F0 = 0;
 			if (ntc_estimate(&p[ki * 2 * 65536], opt.r_bits, opt.s_bits, opt.cov_max, &F0, f.data()) != 0) die_engine();
 			std::ostringstream name;
-			name << opt.prefix << "_k" << opt.klist[ki] << ".hist";
+			name << opt.prefix;
+			if (seeded) name << "_seed" << ki + 1;
+			name << "_k" << opt.klist[ki] << ".hist";
 			if (ntc_write_hist(name.str().c_str(), f1[ki], F0, f.data(), opt.cov_max) != 0) {
 				std::cerr << PROGRAM << ": cannot write " << name.str() << "\n";
 				return EXIT_FAILURE;
@@ -261,14 +306,16 @@ int main(int argc, char** argv)
 			std::cerr << PROGRAM << ": cannot write " << opt.output << "\n";
 			return EXIT_FAILURE;
 		}
-		std::fprintf(out, "k\tf\tn\n");
+		std::fprintf(out, seeded ? "seed\tf\tn\n" : "k\tf\tn\n");
 		for (size_t ki = 0; ki < nk; ++ki) {
 			double F0 = 0;
 			if (ntc_estimate(&p[ki * 2 * 65536], opt.r_bits, opt.s_bits, opt.cov_max, &F0, f.data()) != 0) die_engine();
-			std::cerr << "k=" << opt.klist[ki] << "\tF1\t" << f1[ki] << "\n";
-			std::cerr << "k=" << opt.klist[ki] << "\tF0\t" << (uint64_t)F0 << "\n";
+			const unsigned label = seeded ? (unsigned)ki + 1 : opt.klist[ki]; // --seed: the 1-based seed index
+			const char* const tag = seeded ? "seed=" : "k=";
+			std::cerr << tag << label << "\tF1\t" << f1[ki] << "\n";
+			std::cerr << tag << label << "\tF0\t" << (uint64_t)F0 << "\n";
 			for (unsigned i = 1; i <= opt.cov_max; ++i)
-				std::fprintf(out, "%u\t%u\t%llu\n", opt.klist[ki], i, (unsigned long long)(uint64_t)f[i]);
+				std::fprintf(out, "%u\t%u\t%llu\n", label, i, (unsigned long long)(uint64_t)f[i]);
 		}
 		std::fclose(out);
 	}

@@ -17,6 +17,8 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <string>
+#include <vector>
 
 namespace ntc {
 
@@ -95,9 +97,19 @@ inline void poly_a_state(unsigned k, uint32_t out[6])
 // as {fwd.lo, fwd.hi, rev.lo, rev.hi} (nthash.hpp:220-239: fh = XOR_i srol^(k-1-i) seed(c_i), rh = XOR_i srol^i comp(c_i)).
 // For odd k the last pair has no second base (its b term is dropped).  Entry offset: j*256 + (a*4+b)*16 bytes.
 inline unsigned t2_pairs(unsigned k) { return (k + 1) / 2; }
-inline void build_t2(unsigned k, uint32_t* out /* t2_pairs(k)*16*4 dwords */, unsigned gap_first = 0, unsigned gap = 0)
+// A spaced seed as a mask of k characters: '1' = the base at that window offset enters the hash, '0' = don't care
+// (stHashIterator::parseSeed, stHashIterator.hpp:23-33).  ntcard's -g seed is 1^((k-g)/2) 0^g 1^((k-g)/2) (ntcard.cpp:407-413).
+inline std::string gap_mask(unsigned k, unsigned gap)
 {
-	auto dc = [&](unsigned i) { return i >= gap_first && i < gap_first + gap; }; // don't-care position of a spaced seed
+	std::string m(k, '1');
+	for (unsigned i = (k - gap) / 2; i < (k - gap) / 2 + gap; ++i)
+		m[i] = '0';
+	return m;
+}
+// mask == nullptr: every position is cared for
+inline void build_t2(unsigned k, uint32_t* out /* t2_pairs(k)*16*4 dwords */, const char* mask)
+{
+	auto dc = [&](unsigned i) { return mask != nullptr && mask[i] == '0'; }; // don't-care position of a spaced seed
 	for (unsigned j = 0; j < t2_pairs(k); ++j)
 		for (unsigned a = 0; a < 4; ++a)
 			for (unsigned b = 0; b < 4; ++b) {
@@ -115,12 +127,18 @@ inline void build_t2(unsigned k, uint32_t* out /* t2_pairs(k)*16*4 dwords */, un
 				e[3] = (uint32_t)(r >> 32);
 			}
 }
+inline void build_t2(unsigned k, uint32_t* out, unsigned gap_first = 0, unsigned gap = 0)
+{
+	const std::string m = gap_mask(k, gap);
+	(void)gap_first; // (always (k - gap) / 2)
+	build_t2(k, out, gap ? m.c_str() : nullptr);
+}
 
 // Closed-form table of K1b's resolve stage, FOUR bases per entry, indexed by a packed byte of 2-bit codes in
 // code2 order (code2 = (ascii >> 1) & 3: A=0 C=1 T/U=2 G=3; base t of the group in bits 2t+1:2t):
 // entry (g, v) = XOR over t < 4, i = 4 g + t < k of  srol^(k-1-i)(seed(c_t))  and  srol^i(comp(c_t))   (nthash.hpp:220-239)
 inline unsigned t4_groups(unsigned k) { return (k + 3) / 4; }
-inline void build_t4(unsigned k, uint32_t* out /* t4_groups(k)*256*4 dwords */, unsigned gap_first = 0, unsigned gap = 0)
+inline void build_t4(unsigned k, uint32_t* out /* t4_groups(k)*256*4 dwords */, const char* mask)
 {
 	static const unsigned code_of_code2[4] = { 0, 1, 3, 2 }; // code2 -> the A C G T numbering of seed_of()
 	for (unsigned g = 0; g < t4_groups(k); ++g)
@@ -129,7 +147,7 @@ inline void build_t4(unsigned k, uint32_t* out /* t4_groups(k)*256*4 dwords */, 
 			for (unsigned t = 0; t < 4; ++t) {
 				const unsigned i = 4 * g + t;
 				if (i >= k) break;
-				if (i >= gap_first && i < gap_first + gap) continue; // spaced seed: a don't-care position (nthash.hpp:641-646)
+				if (mask != nullptr && mask[i] == '0') continue; // spaced seed: a don't-care position (nthash.hpp:641-646)
 				const unsigned c = code_of_code2[(v >> (2 * t)) & 3u];
 				f ^= srol(seed_of(c), k - 1 - i);
 				r ^= srol(comp_of(c), i);
@@ -140,6 +158,12 @@ inline void build_t4(unsigned k, uint32_t* out /* t4_groups(k)*256*4 dwords */, 
 			e[2] = (uint32_t)r;
 			e[3] = (uint32_t)(r >> 32);
 		}
+}
+inline void build_t4(unsigned k, uint32_t* out, unsigned gap_first = 0, unsigned gap = 0)
+{
+	const std::string m = gap_mask(k, gap);
+	(void)gap_first; // (always (k - gap) / 2)
+	build_t4(k, out, gap ? m.c_str() : nullptr);
 }
 
 // Spaced-seed filter table: for the p-th PAIR of don't-care positions (i, i+1), entry (a, b) holds the H halves
@@ -178,6 +202,92 @@ inline void build_gap_roll_table(unsigned k, unsigned gap_first, unsigned gap, u
 			out[a * 4 + b][0] = hd_of(f);
 			out[a * 4 + b][1] = hd_of(r);
 		}
+}
+
+// ---- general spaced seeds (masks): the tables of K1's spaced-seed mode ----
+//
+// Closed-form XOR-out (ragged and dirty-free walks of unequal length): the don't-care offsets d_0 < d_1 < ... are taken in
+// PAIRS (d_2p, d_2p+1); pair p has a table like build_gap_table's, entry (a, b) = the H halves of
+//   srol^(k-1-d)(seed(a)) ^ srol^(k-1-d')(seed(b))  and  srol^d(comp(a)) ^ srol^d'(comp(b))      (nthash.hpp:641-646)
+// and a position word d | d' << 16 (an odd last offset pairs with itself and has no b term).
+//
+// Rolling form (equal-length waves): one step of the plain roll moves every base one window offset down; a base whose
+// new offset j (-1 .. k-1) is cared for now but was not before, or the other way round, toggles one term:
+//   j = -1     (the outgoing base)     when mask[0] == '0'   (the plain roll removed a term that was never there)
+//   0 <= j < k-1                       when mask[j] != mask[j+1]
+//   j = k - 1  (the incoming base)     when mask[k-1] == '0' (the plain roll added a term that must not be there)
+// With t = j + 1 (the byte q - k + t of step q), the toggled term is  f: srol^(k-t)(seed(c)) (XORed after the forward rotate),
+// r: srol^t(comp(c)) (XORed before the reverse rotate).  An interior run of '0's toggles twice per step (exactly the pair
+// build_gap_roll_table tabulates for ntcard's -g seed), a run at either end of the window twice as well (its inner boundary
+// and the end's own correction).  The toggles are looked up two at a time, one table of 16 (a, b) entries per pair.
+constexpr unsigned kMaxRollPairs = 4; // a mask with more toggle pairs walks every wave with the closed-form XOR-out (mask mode)
+
+struct SeedPlan {
+	uint32_t k = 0, n_dc = 0;          // window length, don't-care positions
+	uint32_t n_roll = 0;               // toggle pairs of the rolling form (1 .. kMaxRollPairs); 0: the closed-form XOR-out in every wave
+	uint32_t roll_t[kMaxRollPairs] = {}; // toggle pair p: t_a | t_b << 16
+	uint32_t tabg[16][2] = {};         // toggle pair 0: {f, r} H halves per (a, b); pairs 1.. are in `blob`
+	// what K1 stages in LDS behind its closed-form tables: [ceil(n_dc/2)][16] x {f.Hd, r.Hd, 0, 0} XOR-out tables,
+	// [n_roll - 1][16] x {f.Hd, r.Hd, 0, 0} toggle tables, [ceil(n_dc/2)] position words, zero padding to 16 B
+	std::vector<uint32_t> blob;
+	uint32_t extra_bytes() const { return (uint32_t)(blob.size() * 4) - (n_dc + 1) / 2 * 256u; } // the part behind the XOR-out tables
+};
+
+// mask: k characters of '0' / '1' (validated by the caller)
+inline void build_seed_plan(const std::string& mask, SeedPlan& sp)
+{
+	const unsigned k = (unsigned)mask.size();
+	sp = SeedPlan();
+	sp.k = k;
+	std::vector<unsigned> dc, tog;
+	for (unsigned i = 0; i < k; ++i)
+		if (mask[i] == '0') dc.push_back(i);
+	sp.n_dc = (uint32_t)dc.size();
+	if (mask[0] == '0') tog.push_back(0);
+	for (unsigned j = 0; j + 1 < k; ++j)
+		if (mask[j] != mask[j + 1]) tog.push_back(j + 1);
+	if (mask[k - 1] == '0') tog.push_back(k);
+	const unsigned npairs = ((unsigned)tog.size() + 1) / 2;
+	sp.n_roll = npairs <= kMaxRollPairs ? npairs : 0;
+	auto hd2 = [&](uint64_t f, uint64_t r, uint32_t* e) {
+		e[0] = hd_of(f);
+		e[1] = hd_of(r);
+		e[2] = e[3] = 0;
+	};
+	const unsigned ngp = (sp.n_dc + 1) / 2, nrx = sp.n_roll > 1 ? sp.n_roll - 1 : 0;
+	const size_t words = (size_t)(ngp + nrx) * 64 + ((ngp + 3) / 4) * 4;
+	sp.blob.assign(words, 0u);
+	for (unsigned p = 0; p < ngp; ++p) {
+		const unsigned d0 = dc[2 * p], d1 = 2 * p + 1 < dc.size() ? dc[2 * p + 1] : d0;
+		for (unsigned a = 0; a < 4; ++a)
+			for (unsigned b = 0; b < 4; ++b) {
+				uint64_t f = srol(seed_of(a), k - 1 - d0), r = srol(comp_of(a), d0);
+				if (d1 != d0) {
+					f ^= srol(seed_of(b), k - 1 - d1);
+					r ^= srol(comp_of(b), d1);
+				}
+				hd2(f, r, sp.blob.data() + ((size_t)p * 16 + a * 4 + b) * 4);
+			}
+		sp.blob[(size_t)(ngp + nrx) * 64 + p] = d0 | (d1 << 16);
+	}
+	for (unsigned p = 0; p < sp.n_roll; ++p) {
+		const unsigned ta = tog[2 * p], tb = 2 * p + 1 < tog.size() ? tog[2 * p + 1] : ta;
+		sp.roll_t[p] = ta | (tb << 16);
+		for (unsigned a = 0; a < 4; ++a)
+			for (unsigned b = 0; b < 4; ++b) {
+				uint64_t f = srol(seed_of(a), k - ta), r = srol(comp_of(a), ta);
+				if (tb != ta) {
+					f ^= srol(seed_of(b), k - tb);
+					r ^= srol(comp_of(b), tb);
+				}
+				if (p == 0) {
+					sp.tabg[a * 4 + b][0] = hd_of(f);
+					sp.tabg[a * 4 + b][1] = hd_of(r);
+				} else {
+					hd2(f, r, sp.blob.data() + ((size_t)(ngp + p - 1) * 16 + a * 4 + b) * 4);
+				}
+			}
+	}
 }
 
 } // namespace ntc

@@ -51,6 +51,32 @@ class Engine:
         h = C.c_void_p()
         check(self._lib.ntc_create(C.byref(cfg), C.byref(h)))
         self._h = h
+        self.seeds = None
+
+    @classmethod
+    def from_seeds(cls, seeds, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0):
+        """an engine whose planes are spaced seeds given as masks of '0' / '1' (include/ntcard_hip.h: ntc_create_seeded); its klist is
+        the masks' lengths, so finish, merge_counters and the rest work as for a k list"""
+        self = cls.__new__(cls)
+        self._lib = _abi.lib()
+        self.seeds = [s.decode() if isinstance(s, bytes) else str(s) for s in seeds]
+        self.klist = [len(s) for s in self.seeds]
+        self.gap, self.r_bits, self.s_bits, self.device = 0, int(r_bits), int(s_bits), int(device)
+        cfg = NtcConfig()
+        cfg.n_k, cfg.k, cfg.gap = 0, None, 0
+        cfg.r_bits, cfg.s_bits, cfg.device = self.r_bits, self.s_bits, self.device
+        cfg.stream = C.c_void_p(stream) if stream else None
+        self._keep = (ext_sketch, ext_f1)
+        cfg.ext_sketch = C.c_void_p(ext_sketch.data_ptr()) if ext_sketch is not None else None
+        cfg.ext_f1 = C.c_void_p(ext_f1.data_ptr()) if ext_f1 is not None else None
+        cfg.flags = int(flags)
+        cfg.log_entries = int(log_entries)
+        self._sarr = (C.c_char_p * len(self.seeds))(*[s.encode() for s in self.seeds])
+        h = C.c_void_p()
+        self._h = None
+        check(self._lib.ntc_create_seeded(C.byref(cfg), len(self.seeds), self._sarr, C.byref(h)))
+        self._h = h
+        return self
 
     # -- lifecycle ---------------------------------------------------------------------------
     def close(self):
@@ -316,3 +342,11 @@ def hash_dump_device(d_slots_ptr, n_reads, read_len, stride, k, gap, max_win, d_
     fn = _abi.lib().ntc_hash_dump_k1_device if k1 else _abi.lib().ntc_hash_dump_device
     check(fn(device, C.c_void_p(stream) if stream else None, C.c_void_p(d_slots_ptr), n_reads,
                                           read_len, stride, k, gap, max_win, C.c_void_p(d_hash_ptr), C.c_void_p(d_count_ptr)))
+
+
+def hash_dump_seed_device(d_slots_ptr, n_reads, read_len, stride, seed, max_win, d_hash_ptr, d_count_ptr, device=0, stream=None):
+    """every canonical spaced-seed hash of every clean window under a mask of '0' / '1', out of the production kernel K1
+    (include/ntcard_hip.h: ntc_hash_dump_seed_device)"""
+    seed = seed.encode() if isinstance(seed, str) else bytes(seed)
+    check(_abi.lib().ntc_hash_dump_seed_device(device, C.c_void_p(stream) if stream else None, C.c_void_p(d_slots_ptr), n_reads, read_len, stride, seed,
+                                               max_win, C.c_void_p(d_hash_ptr), C.c_void_p(d_count_ptr)))
