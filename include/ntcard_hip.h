@@ -86,6 +86,24 @@ typedef struct {
                                       (a small batch then costs its share of a large launch instead of a launch of its own).  Without the flag a
                                       buffer may be reused as soon as the stream has passed the submit call. */
 #define NTC_FLAG_REQUIRE_TILED 64u  /* validation: a tiled batch must be served by the tiled kernels for EVERY k of the list, else ntc_submit_tiled_device fails */
+/* ONE STRAND instead of the canonical k-mer (additive to ABI 6: two flag bits and ntc_hash_dump_strand_device; ntc_config and NTC_ABI_VERSION are unchanged).
+ * An engine has a strand: canonical (no flag, what ntcard counts), forward, or reverse.
+ *   - Which windows count is unchanged: a window of k bytes counts (F1, sketch) only when all k bytes are bases, those under a mask's '0' included,
+ *     so F1 of a read set is the same for all three strands.
+ *   - The value that goes into ntComp (ntcard.cpp:132-145) is
+ *       canonical:  rh < fh ? rh : fh                                    (nthash.hpp:275-279)
+ *       forward:    fh = XOR_i srol^(k-1-i)(seedTab[b_i])                (nthash.hpp:220-228, what NTF64 rolls)
+ *       reverse:    rh = XOR_i srol^i(seedTab[b_i & cpOff])              (nthash.hpp:231-239, NTR64): the forward value of the window's reverse complement.
+ *     For a plane that is a spaced seed (ntc_create_seeded, ntc_create with gap) fs / rs as defined there — the don't-care terms XORed out of fh / rh —
+ *     take the place of fh / rh.
+ *   - Everything behind the value is unchanged: sampling, bucket, hit log, sketch update, estimator, output.
+ * Valid with ntc_create (k lists, gap) and ntc_create_seeded; both flags together are NTC_ERR_ARG (checked before a device is looked for).  A strand engine
+ * is the general kernel's (K1, in its one-strand form: one rolling update and one table half per base instead of two) and the simple validation kernel's:
+ * the tiled kernel pair K1h + K1f is canonical only, so no k of a strand engine is theirs — tiled batches, ragged ones and bins included, are re-laid out
+ * on the device and counted by K1, NTC_FLAG_REQUIRE_TILED makes the tiled submit fail with nothing counted, host batches take row slots.  It counts at K1's
+ * rate, not at K1h's (DESIGN.md §4 "One strand").  ntc_merge_devices refuses engines whose strands differ.  ntc_hll_create has no flags: nthll is canonical. */
+#define NTC_FLAG_STRAND_FORWARD 512u
+#define NTC_FLAG_STRAND_REVERSE 1024u
 #define NTC_FLAG_DIRECT_ATOMICS 2u /* no hit log: every sampled k-mer is one device atomic on the sketch
                                       (the literal form of ntcard.cpp:142-143; cross-check and A/B runs) */
 
@@ -271,6 +289,12 @@ int ntc_hash_dump_k1_device(int32_t device, void *stream, const void *d_slots, u
  * The arguments are checked before the device is touched. */
 int ntc_hash_dump_seed_device(int32_t device, void *stream, const void *d_slots, uint64_t n_reads, uint32_t read_len,
                               uint32_t stride, const char *seed, uint32_t max_win, void *d_hash_out, void *d_count_out);
+
+/* The same with a strand: 0 the canonical value (bit for bit ntc_hash_dump_seed_device), 1 the forward value fh / fs, 2 the reverse value rh / rs of every
+ * window (NTC_FLAG_STRAND_*); anything else is NTC_ERR_ARG before the device is touched.  Strands 1 and 2 come out of the resolve stage of K1's one-strand form. */
+int ntc_hash_dump_strand_device(int32_t device, void *stream, const void *d_slots, uint64_t n_reads, uint32_t read_len,
+                                uint32_t stride, const char *seed, uint32_t strand, uint32_t max_win, void *d_hash_out,
+                                void *d_count_out);
 
 /* Synthetic workload generator (K0), bit-identical to oracle/orc_gen_reads; DESIGN.md
  * "Synthetic workloads".  Fills d_slots[n_reads*stride].                                         */

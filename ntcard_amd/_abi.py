@@ -18,7 +18,7 @@ ABI_SYMBOLS = [
     "ntc_submit_tiled_device", "ntc_submit_tiled_ragged_device", "ntc_submit_tiled_bins_device", "ntc_tiled_bytes", "ntc_gen_reads_tiled_device",
     "ntc_narrow_u16_device", "ntc_sum_slices_u16_device", "ntc_value_hist_u16_device",
     "ntc_log_export_device", "ntc_log_replace_device",
-    "ntc_create_seeded", "ntc_hash_dump_seed_device",
+    "ntc_create_seeded", "ntc_hash_dump_seed_device", "ntc_hash_dump_strand_device",
 ]
 
 
@@ -94,6 +94,7 @@ def lib():
     L.ntc_hash_dump_device.argtypes = [i32, p, p, u64, u32, u32, u32, u32, u32, p, p]
     L.ntc_hash_dump_k1_device.argtypes = [i32, p, p, u64, u32, u32, u32, u32, u32, p, p]
     L.ntc_hash_dump_seed_device.argtypes = [i32, p, p, u64, u32, u32, C.c_char_p, u32, p, p]
+    L.ntc_hash_dump_strand_device.argtypes = [i32, p, p, u64, u32, u32, C.c_char_p, u32, u32, p, p]
     L.ntc_gen_reads_device.argtypes = [i32, p, p, u64, u64, u64, u32, u32, u32, u64]
     L.ntc_estimate.argtypes = [p, u32, u32, u32, C.POINTER(C.c_double), p]
     L.ntc_write_hist.argtypes = [C.c_char_p, u64, C.c_double, p, u32]

@@ -118,7 +118,9 @@ struct HfPlan {
 };
 
 // per-k block of the K1 argument struct
-void fill_hfk(ntc::HfK& o, uint32_t k, uint32_t* sketch, unsigned long long* f1, const void* t1, uint32_t key_base = 0)
+// strand: 0 canonical; 1 forward / 2 reverse — the wanted strand's step terms and start value go FIRST, where K1's one-strand instantiations
+// read them (the reverse step terms rotated right: nthash_tables.hpp, "one strand")
+void fill_hfk(ntc::HfK& o, uint32_t k, uint32_t* sketch, unsigned long long* f1, const void* t1, uint32_t key_base = 0, uint32_t strand = 0)
 {
 	ntc::HashTables tab;
 	uint32_t init[6];
@@ -127,7 +129,7 @@ void fill_hfk(ntc::HfK& o, uint32_t k, uint32_t* sketch, unsigned long long* f1,
 	o.k = k;
 	o.init_f = init[2];
 	o.init_r = init[5];
-	o.pad_ = 0;
+	o.strand = strand;
 	o.key_base = key_base;
 	o.pad2_ = 0;
 	o.sketch = sketch;
@@ -136,7 +138,9 @@ void fill_hfk(ntc::HfK& o, uint32_t k, uint32_t* sketch, unsigned long long* f1,
 	for (int slot = 0; slot < ntc::kMainSlots; ++slot) {
 		o.tabh[slot][0] = tab.A[slot][1];
 		o.tabh[slot][1] = tab.A[slot][3];
+		if (strand == 2) o.tabh[slot][0] = ntc::hd_rotr(tab.A[slot][3]);
 	}
+	if (strand == 2) o.init_f = init[5];
 }
 // block shape only (no device call): waves per CU and waves per block for a slot stride, 0 waves = does not fit
 // seed_lds: the LDS a spaced seed adds (seed_lds(SeedPlan)), 0 for plain k-mers
@@ -348,6 +352,7 @@ struct ntc_engine {
 	bool ts_required = false;       // NTC_FLAG_REQUIRE_TILED
 	bool seeded = false;            // ntc_create_seeded (a ragged tiled batch of a list no plane of which is K1h's goes to row slots, instead of being refused)
 	bool defer_redo = false;        // NTC_FLAG_DEFER_REDO
+	uint32_t strand = 0;            // 0 canonical; 1 NTC_FLAG_STRAND_FORWARD, 2 NTC_FLAG_STRAND_REVERSE: every batch is K1's one-strand form (no k is K1h's)
 	unsigned char* d_untile = nullptr; // row-major scratch for tiled batches of configurations K1h is not built for
 	size_t untile_cap = 0;
 	uint32_t* d_tmeta = nullptr;       // K1's slot table (len | len << 16 per read) of a RAGGED tiled batch under a list of which a part is K1's (round 6)
@@ -819,6 +824,7 @@ int run_batch(ntc_engine* e, const unsigned char* d_slots, const uint32_t* d_met
 		a.f1 = e->d_f1 + ki;
 		ntc::build_tables(a.k, a.tab);
 		ntc::poly_a_state(a.k, a.init);
+		a.strand = e->strand;
 		hipEvent_t ev0 = nullptr, ev1 = nullptr;
 		if (e->profiling) {
 			HIP_TRY(hipEventCreate(&ev0));
@@ -901,7 +907,7 @@ int run_tiled_segs(ntc_engine* e, const TiledSeg* segs_in, uint32_t n_in, uint64
 	for (const auto& sg : segs)
 		any_tails |= sg.d_tails != nullptr;
 	if (!e->ts_all && e->ts_required) return fail(NTC_ERR_ARG, "ntc_submit_tiled_device: the tiled kernel is not available for this configuration (NTC_FLAG_REQUIRE_TILED)");
-	if (!e->ts_ok && any_tails && !e->seeded) return fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: the tiled kernels are not built for any k of this configuration");
+	if (!e->ts_ok && any_tails && !e->seeded && e->strand == 0) return fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: the tiled kernels are not built for any k of this configuration");
 	if (!e->ts_ok) { // this configuration is K1's
 		for (const auto& sg : segs) {
 			const uint32_t* d_meta = nullptr;
@@ -1242,7 +1248,7 @@ uint32_t symmetric_gap(const std::string& m)
 }
 int check_config(const ntc_config* cfg);
 int dump_k1(int32_t device, void* stream, const void* d_slots, uint64_t n_reads, uint32_t read_len, uint32_t stride, uint32_t k, const std::string& mask,
-            uint32_t max_win, void* d_hash_out, void* d_count_out);
+            uint32_t max_win, void* d_hash_out, void* d_count_out, uint32_t strand = 0);
 int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, bool seeded, ntc_engine** out);
 
 } // namespace
@@ -1302,9 +1308,11 @@ namespace {
 int check_config(const ntc_config* cfg)
 {
 	constexpr uint32_t kKnownFlags = NTC_FLAG_SIMPLE_KERNEL | NTC_FLAG_DIRECT_ATOMICS | NTC_FLAG_ALWAYS_LOG | NTC_FLAG_PARTITION_ALWAYS | NTC_FLAG_LANE_KERNEL |
-	                                 NTC_FLAG_REQUIRE_TILED | NTC_FLAG_DEFER_REDO;
+	                                 NTC_FLAG_REQUIRE_TILED | NTC_FLAG_DEFER_REDO | NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE;
 	if (cfg->flags & ~kKnownFlags) // (ABI 4's NTC_FLAG_BITSLICE_KERNEL = 4 and NTC_FLAG_TILED_TEAMS = 256 selected kernels that no longer exist)
 		return fail(NTC_ERR_ARG, "ntc_create: unknown flag bits 0x%x", cfg->flags & ~kKnownFlags);
+	if ((cfg->flags & NTC_FLAG_STRAND_FORWARD) && (cfg->flags & NTC_FLAG_STRAND_REVERSE))
+		return fail(NTC_ERR_ARG, "ntc_create: NTC_FLAG_STRAND_FORWARD and NTC_FLAG_STRAND_REVERSE exclude each other");
 	for (uint32_t i = 0; i < cfg->n_k; ++i)
 		if (cfg->k[i] < 1 || cfg->k[i] > kMaxK)
 			return fail(NTC_ERR_ARG, "ntc_create: k=%u outside 1..%u", cfg->k[i], kMaxK);
@@ -1336,6 +1344,7 @@ int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, 
 	e->stream = (hipStream_t)cfg->stream;
 	e->klist.assign(cfg->k, cfg->k + cfg->n_k);
 	e->seeded = seeded;
+	e->strand = (cfg->flags & NTC_FLAG_STRAND_FORWARD) ? 1u : (cfg->flags & NTC_FLAG_STRAND_REVERSE) ? 2u : 0u;
 	e->masks.assign(cfg->n_k, std::string());
 	e->kgap.assign(cfg->n_k, 0u);
 	e->seeds.assign(cfg->n_k, ntc::SeedPlan());
@@ -1345,6 +1354,7 @@ int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, 
 		e->masks[ki] = m;
 		e->kgap[ki] = symmetric_gap(m);
 		ntc::build_seed_plan(m, e->seeds[ki]);
+		ntc::strand_seed_plan(e->seeds[ki], e->strand);
 		e->max_seed_lds = std::max(e->max_seed_lds, seed_lds(e->seeds[ki]));
 	}
 	e->r_bits = cfg->r_bits;
@@ -1380,6 +1390,7 @@ int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, 
 	for (size_t ki = 0; ki < e->klist.size(); ++ki) {
 		std::vector<uint32_t> t1((size_t)ntc::t2_pairs(e->klist[ki]) * 64);
 		ntc::build_t2(e->klist[ki], t1.data(), e->plain(ki) ? nullptr : e->masks[ki].c_str());
+		ntc::strand_t2(e->klist[ki], t1.data(), e->strand);
 		void* d = nullptr;
 		if (hipMalloc(&d, t1.size() * 4) != hipSuccess || hipMemcpy(d, t1.data(), t1.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
 			ntc_destroy(e);
@@ -1436,7 +1447,9 @@ int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, 
 	// served by one launch per k over the same resident tiles.  Its hit-log keys and K1f's atomics are 32-bit counter indices.  Everything else —
 	// row slots, other k, other seeds, nthll — is K1's (NTC_FLAG_LANE_KERNEL: tiled batches too, re-laid out as row slots).
 	// A list may mix both kinds (round 5: `-k 16,24,32,48`, BASELINE config 4's `32,64,96,128`): K1h takes its k from the tiles, K1 stages the same tiles for the rest.
-	const bool ts_pre = e->kernel_kind == KIND_HF && !(cfg->flags & NTC_FLAG_LANE_KERNEL) && e->hll_bits == 0 && e->klist.size() * e->plane_elems() <= (1ull << 32);
+	// One strand: K1h + K1f walk both strands bit-sliced and are not touched — no k of a strand engine is theirs (tiled batches: re-laid out, then K1).
+	const bool ts_pre = e->kernel_kind == KIND_HF && !(cfg->flags & NTC_FLAG_LANE_KERNEL) && e->hll_bits == 0 && e->strand == 0 &&
+	                    e->klist.size() * e->plane_elems() <= (1ull << 32);
 	e->k_tiled.assign(e->klist.size(), 0);
 	e->ts_ok = false;
 	e->ts_all = ts_pre;
@@ -1470,7 +1483,7 @@ int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, 
 	e->defer_redo = (cfg->flags & NTC_FLAG_DEFER_REDO) != 0;
 	e->hfk.resize(e->klist.size());
 	for (size_t ki = 0; ki < e->klist.size(); ++ki)
-		fill_hfk(e->hfk[ki], e->klist[ki], e->d_sketch + ki * e->plane_elems(), e->d_f1 + ki, e->d_t1[ki], (uint32_t)(ki * e->plane_elems()));
+		fill_hfk(e->hfk[ki], e->klist[ki], e->d_sketch + ki * e->plane_elems(), e->d_f1 + ki, e->d_t1[ki], (uint32_t)(ki * e->plane_elems()), e->strand);
 	int rc = ntc_reset(e);
 	if (rc) {
 		ntc_destroy(e);
@@ -2220,7 +2233,7 @@ int ntc_merge_devices(ntc_engine* const* engines, int32_t n_engines)
 	if (!root) return fail(NTC_ERR_ARG, "ntc_merge_devices: null engine");
 	for (int32_t i = 0; i < n_engines; ++i) {
 		ntc_engine* e = engines[i];
-		if (!e || e->klist != root->klist || e->masks != root->masks || e->r_bits != root->r_bits || e->s_bits != root->s_bits || e->hll_bits != root->hll_bits)
+		if (!e || e->klist != root->klist || e->masks != root->masks || e->strand != root->strand || e->r_bits != root->r_bits || e->s_bits != root->s_bits || e->hll_bits != root->hll_bits)
 			return fail(NTC_ERR_ARG, "ntc_merge_devices: engine %d is not configured like engine 0", i);
 		for (int32_t j = 0; j < i; ++j)
 			if (engines[j] == e) return fail(NTC_ERR_ARG, "ntc_merge_devices: engine %d listed twice", i);
@@ -2486,12 +2499,29 @@ int ntc_hash_dump_seed_device(int32_t device, void* stream, const void* d_slots,
 	               d_hash_out, d_count_out);
 }
 
+int ntc_hash_dump_strand_device(int32_t device, void* stream, const void* d_slots, uint64_t n_reads, uint32_t read_len, uint32_t stride, const char* seed,
+                                uint32_t strand, uint32_t max_win, void* d_hash_out, void* d_count_out)
+{
+	if (!d_slots || !d_hash_out || !d_count_out || !seed) return fail(NTC_ERR_ARG, "ntc_hash_dump_strand_device: null argument");
+	if (strand > 2) return fail(NTC_ERR_ARG, "ntc_hash_dump_strand_device: strand %u is none of 0 (canonical), 1 (forward), 2 (reverse)", strand);
+	const size_t k = strnlen(seed, (size_t)kMaxK + 1);
+	if (k < 1 || k > kMaxK) return fail(NTC_ERR_ARG, "ntc_hash_dump_strand_device: seed length outside 1..%u", kMaxK);
+	for (size_t j = 0; j < k; ++j)
+		if (seed[j] != '0' && seed[j] != '1') return fail(NTC_ERR_ARG, "ntc_hash_dump_strand_device: character %zu of the seed is neither '0' nor '1'", j + 1);
+	const std::string mask(seed, k);
+	if (mask.find('1') == std::string::npos) return fail(NTC_ERR_ARG, "ntc_hash_dump_strand_device: the seed has no '1'");
+	if ((stride & 3u) || stride < read_len || ((uintptr_t)d_slots & 15u))
+		return fail(NTC_ERR_ARG, "ntc_hash_dump_strand_device: need 16-byte aligned slots, stride %% 4 == 0, stride >= read_len");
+	return dump_k1(device, stream, d_slots, n_reads, read_len, stride, (uint32_t)k, mask.find('0') == std::string::npos ? std::string() : mask, max_win,
+	               d_hash_out, d_count_out, strand);
+}
+
 } // extern "C"
 
 namespace {
 // K1's validation build over a batch: mask empty = plain k-mers (the arguments are checked)
 int dump_k1(int32_t device, void* stream, const void* d_slots, uint64_t n_reads, uint32_t read_len, uint32_t stride, uint32_t k, const std::string& mask,
-            uint32_t max_win, void* d_hash_out, void* d_count_out)
+            uint32_t max_win, void* d_hash_out, void* d_count_out, uint32_t strand)
 {
 	if (n_reads == 0) return 0;
 	HIP_TRY(hipSetDevice(device));
@@ -2500,8 +2530,10 @@ int dump_k1(int32_t device, void* stream, const void* d_slots, uint64_t n_reads,
 	const uint32_t n_win = read_len >= k ? read_len - k + 1 : 1;
 	std::vector<uint32_t> t1((size_t)ntc::t2_pairs(k) * 64);
 	ntc::build_t2(k, t1.data(), mask.empty() ? nullptr : mask.c_str());
+	ntc::strand_t2(k, t1.data(), strand);
 	ntc::SeedPlan sp;
 	if (!mask.empty()) ntc::build_seed_plan(mask, sp);
+	ntc::strand_seed_plan(sp, strand);
 	const std::vector<uint32_t>& gt = sp.blob;
 	const bool gap = !mask.empty();
 	void *d_t1 = nullptr, *d_gt = nullptr;
@@ -2535,7 +2567,7 @@ int dump_k1(int32_t device, void* stream, const void* d_slots, uint64_t n_reads,
 		a.s_bits = 7;
 		a.n_k = 1;
 		if (gap) set_seed_args(a, sp, d_gt);
-		fill_hfk(a.ks[0], k, nullptr, d_f1, d_t1);
+		fill_hfk(a.ks[0], k, nullptr, d_f1, d_t1, 0, strand);
 		a.dump = d_full;
 		a.dump_valid = d_valid;
 		a.dump_win = n_win;

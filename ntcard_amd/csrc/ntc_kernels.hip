@@ -155,19 +155,19 @@ __global__ __launch_bounds__(kBlockThreads) void nthash_kernel(const HashArgs a)
 		const uint64_t myslot = slot0 + lane;
 
 		auto do_emit = [&](int32_t q, bool live) {
-			// sample test on the canonical hash's top bits: top bits of min(fh,rh) == min of top bits
-			const uint32_t m = s.fHd < s.rHd ? s.fHd : s.rHd;
+			// sample test on the canonical hash's top bits: top bits of min(fh,rh) == min of top bits; one strand (a.strand 1 / 2): that strand's own
+			const uint32_t m = a.strand == 1u ? s.fHd : a.strand == 2u ? s.rHd : (s.fHd < s.rHd ? s.fHd : s.rHd);
+			const bool rv = a.strand == 0u ? rev_smaller(s) : a.strand == 2u;
 			if (MODE == 0) {
 				const bool c0 = (m ^ lo0) < lo0;
 				const bool c1 = (int32_t)m >= lo1;
 				if (live && (c0 | c1)) {
-					const uint32_t lo = rev_smaller(s) ? s.rlo : s.flo;
+					const uint32_t lo = rv ? s.rlo : s.flo;
 					const uint32_t idx = (lo & rmask) + (c1 ? rbuck : 0u);
 					atomicAdd(a.sketch + idx, 1u);
 				}
 			} else {
 				if (live) {
-					const bool rv = rev_smaller(s);
 					const uint64_t h = rv ? assemble(s.rlo, s.rB & 1u, s.rHd)
 					                      : assemble(s.flo, s.fB >> 31, s.fHd);
 					if (nemit < a.max_win) a.dump[myslot * a.max_win + nemit] = h;

@@ -30,6 +30,7 @@ struct HashArgs {
 	uint32_t hll_bits;          // != 0: nthll mode — `sketch` is uint32 M[1<<hll_bits] (max leading-zero runs, nthll.cpp:92-97)
 	const uint32_t* hll_thr;    // nthll mode: device word, only hashes whose top 32 bits are < *hll_thr can raise a register
 	uint32_t init[6];           // fast kernel: strand registers of the k x 'A' window {flo,fB,fHd,rlo,rB,rHd}
+	uint32_t strand;            // 0: canonical min(fh, rh); 1: fh; 2: rh (NTC_FLAG_STRAND_*)
 	HashTables tab;
 };
 
@@ -39,7 +40,9 @@ constexpr int kMaxFusedK = 4;
 struct HfK {
 	uint32_t k;
 	uint32_t init_f, init_r;    // H halves ((H << 1) | H[30]) of the hash of k x 'A', forward / reverse
-	uint32_t pad_;
+	uint32_t strand;            // 0: canonical; 1 forward / 2 reverse (the same for every k of a launch): the one-strand instantiations, which read the FIRST
+	                            // half of every table entry — tabh[][0], init_f, HfArgs::tabg[][0], the first 8 (t1) / 4 (gapt) bytes — where the host has put the
+	                            // wanted strand's words (nthash_tables.hpp: strand_t2, strand_seed_plan); the value only picks the rotate of the rolling update
 	uint32_t* sketch;           // uint32 [2][1<<r_bits] plane pair of this k (nthll: uint32 M[1<<hll_bits])
 	unsigned long long* f1;     // F1 of this k
 	const void* t1;             // [ceil(k/2)][16] x {fwd.lo, fwd.hi, rev.lo, rev.hi} pre-rotated seed pairs (device)

@@ -54,6 +54,11 @@ typedef __attribute__((address_space(3))) const v4u32* lds_v4_ptr;
 typedef __attribute__((address_space(3))) unsigned char* lds_byte_ptr;
 __device__ __forceinline__ uint32_t lds_off(const void* p) { return (uint32_t)(uintptr_t)(lds_byte_ptr)p; }
 __device__ __forceinline__ v4u32 lds_read4(uint32_t off) { return *(lds_v4_ptr)(uintptr_t)off; }
+typedef uint32_t v2u32 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) const v2u32* lds_v2_ptr;
+typedef __attribute__((address_space(3))) const uint32_t* lds_u32_ptr;
+__device__ __forceinline__ uint32_t lds_read1(uint32_t off) { return *(lds_u32_ptr)(uintptr_t)off; }
+__device__ __forceinline__ v2u32 lds_read2(uint32_t off) { return *(lds_v2_ptr)(uintptr_t)off; } // one strand: the first half of an entry
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
 
 // Closed-form table addresses of 4 window bases w = [c0 c1 c2 c3] (code<<6 per byte): pair (c0,c1) -> a0, (c2,c3) -> a1.
@@ -98,6 +103,16 @@ __device__ __forceinline__ uint32_t decode4(uint32_t w, uint32_t& badacc)
 	return code;
 }
 
+// a {forward, reverse} H-half entry of tabH / tabG / the seed blob; one strand: its first word only (ds_read_b32)
+template <bool kOne>
+__device__ __forceinline__ uint2 ld_h(const unsigned char* p)
+{
+	if constexpr (kOne)
+		return make_uint2(*reinterpret_cast<const uint32_t*>(p), 0u);
+	else
+		return *reinterpret_cast<const uint2*>(p);
+}
+
 // wave ballot of a bool without the int round trip hipcc's ballot() goes through (saves 2 VALU ops per use)
 __device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 
@@ -112,6 +127,11 @@ __device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_bal
 // kDump: validation build (ntc_hash_dump_k1_device): the filter lets EVERY window through, so the resolve stage
 // re-derives the full canonical hash of every window with the production code path, and writes it out instead of
 // sampling it (what ntHashIterator / stHashIterator enumerate, ntHashIterator.hpp:59-86, stHashIterator.hpp:60-87)
+// kOne: ONE strand instead of the canonical value (HfK::strand 1 forward, 2 reverse): the walk rolls, looks up and tests one H half (no second
+// rolling update, no min), the resolve stage XORs one strand's 64-bit terms (8 of an entry's 16 bytes) and skips the strand compare.  Both strands
+// share the instantiation: the host puts the wanted strand's words in the first half of every table entry (nthash_tables.hpp: strand_t2,
+// strand_seed_plan), and the only thing the kernel takes from HfK::strand is the shift of its rotate — x' = rot(x) ^ T with
+// rot = v_alignbit(x, x << 1, 31) (rotl31, NTF64) or (x, x << 1, 2) (rotr31, NTR64 with its terms pre-rotated), both in the (H << 1) | H[30] layout
 #ifdef NTC_HF_CLOCKS // timing experiment (tools/ab_build.sh <name> -DNTC_HF_CLOCKS): first / last clock (100 MHz) of every wave of the LAST launch
 __device__ unsigned long long g_hf_clocks[2 * 8192];
 } // namespace ntc
@@ -119,7 +139,7 @@ extern "C" int ntc_dbg_hf_clocks(unsigned long long* out) { return (int)hipMemcp
 namespace ntc {
 #endif
 
-template <bool kMulti, int kMode, int kPref, bool kDump = false, bool kTiled = false>
+template <bool kMulti, int kMode, int kPref, bool kDump = false, bool kTiled = false, bool kOne = false>
 __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(const HfArgs a)
 {
 #ifdef NTC_HF_CLOCKS
@@ -167,7 +187,10 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 	// made exact by the resolve stage, which re-derives everything from the bases.  Sample 1 looks at the bits
 	// above c only and is unaffected.  nthll compares against a moving threshold and runs unflipped.
 	const uint32_t flipc = kMode == 2 ? 0u : 1u << (31 - a.s_bits);
-	const uint32_t flipx = flipc ^ (flipc << 1);
+	// (one strand: x' = rot(x) ^ T for both, so the flipped bit rolls with T ^ c ^ rot(c); sBits 2 .. 24 keeps c and rot(c) inside bits 30 .. 6)
+	const uint32_t flipx = flipc ^ (kOne && a.ks[0].strand == 2u ? flipc >> 1 : flipc << 1);
+	uint32_t rot_sh = kOne && a.ks[0].strand == 2u ? 2u : 31u;
+	if constexpr (kOne) asm volatile("" : "+v"(rot_sh)); // VGPR-resident like the sample bounds below
 	{
 		for (uint32_t j = 0; j < n_k; ++j) {
 			for (int i = tid; i < kMainSlots * 4; i += (int)blockDim.x) {
@@ -376,11 +399,19 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 
 		const unsigned char* const tabGb = reinterpret_cast<const unsigned char*>(tabG);
 		auto roll2 = [&](const uint2 t, const uint2 g) { // spaced seed, rolling form: two more terms per strand
+			if constexpr (kOne) {
+				fHd = xor3(alignbit(fHd, dbl(fHd), rot_sh), t.x, g.x);
+				return;
+			}
 			fHd = alignbit(fHd, dbl(fHd), 31) ^ t.x ^ g.x;
 			const uint32_t xh = rHd ^ t.y ^ g.y;
 			rHd = alignbit(xh >> 1, xh, 1);
 		};
 		auto roll = [&](const uint2 t) {
+			if constexpr (kOne) { // the one strand lives in fHd, whichever it is: rotl31 / rotr31 by rot_sh, then ^ T (the host rotated the reverse terms)
+				fHd = alignbit(fHd, dbl(fHd), rot_sh) ^ t.x;
+				return;
+			}
 			fHd = alignbit(fHd, dbl(fHd), 31) ^ t.x;          // rotl31 in the (H<<1)|H[30] layout, then ^ Tf
 			const uint32_t xh = rHd ^ t.y;                    // reverse strand: ^ Tr, then rotr31
 			rHd = alignbit(xh >> 1, xh, 1);
@@ -405,11 +436,17 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 				dirty |= w; // bit 0 of a byte: not ACGTU
 				uint32_t a0, a1;
 				pair_addresses(w, tp, a0, a1);
-				const v4u32 t0 = lds_read4(a0), t1v = lds_read4(a1);
-				flo = xor3(flo, t0.x, t1v.x);
-				fhi = xor3(fhi, t0.y, t1v.y);
-				rlo = xor3(rlo, t0.z, t1v.z);
-				rhi = xor3(rhi, t0.w, t1v.w);
+				if constexpr (kOne) { // the wanted strand's 64-bit term is the first half of the entry
+					const v2u32 t0 = lds_read2(a0), t1v = lds_read2(a1);
+					flo = xor3(flo, t0.x, t1v.x);
+					fhi = xor3(fhi, t0.y, t1v.y);
+				} else {
+					const v4u32 t0 = lds_read4(a0), t1v = lds_read4(a1);
+					flo = xor3(flo, t0.x, t1v.x);
+					fhi = xor3(fhi, t0.y, t1v.y);
+					rlo = xor3(rlo, t0.z, t1v.z);
+					rhi = xor3(rhi, t0.w, t1v.w);
+				}
 				tp += 512u;
 			}
 			if (k & 3u) { // 1..3 bases left: a base beyond k contributes nothing because the odd-k table drops the b term
@@ -417,23 +454,34 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 				dirty |= w & (0xffffffffu >> (8 * (4 - (k & 3u))));
 				uint32_t a0, a1;
 				pair_addresses(w, tp, a0, a1);
-				const v4u32 t0 = lds_read4(a0);
-				flo ^= t0.x;
-				fhi ^= t0.y;
-				rlo ^= t0.z;
-				rhi ^= t0.w;
-				if ((k & 3u) == 3u) {
-					const v4u32 t1v = lds_read4(a1);
-					flo ^= t1v.x;
-					fhi ^= t1v.y;
-					rlo ^= t1v.z;
-					rhi ^= t1v.w;
+				if constexpr (kOne) {
+					const v2u32 t0 = lds_read2(a0);
+					flo ^= t0.x;
+					fhi ^= t0.y;
+					if ((k & 3u) == 3u) {
+						const v2u32 t1v = lds_read2(a1);
+						flo ^= t1v.x;
+						fhi ^= t1v.y;
+					}
+				} else {
+					const v4u32 t0 = lds_read4(a0);
+					flo ^= t0.x;
+					fhi ^= t0.y;
+					rlo ^= t0.z;
+					rhi ^= t0.w;
+					if ((k & 3u) == 3u) {
+						const v4u32 t1v = lds_read4(a1);
+						flo ^= t1v.x;
+						fhi ^= t1v.y;
+						rlo ^= t1v.z;
+						rhi ^= t1v.w;
+					}
 				}
 			}
 			bool hit = false;
 			uint32_t key = 0, rel = 0; // rel: counter index inside this k's plane pair; key: index in the engine's whole sketch (hit-log keys)
 			if (act && (dirty & 0x01010101u) == 0u) { // a window with a non-ACGTU byte yields no k-mer (ntHashIterator.hpp:59-86)
-				const bool rev = (rhi < fhi) | ((rhi == fhi) & (rlo < flo)); // nthash.hpp:275-279
+				const bool rev = !kOne && ((rhi < fhi) | ((rhi == fhi) & (rlo < flo))); // nthash.hpp:275-279 (one strand: no choice to make)
 				const uint32_t hi = rev ? rhi : fhi;
 				const uint32_t lo = rev ? rlo : flo;
 				if constexpr (kDump) {
@@ -528,10 +576,10 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 			uint2 t[4];
 		};
 		auto issue = [&](uint32_t idx4, Tab4& T) {
-			T.t[0] = *reinterpret_cast<const uint2*>(tabHb + (idx4 & 0xffu));
-			T.t[1] = *reinterpret_cast<const uint2*>(tabHb + ((idx4 >> 8) & 0xffu));
-			T.t[2] = *reinterpret_cast<const uint2*>(tabHb + ((idx4 >> 16) & 0xffu));
-			T.t[3] = *reinterpret_cast<const uint2*>(tabHb + (idx4 >> 24));
+			T.t[0] = ld_h<kOne>(tabHb + (idx4 & 0xffu));
+			T.t[1] = ld_h<kOne>(tabHb + ((idx4 >> 8) & 0xffu));
+			T.t[2] = ld_h<kOne>(tabHb + ((idx4 >> 16) & 0xffu));
+			T.t[3] = ld_h<kOne>(tabHb + (idx4 >> 24));
 		};
 
 		// group ranges: [0,e0) never emit and never see a real outgoing base; [e0,e1) are the (at most
@@ -583,12 +631,12 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 						for (uint32_t p = 0; p < ngp; ++p) {
 							const uint32_t dw = dcw[p];
 							const uint32_t off = (gp[dw & 0xffffu] & 0xc0u) | ((gp[dw >> 16] >> 2) & 0x30u);
-							const uint2 g = *reinterpret_cast<const uint2*>(gapT + p * 256u + off);
+							const uint2 g = ld_h<kOne>(gapT + p * 256u + off);
 							fs ^= g.x;
 							rs ^= g.y;
 						}
 					}
-					const uint32_t mn = fs < rs ? fs : rs; // top bits of min(fh,rh) (of the spaced-seed values when gapped)
+					const uint32_t mn = kOne ? fs : (fs < rs ? fs : rs); // top bits of min(fh,rh) (of the spaced-seed values when gapped); one strand: of that strand
 					if (kDump)
 						m = ballot(true);
 					else if (hll.value)
@@ -623,10 +671,10 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 							asm volatile("" : "+v"(ig));
 							const unsigned char* tg = p == 0 ? tabGb : rollT + (p - 1u) * 256u;
 							uint2 v[4];
-							v[0] = *reinterpret_cast<const uint2*>(tg + (ig & 0xffu));
-							v[1] = *reinterpret_cast<const uint2*>(tg + ((ig >> 8) & 0xffu));
-							v[2] = *reinterpret_cast<const uint2*>(tg + ((ig >> 16) & 0xffu));
-							v[3] = *reinterpret_cast<const uint2*>(tg + (ig >> 24));
+							v[0] = ld_h<kOne>(tg + (ig & 0xffu));
+							v[1] = ld_h<kOne>(tg + ((ig >> 8) & 0xffu));
+							v[2] = ld_h<kOne>(tg + ((ig >> 16) & 0xffu));
+							v[3] = ld_h<kOne>(tg + (ig >> 24));
 #pragma unroll
 							for (int b = 0; b < 4; ++b) {
 								TG.t[b].x = p == 0 ? v[b].x : TG.t[b].x ^ v[b].x;
@@ -693,13 +741,13 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 						const uint32_t tw = a.roll_t[p];
 						const int32_t o1 = q - (int32_t)k + (int32_t)(tw & 0xffffu), o2 = q - (int32_t)k + (int32_t)(tw >> 16);
 						const uint32_t og = (mine[o1] & 0xc0u) | ((mine[o2] >> 2) & 0x30u);
-						const uint2 v = *reinterpret_cast<const uint2*>((p == 0 ? tabGb : rollT + (p - 1u) * 256u) + og);
+						const uint2 v = ld_h<kOne>((p == 0 ? tabGb : rollT + (p - 1u) * 256u) + og);
 						g.x ^= v.x;
 						g.y ^= v.y;
 					}
-					roll2(*reinterpret_cast<const uint2*>(tabHb + off), g);
+					roll2(ld_h<kOne>(tabHb + off), g);
 				} else {
-					roll(*reinterpret_cast<const uint2*>(tabHb + off));
+					roll(ld_h<kOne>(tabHb + off));
 				}
 				record(q, q >= (int32_t)k - 1);
 			};
@@ -727,9 +775,13 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 						if (wc.value == DIRTY) book_marks(i, w);
 						uint32_t a0, a1;
 						pair_addresses(w, tp, a0, a1);
-						const v4u32 t0 = lds_read4(a0), t1v = lds_read4(a1);
-						fhi = xor3(fhi, t0.y, t1v.y);
-						rhi = xor3(rhi, t0.w, t1v.w);
+						if constexpr (kOne) { // (word 1 of an entry: the high half of the wanted strand's term)
+							fhi = xor3(fhi, lds_read1(a0 + 4u), lds_read1(a1 + 4u));
+						} else {
+							const v4u32 t0 = lds_read4(a0), t1v = lds_read4(a1);
+							fhi = xor3(fhi, t0.y, t1v.y);
+							rhi = xor3(rhi, t0.w, t1v.w);
+						}
 						tp += 512u;
 					}
 					if (k & 3u) {
@@ -737,13 +789,18 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 						if (wc.value == DIRTY) book_marks(i, w & (0xffffffffu >> (8 * (4 - (k & 3u)))));
 						uint32_t a0, a1;
 						pair_addresses(w, tp, a0, a1);
-						const v4u32 t0 = lds_read4(a0);
-						fhi ^= t0.y;
-						rhi ^= t0.w;
-						if ((k & 3u) == 3u) {
-							const v4u32 t1v = lds_read4(a1);
-							fhi ^= t1v.y;
-							rhi ^= t1v.w;
+						if constexpr (kOne) {
+							fhi ^= lds_read1(a0 + 4u);
+							if ((k & 3u) == 3u) fhi ^= lds_read1(a1 + 4u);
+						} else {
+							const v4u32 t0 = lds_read4(a0);
+							fhi ^= t0.y;
+							rhi ^= t0.w;
+							if ((k & 3u) == 3u) {
+								const v4u32 t1v = lds_read4(a1);
+								fhi ^= t1v.y;
+								rhi ^= t1v.w;
+							}
 						}
 					}
 					// high word of the 64-bit hash = (H << 1) | L[32]  ->  walk layout (H << 1) | H[30], plus the sample-bit flip
@@ -845,6 +902,24 @@ hipError_t launch_sketch_hf(const HfArgs& a, unsigned grid, unsigned waves_per_b
 	const dim3 g(grid), b(64u * waves_per_block);
 	const bool deep = sketch_hf_deep_prefetch(a.stride) && waves_per_block <= 12; // plain k-mer mode only
 	if (a.tiled != 0u && (a.dump != nullptr || a.gap != 0 || a.hll_bits != 0)) return hipErrorInvalidValue; // (tiled staging: plain k-mer mode only)
+	if (a.ks[0].strand > 2u || (a.ks[0].strand != 0u && (a.tiled != 0u || a.hll_bits != 0))) return hipErrorInvalidValue; // (one strand: row slots; nthll is canonical)
+	if (a.ks[0].strand != 0u) { // the one-strand copies of the seven instantiations a strand engine can reach (its tiled batches are re-laid out as row slots)
+		if (a.dump != nullptr && a.gap != 0)
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, true, false, true>), g, b, smem, st, a);
+		else if (a.dump != nullptr)
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, true, false, true>), g, b, smem, st, a);
+		else if (a.gap != 0)
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, false, false, true>), g, b, smem, st, a);
+		else if (a.n_k > 1 && deep)
+			hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 16, false, false, true>), g, b, smem, st, a);
+		else if (a.n_k > 1)
+			hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 10, false, false, true>), g, b, smem, st, a);
+		else if (deep)
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 16, false, false, true>), g, b, smem, st, a);
+		else
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, false, false, true>), g, b, smem, st, a);
+		return hipGetLastError();
+	}
 	if (a.dump != nullptr && a.gap != 0)
 		hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, true>), g, b, smem, st, a);
 	else if (a.dump != nullptr)
@@ -904,7 +979,12 @@ hipError_t set_sketch_hf_smem_limit(size_t smem)
 		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 2, 10>),
 		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, true>),
 		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 10, false, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 16, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 16, false, true>) };
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 16, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 16, false, true>),
+		              // one strand
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, false, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 10, false, false, true>),
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 16, false, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 16, false, false, true>),
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, false, false, true>),
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, true, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, true, false, true>) };
 	for (const void* f : fns) {
 		const hipError_t rc = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 		if (rc != hipSuccess) return rc;

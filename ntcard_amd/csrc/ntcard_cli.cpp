@@ -46,6 +46,8 @@ void usage(std::ostream& os)
 	   << "  -o, --output=STRING\tsingle tab separated output file (k, f, n)\n"
 	   << "      --seed=MASK[,MASK...]\tspaced seeds instead of -k / -g: strings of 0 (don't care) and 1 (counted), one spectrum each;\n"
 	   << "\t\toutput files <STRING>_seed<i>_k<length>.hist, or -o rows (seed, f, n) with i = 1, 2, ...\n"
+	   << "      --strand=canonical|forward|reverse\twhich value of a k-mer is counted [canonical]: the smaller of the k-mer and its reverse\n"
+	   << "\t\tcomplement (ntcard), the k-mer as read, or its reverse complement; with -k, -g and --seed; output files unchanged\n"
 	   << "      --help\tdisplay this help and exit\n"
 	   << "      --version\toutput version information and exit\n";
 }
@@ -60,6 +62,7 @@ struct Options {
 	std::vector<unsigned> klist;
 	bool gap_given = false;
 	std::vector<std::string> seeds; // --seed: masks of '0' / '1' (include/ntcard_hip.h: ntc_create_seeded)
+	uint32_t strand_flag = 0;       // --strand: NTC_FLAG_STRAND_FORWARD / _REVERSE, 0 = canonical
 };
 
 void process_file(const std::string& path, ntc_engine* eng)
@@ -89,7 +92,7 @@ int main(int argc, char** argv)
 {
 	const auto t_start = std::chrono::steady_clock::now();
 	static const char shortopts[] = "t:s:r:k:c:l:p:f:o:g:";
-	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED };
+	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED, OPT_STRAND };
 	static const struct option longopts[] = { { "threads", required_argument, nullptr, 't' },
 		                                      { "kmer", required_argument, nullptr, 'k' },
 		                                      { "gap", required_argument, nullptr, 'g' },
@@ -101,6 +104,7 @@ int main(int argc, char** argv)
 		                                      { "help", no_argument, nullptr, OPT_HELP },
 		                                      { "version", no_argument, nullptr, OPT_VERSION },
 		                                      { "seed", required_argument, nullptr, OPT_SEED },
+		                                      { "strand", required_argument, nullptr, OPT_STRAND },
 		                                      { nullptr, 0, nullptr, 0 } };
 	Options opt;
 	bool die = false;
@@ -128,6 +132,20 @@ int main(int argc, char** argv)
 				opt.seeds.push_back(arg.substr(b, e == std::string::npos ? std::string::npos : e - b));
 				if (e == std::string::npos) break;
 				b = e + 1;
+			}
+			break;
+		}
+		case OPT_STRAND: {
+			const std::string arg(optarg ? optarg : "");
+			if (arg == "canonical")
+				opt.strand_flag = 0;
+			else if (arg == "forward")
+				opt.strand_flag = NTC_FLAG_STRAND_FORWARD;
+			else if (arg == "reverse")
+				opt.strand_flag = NTC_FLAG_STRAND_REVERSE;
+			else {
+				std::cerr << PROGRAM << ": --strand: `" << arg << "' is none of canonical, forward, reverse\n";
+				die = true;
 			}
 			break;
 		}
@@ -242,6 +260,7 @@ int main(int argc, char** argv)
 	cfg.gap = opt.gap;
 	cfg.r_bits = opt.r_bits;
 	cfg.s_bits = opt.s_bits;
+	cfg.flags = opt.strand_flag;
 	// Devices: NTCARD_DEVICES="0,1,2,..." spreads the input files over several GPUs (one private sketch each, merged
 	// at the end: counting is a commutative sum); NTCARD_DEVICE=<n> or nothing selects a single one.
 	std::vector<int> devices;

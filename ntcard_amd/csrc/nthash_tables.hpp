@@ -290,4 +290,38 @@ inline void build_seed_plan(const std::string& mask, SeedPlan& sp)
 	}
 }
 
+// ---- one strand (NTC_FLAG_STRAND_FORWARD / _REVERSE): the tables of K1's one-strand instantiations ----
+//
+// The one-strand kernel reads the FIRST half of every table entry and nothing else, so forward against reverse is
+// decided here: the wanted strand's words are moved to the front of each entry (strand: 0 canonical = leave the
+// tables alone, 1 forward, 2 reverse).  It rolls one form for both strands, x' = rot(x) ^ T, rot = rotl31 forward and
+// rotr31 reverse.  NTR64 (nthash.hpp:251-257) XORs before it rotates, rh' = rotr(rh ^ Tr) = rotr(rh) ^ rotr(Tr): the
+// reverse strand's STEP terms (HfK::tabh, the toggle tables of a spaced seed) are therefore handed over rotated
+// right by one; the closed-form terms (build_t2, the XOR-out tables) apply to the value as it stands and are not.
+inline uint32_t hd_rotr(uint32_t hd)
+{
+	uint32_t h = hd >> 1; // 31 bits
+	h = (h >> 1) | ((h & 1u) << 30);
+	return (h << 1) | (h >> 30);
+}
+inline void strand_t2(unsigned k, uint32_t* t2 /* build_t2's output */, unsigned strand)
+{
+	if (strand != 2) return; // (forward: already in front)
+	for (size_t e = 0; e < (size_t)t2_pairs(k) * 16; ++e) {
+		t2[e * 4 + 0] = t2[e * 4 + 2];
+		t2[e * 4 + 1] = t2[e * 4 + 3];
+	}
+}
+inline void strand_seed_plan(SeedPlan& sp, unsigned strand)
+{
+	if (strand != 2 || sp.k == 0) return;
+	const unsigned ngp = (sp.n_dc + 1) / 2, nrx = sp.n_roll > 1 ? sp.n_roll - 1 : 0;
+	for (size_t e = 0; e < (size_t)ngp * 16; ++e) // XOR-out tables: as they are
+		sp.blob[e * 4] = sp.blob[e * 4 + 1];
+	for (size_t e = (size_t)ngp * 16; e < (size_t)(ngp + nrx) * 16; ++e) // toggle tables of pairs 1 ..: rotated
+		sp.blob[e * 4] = hd_rotr(sp.blob[e * 4 + 1]);
+	for (unsigned e = 0; e < 16; ++e)
+		sp.tabg[e][0] = hd_rotr(sp.tabg[e][1]);
+}
+
 } // namespace ntc

@@ -20,6 +20,9 @@ FLAG_PARTITION_ALWAYS = 16  # NTC_FLAG_PARTITION_ALWAYS: small logs go through t
 FLAG_DEFER_REDO = 128  # NTC_FLAG_DEFER_REDO: submit_device buffers stay unchanged until sync(); the handed-back reads of several batches share one pass
 FLAG_REQUIRE_TILED = 64  # NTC_FLAG_REQUIRE_TILED: submit_tiled_device fails instead of falling back to the general kernel
 FLAG_DIRECT_ATOMICS = 2  # NTC_FLAG_DIRECT_ATOMICS: no hit log, one device atomic per sampled k-mer
+FLAG_STRAND_FORWARD = 512  # NTC_FLAG_STRAND_FORWARD: count the forward value fh of every window instead of the canonical min(fh, rh)
+FLAG_STRAND_REVERSE = 1024  # NTC_FLAG_STRAND_REVERSE: count the reverse value rh (the forward value of the window's reverse complement)
+_STRAND_FLAGS = {"canonical": 0, "forward": FLAG_STRAND_FORWARD, "reverse": FLAG_STRAND_REVERSE}
 SIZE_RULE_BYTES = 50_000_000_000  # ntcard.cpp:430: total input < 50 GB => sBits = 7
 
 
@@ -32,8 +35,24 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _strand_flags(flags, strand):
+    """`flags` with the bit of the `strand` keyword ORed in (None: whatever `flags` says); checked before the library is asked for a device"""
+    flags = int(flags)
+    if strand is None:
+        return flags
+    if not isinstance(strand, str) or strand not in _STRAND_FLAGS:
+        raise ValueError(f"strand must be 'canonical', 'forward' or 'reverse', not {strand!r}")
+    given = flags & (FLAG_STRAND_FORWARD | FLAG_STRAND_REVERSE)
+    if given and given != _STRAND_FLAGS[strand]:
+        raise ValueError(f"strand={strand!r} contradicts the strand bits 0x{given:x} passed in flags")
+    return flags | _STRAND_FLAGS[strand]
+
+
 class Engine:
-    def __init__(self, klist, gap=0, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0):
+    def __init__(self, klist, gap=0, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0, strand=None):
+        """strand: "canonical" (the default, what ntcard counts), "forward" or "reverse" — which value of a window is counted
+        (include/ntcard_hip.h: NTC_FLAG_STRAND_FORWARD / _REVERSE)"""
+        flags = _strand_flags(flags, strand)
         self._lib = _abi.lib()
         self.klist = [int(k) for k in klist]
         self.gap, self.r_bits, self.s_bits, self.device = int(gap), int(r_bits), int(s_bits), int(device)
@@ -54,9 +73,10 @@ class Engine:
         self.seeds = None
 
     @classmethod
-    def from_seeds(cls, seeds, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0):
+    def from_seeds(cls, seeds, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0, strand=None):
         """an engine whose planes are spaced seeds given as masks of '0' / '1' (include/ntcard_hip.h: ntc_create_seeded); its klist is
-        the masks' lengths, so finish, merge_counters and the rest work as for a k list"""
+        the masks' lengths, so finish, merge_counters and the rest work as for a k list; strand as for Engine()"""
+        flags = _strand_flags(flags, strand)
         self = cls.__new__(cls)
         self._lib = _abi.lib()
         self.seeds = [s.decode() if isinstance(s, bytes) else str(s) for s in seeds]
@@ -350,3 +370,11 @@ def hash_dump_seed_device(d_slots_ptr, n_reads, read_len, stride, seed, max_win,
     seed = seed.encode() if isinstance(seed, str) else bytes(seed)
     check(_abi.lib().ntc_hash_dump_seed_device(device, C.c_void_p(stream) if stream else None, C.c_void_p(d_slots_ptr), n_reads, read_len, stride, seed,
                                                max_win, C.c_void_p(d_hash_ptr), C.c_void_p(d_count_ptr)))
+
+
+def hash_dump_strand_device(d_slots_ptr, n_reads, read_len, stride, seed, strand, max_win, d_hash_ptr, d_count_ptr, device=0, stream=None):
+    """hash_dump_seed_device with a strand: 0 the canonical value, 1 the forward, 2 the reverse value of every clean window
+    (include/ntcard_hip.h: ntc_hash_dump_strand_device)"""
+    seed = seed.encode() if isinstance(seed, str) else bytes(seed)
+    check(_abi.lib().ntc_hash_dump_strand_device(device, C.c_void_p(stream) if stream else None, C.c_void_p(d_slots_ptr), n_reads, read_len, stride, seed,
+                                                 int(strand), max_win, C.c_void_p(d_hash_ptr), C.c_void_p(d_count_ptr)))
