@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import orc
+from devview import DevArray as _DevArray
 
 pytestmark = pytest.mark.gpu
 
@@ -375,13 +376,6 @@ def test_log_and_adaptive_modes_agree_at_size(nt):
             res.append((ph.copy(), f1.copy(), torch.as_tensor(_DevArray(sk, ncnt), device="cuda").clone()))
     assert np.array_equal(res[0][1], res[1][1]) and np.array_equal(res[0][0], res[1][0])
     assert torch.equal(res[0][2], res[1][2])
-
-
-class _DevArray:
-    """zero-copy view of a device int32 array for torch.as_tensor (__cuda_array_interface__)"""
-
-    def __init__(self, ptr, n):
-        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
 
 
 def test_golden_hist_from_reference(nt, golden_dir, tmp_path):
