@@ -14,7 +14,7 @@
 
 #include "../../include/ntcard_hip.h"
 
-int ntc_internal_fail(int code, const char* fmt, ...); // ntc_engine.hip: sets ntc_last_error()
+int ntc_internal_fail(int code, const char* fmt, ...); // ntc_lifecycle.hip: sets ntc_last_error()
 
 extern "C" {
 

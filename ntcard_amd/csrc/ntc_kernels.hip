@@ -461,7 +461,7 @@ hipError_t launch_hll_threshold(const uint32_t* regs, uint32_t n_regs, uint32_t*
 	return hipGetLastError();
 }
 
-// ---- host-side launch helpers (called from ntc_engine.hip) -----------------------------------------
+// ---- host-side launch helpers (called from the engine's host layer, ntc_engine.hpp) -----------------------------------------
 hipError_t launch_hash(int mode, const HashArgs& a, unsigned grid, size_t smem, hipStream_t st)
 {
 	if (mode == 0)

@@ -1,4 +1,4 @@
-// ntc_kernels.hpp — argument blocks and launch helpers shared by ntc_kernels.hip / ntc_engine.hip
+// ntc_kernels.hpp — argument blocks and launch helpers shared by ntc_kernels.hip and the engine's host layer (ntc_engine.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,0 +1,364 @@
+// ntc_submit.hip — the ntc_submit* entry points: device-resident batches as they come; host reads packed into a staging pair (tiles for the
+// tiled kernels, length bins for ragged sets, row slots for the rest) and copied behind the engine's stream (ntc_engine.hpp)
+#include "ntc_engine.hpp"
+
+using namespace ntc_eng;
+
+namespace {
+
+// A staging pair on loan to one submitting thread: packing happens outside the engine's lock, only copy + launch take it
+struct StageLease {
+	ntc_engine* e = nullptr;
+	ntc_engine::StageSlot* sl = nullptr;
+	StageLease() = default;
+	StageLease(const StageLease&) = delete;
+	StageLease& operator=(const StageLease&) = delete;
+	~StageLease()
+	{
+		if (!sl) return;
+		{
+			std::lock_guard<std::mutex> lk(e->stage_mu);
+			sl->busy = false;
+		}
+		e->stage_cv.notify_one();
+	}
+};
+
+// take a free staging pair; wait (this thread only) until the GPU is done with its previous contents; grow it to stage_bytes (doubling)
+int lease_stage(ntc_engine* e, size_t stage_bytes, StageLease& lease)
+{
+	HIP_TRY(hipSetDevice(e->device));
+	{
+		std::unique_lock<std::mutex> lk(e->stage_mu);
+		auto free_slot = [&]() -> ntc_engine::StageSlot* {
+			for (auto& c : e->stage)
+				if (!c.busy) return &c;
+			return nullptr;
+		};
+		e->stage_cv.wait(lk, [&] { return free_slot() != nullptr; });
+		lease.e = e;
+		lease.sl = free_slot();
+		lease.sl->busy = true;
+	}
+	auto& sl = *lease.sl;
+	if (sl.done == nullptr) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+	if (sl.used) HIP_TRY(hipEventSynchronize(sl.done));
+	const size_t h_cap = std::max(stage_bytes, sl.h_stage.cap * 2), d_cap = std::max(stage_bytes, sl.d_stage.cap * 2);
+	if (!sl.h_stage.reserve(stage_bytes, h_cap)) return fail(NTC_ERR_MEMORY, "ntc_submit: cannot pin %zu B", h_cap);
+	if (!sl.d_stage.reserve(stage_bytes, d_cap)) return fail(NTC_ERR_MEMORY, "ntc_submit: cannot allocate %zu B on device", d_cap);
+	return 0;
+}
+
+// behind the copies and launches of a leased pair (under e->mu).  The copies are in flight whatever the launches said (rc): the pair may only be
+// reused after them, and nothing may still read the pinned side when it is handed out again
+int end_stage_use(ntc_engine* e, ntc_engine::StageSlot& sl, int rc)
+{
+	sl.used = true;
+	if (hipEventRecord(sl.done, e->stream) != hipSuccess) (void)hipStreamSynchronize(e->stream);
+	return rc;
+}
+
+int stage_copy_failed(ntc_engine* e)
+{
+	(void)hipStreamSynchronize(e->stream);
+	return fail(NTC_ERR_DEVICE, "ntc_submit: host to device copy failed");
+}
+
+// read i = bytes [ptr_of(i), ptr_of(i) + len_of(i)): ntc_submit (concatenated reads + offsets) and ntc_submit_spans (spans of
+// a caller buffer, e.g. the sequence lines inside a block of a FASTQ file) pack into the pinned staging pair the same way
+// (len_of / ptr_of are template callables: the packing loops call them once or twice per read, inlined).
+// Equal-length reads of a host batch go to the device in the TILED layout: the packing loop writes each read's 16-byte pieces
+// where ntc_submit_tiled_device expects them, so the reads the reference's parsers hand to ntRead (ntcard.cpp:182,203,230) reach the
+// tiled kernels like a device-resident producer's do.
+// ragged == false: every read is `len` bases long.  ragged == true: the reads are 16 C - 15 .. 16 C bases long, C = len / 16, and come
+// LONGEST FIRST (so every tile is sorted): the tiles are followed, in the same staging buffer, by tails[tile][16] — the reads of the tile with more than d
+// bases in their last piece — and the batch goes to ntc_submit_tiled_ragged_device's path.
+// A host batch may hold several bins (HostBin: reads idx[0 .. n) of the caller's numbering, or 0 .. n when idx == nullptr): they are packed one behind the other into ONE
+// staging buffer, copied once and hashed by ONE launch per k (run_tiled_segs).
+struct HostBin {
+	const uint64_t* idx;
+	uint64_t n;
+	uint32_t len;  // every read's length, or 16 C for a ragged bin
+	bool ragged;
+};
+template <class LenFn, class PtrFn> int submit_tiled_host(ntc_engine* e, const HostBin* bins, uint32_t n_bins, const LenFn& len_of, const PtrFn& ptr_of)
+{
+	// sections: [tiles of bin 0][tails of bin 0][tiles of bin 1] ... (tile sections are multiples of 32 KiB, tails of 64 B: everything stays 16-byte aligned)
+	std::vector<size_t> off(n_bins), tile_bytes(n_bins);
+	size_t need = 0;
+	for (uint32_t b = 0; b < n_bins; ++b) {
+		off[b] = need;
+		tile_bytes[b] = (size_t)ntc_tiled_bytes(bins[b].n, bins[b].len);
+		need += tile_bytes[b] + (bins[b].ragged ? (size_t)((bins[b].n + ntc::kTileReads - 1) / ntc::kTileReads) * 64 : 0);
+	}
+	StageLease lease;
+	if (int rc = lease_stage(e, need, lease)) return rc;
+	auto& sl = *lease.sl;
+	// ---- pack: piece c of read i of a bin -> ((tile * C + c) * 2048 + i % 2048) * 16 of the bin's section ----
+	for (uint32_t b = 0; b < n_bins; ++b) {
+		const HostBin& hb = bins[b];
+		unsigned char* hs = sl.h_stage + off[b];
+		const uint32_t C = (hb.len + 15u) / 16u;
+		uint32_t* tails = reinterpret_cast<uint32_t*>(hs + tile_bytes[b]);
+		if (hb.ragged) std::memset(tails, 0, (size_t)((hb.n + ntc::kTileReads - 1) / ntc::kTileReads) * 64);
+		for (uint64_t i = 0; i < hb.n; ++i) {
+			const uint64_t r = hb.idx ? hb.idx[i] : i;
+			const char* src = ptr_of(r);
+			const uint32_t tail = (uint32_t)(hb.ragged ? len_of(r) : hb.len) - (C - 1u) * 16u; // 1 .. 16 bases in the last piece
+			unsigned char* dst = hs + ((i / ntc::kTileReads) * C * ntc::kTileReads + i % ntc::kTileReads) * 16u;
+			for (uint32_t c = 0; c + 1u < C; ++c)
+				std::memcpy(dst + (size_t)c * ntc::kTileReads * 16u, src + 16u * c, 16);
+			unsigned char* last = dst + (size_t)(C - 1u) * ntc::kTileReads * 16u;
+			std::memcpy(last, src + 16u * (C - 1u), tail);
+			std::memset(last + tail, 'A', 16u - tail);
+			if (hb.ragged)
+				for (uint32_t d = 0; d < tail; ++d)
+					++tails[(i / ntc::kTileReads) * 16u + d];
+		}
+	}
+	std::lock_guard<std::mutex> lk(e->mu);
+	if (hipMemcpyAsync(sl.d_stage, sl.h_stage, need, hipMemcpyHostToDevice, e->stream) != hipSuccess) return stage_copy_failed(e);
+	std::vector<TiledSeg> segs(n_bins);
+	for (uint32_t b = 0; b < n_bins; ++b)
+		segs[b] = TiledSeg{sl.d_stage + off[b], bins[b].n, bins[b].len, bins[b].ragged ? reinterpret_cast<const uint32_t*>(sl.d_stage + off[b] + tile_bytes[b]) : nullptr};
+	return end_stage_use(e, sl, run_tiled_segs(e, segs.data(), n_bins, 1, true)); // (the staging pair is recycled: its K1f may not be deferred)
+}
+
+// reads -> row slots (one slot per read, long sequences in overlapping chunks) -> K1
+template <class LenFn, class PtrFn> int submit_rows(ntc_engine* e, uint64_t n_reads, const LenFn& len_of, const PtrFn& ptr_of)
+{
+	const uint32_t kmax = *std::max_element(e->klist.begin(), e->klist.end());
+	const uint32_t kmin = *std::min_element(e->klist.begin(), e->klist.end());
+	// ---- plan: one slot per read, or chunks with kmax-1 overlap for long sequences ----
+	uint64_t maxlen = 0;
+	bool uniform = true;
+	const uint64_t len0 = len_of(0);
+	for (uint64_t i = 0; i < n_reads; ++i) {
+		const uint64_t l = len_of(i);
+		maxlen = std::max(maxlen, l);
+		uniform &= (l == len0);
+	}
+	if (maxlen < kmin) return 0; // nothing can produce a k-mer (ntHashIterator.hpp:61-64)
+	const uint32_t cap_chunk = std::max<uint32_t>(kSlotCapMin, ((2 * kmax + 64) + 3) & ~3u);
+	const bool chunked = maxlen > cap_chunk;
+	const uint32_t stride = pick_stride(chunked ? cap_chunk : maxlen, e->klist, e->max_seed_lds);
+	const uint32_t ch = cap_chunk - (kmax - 1); // window starts per chunk
+	uint64_t n_slots = 0;
+	if (!chunked) {
+		n_slots = n_reads;
+	} else {
+		for (uint64_t i = 0; i < n_reads; ++i) {
+			const uint64_t l = len_of(i);
+			if (l < kmin) continue;
+			n_slots += l <= cap_chunk ? 1 : (l - (kmax - 1) + ch - 1) / ch;
+		}
+	}
+	StageLease lease;
+	if (int rc = lease_stage(e, (size_t)n_slots * stride + 16, lease)) return rc;
+	auto& sl = *lease.sl;
+	const bool need_meta = chunked || !uniform;
+	if (need_meta && !(sl.h_meta.reserve(n_slots * 4, sl.h_meta.cap * 2) && sl.d_meta.reserve(n_slots * 4, sl.d_meta.cap * 2)))
+		return fail(NTC_ERR_MEMORY, "ntc_submit: cannot allocate slot metadata");
+	// ---- pack (the copy the ABI promises: caller's buffers are free on return) ----
+	unsigned char* hs = sl.h_stage;
+	uint64_t slot = 0;
+	// Reads of different lengths are packed longest first (counting sort: counting is order-independent, ntcard.cpp:142-143).
+	// 64 consecutive slots form a wave, and a wave whose reads are equally long takes the kernel's fast path: with 5 % of
+	// trimmed reads scattered through a batch almost every wave would be ragged (0.95 vs 0.76 ms per 8 M reads).
+	std::vector<uint32_t> order;
+	if (!chunked && !uniform && n_reads < 0xffffffffull) {
+		std::vector<uint64_t> first(maxlen + 2, 0);
+		for (uint64_t i = 0; i < n_reads; ++i)
+			++first[maxlen - len_of(i) + 1];
+		for (uint64_t l = 1; l <= maxlen + 1; ++l)
+			first[l] += first[l - 1];
+		order.resize(n_reads);
+		for (uint64_t i = 0; i < n_reads; ++i)
+			order[first[maxlen - len_of(i)]++] = (uint32_t)i;
+	}
+	// one slot: nbytes of src, padded; its meta word = bytes | window-start limit << 16
+	auto put = [&](const char* src, uint64_t nbytes, uint64_t limit) {
+		unsigned char* dst = hs + slot * stride;
+		std::memcpy(dst, src, nbytes);
+		std::memset(dst + nbytes, 'A', stride - nbytes);
+		if (need_meta) sl.h_meta[slot] = (uint32_t)nbytes | ((uint32_t)limit << 16);
+		++slot;
+	};
+	for (uint64_t j = 0; j < n_reads; ++j) {
+		const uint64_t i = order.empty() ? j : order[j];
+		const uint64_t l = len_of(i);
+		const char* src = ptr_of(i);
+		if (chunked && l < kmin) continue;
+		if (!chunked || l <= cap_chunk) {
+			put(src, l, l);
+			continue;
+		}
+		for (uint64_t start = 0; start + (kmax - 1) < l || start == 0; start += ch) {
+			const uint64_t nbytes = std::min<uint64_t>(cap_chunk, l - start);
+			const bool last = start + cap_chunk >= l;
+			put(src + start, nbytes, last ? nbytes : ch);
+			if (last) break;
+		}
+	}
+	if (slot != n_slots) return fail(NTC_ERR_STATE, "ntc_submit: internal slot plan mismatch (%llu != %llu)", (unsigned long long)slot, (unsigned long long)n_slots);
+	// ---- enqueue: copy + kernels, in order on the engine's stream (asynchronous; ntc_sync / ntc_finish wait) ----
+	std::lock_guard<std::mutex> lk(e->mu);
+	if (hipMemcpyAsync(sl.d_stage, hs, (size_t)n_slots * stride, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+	    (need_meta && hipMemcpyAsync(sl.d_meta, sl.h_meta, n_slots * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess))
+		return stage_copy_failed(e);
+	return end_stage_use(e, sl, run_batch(e, sl.d_stage, need_meta ? sl.d_meta.get() : nullptr, n_slots, (uint32_t)len0, stride));
+}
+
+template <class LenFn, class PtrFn> int submit_impl(ntc_engine* e, uint64_t n_reads, const LenFn& len_of, const PtrFn& ptr_of)
+{
+	const uint32_t kmin = *std::min_element(e->klist.begin(), e->klist.end());
+	if (e->ts_ok && n_reads >= 1024) {
+		// Reads of ONE length (an untrimmed FASTQ file) are one tiled batch.  Otherwise the reads are binned by their number of 16-base pieces,
+		// C = ceil(len / 16): every bin of at least 32 Ki reads becomes a RAGGED tiled batch — sorted longest first, K1h masks the windows
+		// behind every read's end — all of them hashed by ONE launch per k that shares its workgroups among the bins (run_tiled_segs), and what is left
+		// (thin bins, reads shorter than every k, sequences beyond 64 Ki bases) takes row slots and K1.  profiles/r05_ragged_host.txt: 8 M reads of which
+		// 5 % are trimmed to 50 .. 149 bp: 0.483 ms with bins from 32 Ki reads, 0.527 from 512 Ki (the thin bins through K1), 0.728 through K1 alone;
+		// lengths uniform in 100 .. 150: 0.385 against 0.647.  (With one launch PER BIN, the first form of this, thin bins lost to K1 and the bar was 512 Ki.)
+		// NTC_FLAG_REQUIRE_TILED, the validation flag, lowers the bar to 1024 reads.
+		uint32_t bin_min = e->ts_required ? 1024u : 32u * 1024u;
+		if (const char* ev = std::getenv("NTC_BIN_MIN")) bin_min = (uint32_t)std::max(1024l, std::strtol(ev, nullptr, 10)); // tuning runs (tools/ragged_time.py)
+		const uint64_t len0 = len_of(0);
+		uint64_t same = 0;
+		for (uint64_t i = 0; i < n_reads; ++i)
+			same += len_of(i) == len0;
+		if (same == n_reads) {
+			if (len0 >= kmin && len0 <= 0xffffu && k1_fits_tiles(e, (uint32_t)len0)) { // (a mixed list with reads too long for K1's tiled staging: row slots, chunked)
+				const HostBin one{nullptr, n_reads, (uint32_t)len0, false};
+				return submit_tiled_host(e, &one, 1, len_of, ptr_of);
+			}
+		} else { // (also under a list of which a part is K1's — K1 gets a slot table derived from the tiles' prefix tables)
+			constexpr uint32_t kMaxC = 0x10000u / 16u;
+			std::vector<uint32_t> per_c(kMaxC + 1, 0u);
+			for (uint64_t i = 0; i < n_reads; ++i) {
+				const uint64_t l = len_of(i);
+				if (l >= kmin && l <= 0xffffu) ++per_c[(l + 15u) / 16u];
+			}
+			std::vector<uint64_t> rest;
+			std::vector<std::vector<uint64_t>> bins; // (only the bins that are taken)
+			std::vector<int32_t> bin_of(kMaxC + 1, -1);
+			for (uint32_t c = 1; c <= kMaxC; ++c)
+				if (per_c[c] >= bin_min && k1_fits_tiles(e, 16u * c)) {
+					bin_of[c] = (int32_t)bins.size();
+					bins.emplace_back();
+					bins.back().reserve(per_c[c]);
+				}
+			if (!bins.empty()) {
+				for (uint64_t i = 0; i < n_reads; ++i) {
+					const uint64_t l = len_of(i);
+					const int32_t b = (l >= kmin && l <= 0xffffu) ? bin_of[(l + 15u) / 16u] : -1;
+					if (b >= 0) bins[(size_t)b].push_back(i);
+					else rest.push_back(i);
+				}
+				std::vector<HostBin> hbins;
+				for (uint32_t c = kMaxC; c >= 1; --c) { // (longest bin first)
+					if (bin_of[c] < 0) continue;
+					std::vector<uint64_t>& idx = bins[(size_t)bin_of[c]];
+					// longest first: a counting sort by the 16 possible tails (stable)
+					std::vector<uint64_t> sorted(idx.size());
+					size_t start[17] = { 0 };
+					for (uint64_t i : idx)
+						++start[16u - (uint32_t)(len_of(i) - 16u * (c - 1u))]; // tail 16 -> bucket 0
+					size_t acc = 0;
+					for (int t = 0; t < 17; ++t) {
+						const size_t n = start[t];
+						start[t] = acc;
+						acc += n;
+					}
+					for (uint64_t i : idx)
+						sorted[start[16u - (uint32_t)(len_of(i) - 16u * (c - 1u))]++] = i;
+					idx.swap(sorted);
+					hbins.push_back(HostBin{idx.data(), idx.size(), 16u * c, true});
+				}
+				// all the bins in one staging buffer and one launch per k (up to 8 bins: run_tiled_segs groups the rest)
+				if (int rc = submit_tiled_host(e, hbins.data(), (uint32_t)hbins.size(), len_of, ptr_of)) return rc;
+				if (rest.empty()) return 0;
+				return submit_rows(e, rest.size(), [&](uint64_t i) { return len_of(rest[i]); }, [&](uint64_t i) { return ptr_of(rest[i]); });
+			}
+		}
+	}
+	return submit_rows(e, n_reads, len_of, ptr_of);
+}
+
+} // namespace
+
+extern "C" {
+
+int ntc_submit(ntc_engine* e, const char* bases, const uint64_t* offsets, uint64_t n_reads)
+{
+	if (!e) return fail(NTC_ERR_ARG, "ntc_submit: null engine");
+	if (n_reads == 0) return 0;
+	if (!bases || !offsets) return fail(NTC_ERR_ARG, "ntc_submit: null buffer");
+	for (uint64_t i = 0; i < n_reads; ++i)
+		if (offsets[i + 1] < offsets[i]) return fail(NTC_ERR_ARG, "ntc_submit: offsets not monotone at read %llu", (unsigned long long)i);
+	return submit_impl(e, n_reads, [&](uint64_t i) { return offsets[i + 1] - offsets[i]; }, [&](uint64_t i) { return bases + offsets[i]; });
+}
+
+int ntc_submit_spans(ntc_engine* e, const char* buf, const uint64_t* starts, const uint32_t* lens, uint64_t n_reads)
+{
+	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_spans: null engine");
+	if (n_reads == 0) return 0;
+	if (!buf || !starts || !lens) return fail(NTC_ERR_ARG, "ntc_submit_spans: null buffer");
+	return submit_impl(e, n_reads, [&](uint64_t i) { return (uint64_t)lens[i]; }, [&](uint64_t i) { return buf + starts[i]; });
+}
+
+int ntc_submit_device(ntc_engine* e, const void* d_slots, uint64_t n_reads, uint32_t read_len, uint32_t stride)
+{
+	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_device: null engine");
+	if (n_reads == 0) return 0;
+	if (!d_slots || (stride & 3u) || stride < read_len || ((uintptr_t)d_slots & 15u))
+		return fail(NTC_ERR_ARG, "ntc_submit_device: need 16-byte aligned slots, stride %% 4 == 0, stride >= read_len");
+	if (read_len > 0xffffu) return fail(NTC_ERR_ARG, "ntc_submit_device: read_len %u > 65535", read_len);
+	std::lock_guard<std::mutex> lk(e->mu);
+	HIP_TRY(hipSetDevice(e->device));
+	return run_batch(e, (const unsigned char*)d_slots, nullptr, n_reads, read_len, stride);
+}
+
+int ntc_submit_tiled_device(ntc_engine* e, const void* d_tiles, uint64_t n_reads, uint32_t read_len)
+{
+	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_tiled_device: null engine");
+	if (n_reads == 0) return 0;
+	if (!d_tiles || ((uintptr_t)d_tiles & 15u)) return fail(NTC_ERR_ARG, "ntc_submit_tiled_device: need a 16-byte aligned buffer");
+	if (read_len == 0 || read_len > 0xffffu) return fail(NTC_ERR_ARG, "ntc_submit_tiled_device: read_len %u outside 1..65535", read_len);
+	std::lock_guard<std::mutex> lk(e->mu);
+	HIP_TRY(hipSetDevice(e->device));
+	return defer_or_run_tiled(e, TiledSeg{(const unsigned char*)d_tiles, n_reads, read_len, nullptr});
+}
+
+int ntc_submit_tiled_ragged_device(ntc_engine* e, const void* d_tiles, uint64_t n_reads, uint32_t n_chunks, const uint32_t* d_tails)
+{
+	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: null engine");
+	if (n_reads == 0) return 0;
+	if (!d_tiles || ((uintptr_t)d_tiles & 15u) || !d_tails || ((uintptr_t)d_tails & 3u)) return fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: need a 16-byte aligned tile buffer and a tails array");
+	if (n_chunks == 0 || n_chunks > 0xffffu / 16u) return fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: n_chunks %u outside 1..4095", n_chunks);
+	std::lock_guard<std::mutex> lk(e->mu);
+	HIP_TRY(hipSetDevice(e->device));
+	return defer_or_run_tiled(e, TiledSeg{(const unsigned char*)d_tiles, n_reads, 16u * n_chunks, d_tails});
+}
+
+int ntc_submit_tiled_bins_device(ntc_engine* e, uint32_t n_bins, const void* const* d_tiles, const uint64_t* n_reads, const uint32_t* read_len,
+                                 const uint32_t* const* d_tails)
+{
+	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_tiled_bins_device: null engine");
+	if (n_bins == 0) return 0;
+	if (!d_tiles || !n_reads || !read_len) return fail(NTC_ERR_ARG, "ntc_submit_tiled_bins_device: null argument"); // (d_tails == NULL: every bin is equal-length)
+	std::vector<TiledSeg> segs;
+	for (uint32_t i = 0; i < n_bins; ++i) {
+		if (n_reads[i] == 0) continue;
+		const uint32_t* tails_i = d_tails ? d_tails[i] : nullptr;
+		if (!d_tiles[i] || ((uintptr_t)d_tiles[i] & 15u) || ((uintptr_t)tails_i & 3u)) return fail(NTC_ERR_ARG, "ntc_submit_tiled_bins_device: bin %u: need a 16-byte aligned tile buffer", i);
+		if (read_len[i] == 0 || read_len[i] > 0xffffu || (tails_i && (read_len[i] & 15u)))
+			return fail(NTC_ERR_ARG, "ntc_submit_tiled_bins_device: bin %u: read_len %u (a ragged bin's is 16 x its chunks, at most 65520)", i, read_len[i]);
+		segs.push_back(TiledSeg{(const unsigned char*)d_tiles[i], n_reads[i], read_len[i], tails_i});
+	}
+	if (segs.empty()) return 0;
+	std::lock_guard<std::mutex> lk(e->mu);
+	HIP_TRY(hipSetDevice(e->device));
+	return run_tiled_segs(e, segs.data(), (uint32_t)segs.size());
+}
+
+} // extern "C"

@@ -5,7 +5,7 @@ Every other GPU test reaches the update through a hash kernel, so the keys it se
 `np.unique(keys, return_counts=True)` — exact, no hashing.  The key sets are built from the geometry (which digit, slice and word slot a key falls in)
 and never from what a kernel returned; every expected value is numpy's count of the injected keys.
 
-`Geo` restates `plan_log` (ntc_engine.hip) for ONE purpose: to aim the key sets (which bits are a pass's digit, how many keys overflow a run).  No
+`Geo` restates `plan_log` (ntc_plan.hip) for ONE purpose: to aim the key sets (which bits are a pass's digit, how many keys overflow a run).  No
 assertion on a kernel's output depends on it — a wrong restatement could only make a key set miss the branch it aims at, never make a wrong sketch pass.
 What of it can be seen from outside is checked: the log takes `room` keys and refuses `room + 1` (test_refusals).
 """

@@ -868,3 +868,51 @@ def test_randomised_shapes_small():
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz_parity.py"), "60", "2024"], stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:]
+
+
+def test_engine_lifecycle_returns_device_memory(nt):
+    """Create -> drive -> destroy returns every device buffer an engine took: row slots, a tiled batch, host submits (equal-length: tiled staging; ragged:
+    row staging with slot metadata) and a finish with profiling on, then an nthll engine, several times over.
+
+    Bound: the free device memory at the end of a cycle may differ between cycles by less than the engine's SMALLEST configuration-sized buffer, the value
+    histogram [n_k][2][65536] x 4 B = 1.5 MiB for the three k used here.  Every other buffer of this engine is larger (the sketch, 24 MiB at r_bits = 20; the
+    hit log and its partition areas, 4 x the sketch each; the staging pairs and K1h's hand-over arrays, 0.6 MiB and up, all leaked TOGETHER if their owner is),
+    so a cycle that leaks any of them moves the figure by at least the bound, and a leak repeats every cycle; the few words of state (F1, the dirty word: 8 B ..
+    1 KiB) are below what the allocator's granularity lets this figure resolve.  The first cycle is a warm-up: the runtime loads its code objects and fills its own
+    pools there.  The batch buffers are torch's and stay allocated throughout."""
+    dev = torch.device("cuda:0")
+    klist, r_bits, s_bits = [24, 32, 48], 20, 7
+    n, L, stride = 4096, 150, 152
+    slots = torch.empty(n * stride + 16, dtype=torch.uint8, device=dev)
+    nt.gen_reads_device(slots.data_ptr(), 3, 0, n, L, stride, 1, genome_len=200_000)
+    torch.cuda.synchronize()
+    host = slots[: n * stride].cpu().numpy()
+    reads = [host[i * stride: i * stride + L].tobytes() for i in range(n)]
+    rng = np.random.default_rng(5)
+    trimmed = [r[: int(l)] for r, l in zip(reads, rng.integers(60, 151, size=n))]
+    tiles = torch.from_numpy(nt.tile_reads(reads, L)).to(dev)
+
+    def cycle():
+        with nt.Engine(klist, r_bits=r_bits, s_bits=s_bits, device=0) as e:
+            e.set_profiling(True)
+            e.submit_device(slots.data_ptr(), n, L, stride)
+            e.submit_tiled_device(tiles.data_ptr(), n, L)
+            e.submit_reads(reads)
+            e.submit_reads(trimmed)
+            tc, ph, f1 = e.finish(counters=True)
+            e.kernel_time(), e.fixup_time(), e.apply_time()
+        with nt.HllEngine(32, n_bits=14, device=0) as h:
+            h.submit_device(slots.data_ptr(), n, L, stride)
+            h.finish()
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(dev)[0], f1
+
+    _, f1_first = cycle()
+    free = []
+    for _ in range(5):
+        f, f1 = cycle()
+        free.append(f)
+        assert np.array_equal(f1, f1_first)
+    bound = len(klist) * 2 * 65536 * 4
+    print("free device memory after each cycle:", free, "bound:", bound)
+    assert max(free) - min(free) < bound, (free, bound)

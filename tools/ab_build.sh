@@ -5,7 +5,7 @@ set -e
 NAME=$1; shift
 C=$(cd $(dirname $0)/../ntcard_amd/csrc && pwd)
 T=/tmp/ab_$NAME; mkdir -p $T
-for f in ntc_kernels ntc_sketch_hf ntc_sketch_k1h ntc_apply ntc_engine; do
+for f in ntc_kernels ntc_sketch_hf ntc_sketch_k1h ntc_apply ntc_plan ntc_launch ntc_submit ntc_lifecycle ntc_merge ntc_device_tools; do
   /opt/rocm/bin/hipcc "$@" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$C -c $C/$f.hip -o $T/$f.o &
 done
 wait
