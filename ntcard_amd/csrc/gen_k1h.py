@@ -31,119 +31,16 @@ fixup_kernel) recomputes exactly those (read, block) pairs from the raw bytes wi
 (ntHashIterator.hpp:59-86).  F1 here counts every window; K1f takes the invalid ones back.
 
 Nothing is copied from the reference: the four seeds are its constants (nthash.hpp:25-28), everything else is derived (k1h_terms.py).
+
+The generator in three modules: k1h_regs.py (LDS geometry, the checked register map, the kernel arguments), k1h_exp.py (the K1H_EXP timing
+switches and their post-pass) and this one: class Gen, whose build() strings the kernel together from named stages.
 """
-import os
 import sys
 
 from k1h_terms import step_terms, ttbl, g_of, hseed, rol31, tt4, COMP, CODE2  # noqa: F401
 from k1h_asm import Prog, v, s, vr, sr, schedule
-
-WAVES = 8                    # waves per workgroup = tiles in flight per CU: two per SIMD (round 5; six in round 4, when a wave's ring was three whole chunks)
-QSLOT = 2048                 # one QUARTER of a packed chunk: 4 bases x 2048 reads = [8 rows][64 lanes] dwords, byte t of row i = the read 64 (i + 8 t) + lane
-RQ_MAX = 9                   # quarter-slots of the ring: 4 j + 5 are in use, j = (k - 1) div 16 (what 4 windows span, see quarter_enter)
-RING_BYTES = RQ_MAX * QSLOT  # 18 KiB (round 4: three packed chunks, 24 KiB)
-QCAP = 128                   # queue items, kept as three arrays — hit word, reverse-strand mask (dwords), meta (16 bits: that is what lets 128 items fit) — of QCAP + one
-QSTRIDE = QCAP + 1           # dummy slot: a lane with nothing to queue writes there, so the writes need no exec mask (an exec write costs ~2 issue slots).
-                             # 128 items, not 64 (round 5): a pass for want of room then always finds 64 items (it ran with 49 on average, the queue could never hold a full
-                             # pass AND a step), 154 passes per two tiles instead of 175 (tools: the queue simulation behind DESIGN 5)
-Q_META_OFF = QSTRIDE * 8     # byte offset of the meta array behind the two dword arrays
-WAREA = (RING_BYTES + QSTRIDE * 10 + 15) // 16 * 16  # 19728 bytes per wave
-TABLE_OFF = WAVES * WAREA    # 153728: [2 strands][NG][64] dwords
-LDS_BYTES = 160 * 1024
-
-
-def n_groups(k):
-    return (k + 2) // 3
-
-
-def table_bytes(k):
-    return 2 * n_groups(k) * 256
-
-
-# ---- register map ------------------------------------------------------------------------------------------
-# VGPRs
-V_LANE4, V_LANE16, V_QDUMMY, V_QBASE, V_WAVE4, V_ONE, V_EXP1, V_VMASK = range(0, 8)  # V_WAVE4: 4 x the wave's number in the launch
-V_D0, V_D1, V_D2, V_DN, V_CMASK, V_TACC, V_CARRY0, V_CARRY1, V_SPARE1 = range(8, 17)
-V_DMASK = 17       # reads of this block with a dirty piece in one of its three chunks (and valid): their candidates are SUSPECTS
-V_WRAPF, V_WRAPR = V_SPARE1, 254  # second homes of the two state bits that wrap around in a walk step (walk_step)
-V_F = 18           # F[31]   (register tuples — loads, 64-bit LDS items — must start at even registers on gfx90a+)
-V_R = 49           # R[31]
-V_H0 = 80          # chunk n-2 planes / P_next
-V_H1 = 112
-V_I = 144
-V_RAW = 176        # 8 slots x 4
-V_T = 208          # temps 208 .. 252
-V_PX = V_T         # forward candidate item (x, y)
-V_RX = V_T + 2     # reverse candidate item
-V_SXF = V_T + 4    # the same for suspects
-V_SXR = V_T + 6
-V_TIEW = V_T + 1   # windows of the step whose strands tie on the top bits
-V_T0 = V_T + 4     # scratch of the walk / test / pack: V_T0 .. V_T0 + 29 (the suspect pairs are written behind the test, whose scratch they share)
-V_TP = V_T + 8     # scratch of the resolve pass: V_TP .. V_TP + 25; the transpose uses V_T .. V_T + 31
-# constants that VOP3 instructions cannot take as literals (gfx9: one SGPR or inline constant per instruction, no 32-bit literal)
-V_CMUL, V_CPERMLO, V_CPERMHI, V_CP16A, V_CP16B, V_CP8A, V_CP8B, V_CM4, V_CM2, V_CM1, V_CQMASK4, V_CBYTE = [V_T0 + 30 + i for i in range(12)]
-assert V_CBYTE <= 254
-VCONST = ((V_CMUL, 0x00820820), (V_CPERMLO, 0x0c0c0703), (V_CPERMHI, 0x07030c0c), (V_CP16A, 0x05040100), (V_CP16B, 0x07060302),
-          (V_CP8A, 0x06020400), (V_CP8B, 0x07030501), (V_CM4, 0x0f0f0f0f), (V_CM2, 0x33333333), (V_CM1, 0x55555555), (V_CQMASK4, (QCAP - 1) * 4), (V_CBYTE, 0x703))
-N_VGPRS = 255
-
-# SGPRs: s0 .. S_BASE - 1 are left to the compiler (the asm statement's few inputs live there)
-S_BASE = 26
-_sn = [S_BASE]
-
-
-def _salloc(n=1, align=1):
-    while _sn[0] % align or (_sn[0] < 34 and _sn[0] + n > 32):  # s32 / s33 are the ABI's stack and frame pointer: reserved even in a kernel without a stack
-        _sn[0] += 1
-    r = _sn[0]
-    _sn[0] += n
-    return r
-
-
-S_EXP0 = _salloc()
-S_CHUNKB = _salloc()         # bytes of one tile's slots = C * 32768 (the product with the tile index is 64-bit)
-S_DESC = _salloc(4, 4)       # tile being loaded
-S_TILES = _salloc(2, 2)
-S_SK = _salloc(2, 2)
-S_SUS = _salloc(2, 2)        # this wave's region of the suspect list
-S_DIRTY = _salloc(2, 2)
-S_TIE = _salloc(2, 2)
-S_LOGBASE = _salloc(2, 2)    # current log region
-S_RET = _salloc(2, 2)
-S_F1ACC = _salloc(2, 2)
-S_TMP = _salloc(2, 2)        # 64-bit scratch
-S_KARG = _salloc(2, 2)       # kept: the pointers needed once in a while (log, log_fill, f1) are re-read from the kernel arguments
-S_F0, S_S0 = _salloc(), _salloc()  # first block this wave owns / walks
-S_SUSOFF, S_SUSCAP = _salloc(), _salloc()  # bytes used / capacity of the suspect region
-S_NTILES, S_C, S_L, S_NVLAST, S_KEYBASE, S_RMASK2, S_LOGREG, S_LOGCAP4 = [_salloc() for _ in range(8)]  # (loaded in this order)
-S_NB, S_FEND = _salloc(), _salloc()
-S_WF = _salloc()             # flat index (tile * NB + block) of the block being walked
-S_LREG, S_LFILL4, S_USELOG = [_salloc() for _ in range(3)]
-S_NWAVES = _salloc()
-S_WT, S_WN = _salloc(), _salloc()      # block being walked
-S_PT, S_PN, S_PREAL = _salloc(), _salloc(), _salloc()  # chunk being packed
-S_QT, S_QN, S_QREAL = _salloc(), _salloc(), _salloc()  # chunk being loaded next
-S_PSOFF, S_QSOFF = _salloc(), _salloc()
-S_STEPMASK = _salloc()
-S_RQ = [_salloc() for _ in range(RQ_MAX)]  # LDS addresses of the ring's quarter-slots in window order: S_RQ[i] holds byte i of the oldest window still to be resolved
-S_QHEAD4, S_QTAIL4 = _salloc(), _salloc()
-S_N, S_A, S_B, S_CC = _salloc(), _salloc(), _salloc(), _salloc()  # scalar scratch
-S_SPARE = _salloc()
-S_END = _sn[0]
-assert S_END <= 100, S_END
-# S_STEPMASK: bits 0 .. 15 the steps of this block that complete a window of every read; bits 16 .. 31 (ragged batches, K1hArgs.tails != NULL) the steps that
-# end in the reads' last 16-base piece.  S_USELOG: bit 0 the hit log is in use, bit 8 the batch is ragged, bit 9 the queue is being emptied (read by the pass).
-# (The compiler reserves s100 / s101 next to VCC, FLAT_SCRATCH and XNACK_MASK: nothing of the kernel may live there.)
-F_USELOG, F_RAGGED, F_DRAIN = 0, 8, 9
-
-S_TACC = (S_F1ACC, S_F1ACC + 1, S_SPARE, S_SUSOFF)  # timing build only (S_SUSCAP = the last time stamp): no F1, no suspects
-
-# the asm statement's "s" operands, in order
-INPUTS = ["karg_lo", "karg_hi", "wave_gid", "n_waves", "lds_wbase", "first_block", "end_block"]
-# byte offsets in struct K1hArgs (ntc_kernels.hpp); the kernel reads them with scalar loads
-KARG = dict(tiles=0, log=8, log_fill=16, sketch0=24, f1=32, dirty=40, tie=48, n_tiles=56, n_chunks=60, read_len=64, nv_last=68, key_base=72,
-            rmask2=76, log_regions=80, log_region_cap=84, table=88, blocks_per_wave=104, nb_magic=108, sus=112, sus_count=120, sus_cap=128, s_bits=96, tails=144,
-            sk_dirty=160)
+from k1h_exp import SWITCHES, parse_exp, phase_fix
+from k1h_regs import *  # noqa: F401,F403 (the register map is this module's vocabulary; tests and tools read KARG, WAVES, S_END, ... from here)
 
 
 class Gen:
@@ -171,13 +68,18 @@ class Gen:
             self.rg_terms = [(tt4(jj + 1 - self.g0, True), tt4(jj - self.g1, True)) for jj in range(31)]
         self.cold = []                      # out-of-line fragments (emitted behind the chunk loop): the common path of a test falls through —
                                             # a taken branch costs a lone wave an instruction-buffer refill
-        self.exp = set(x for x in os.environ.get("K1H_EXP", "").split(",") if x)  # timing experiments (tools/k1h_variant.sh): WRONG results
+        self.exp = parse_exp()              # timing experiments (K1H_EXP, k1h_exp.py; tools/k1h_variant.sh)
+
+    def on(self, switch):
+        """is the timing experiment `switch` (k1h_exp.SWITCHES) on?"""
+        assert switch in SWITCHES, switch
+        return switch in self.exp
 
     def lbl(self, base):
         self.uid += 1
         return f"{base}{self.uid}"
 
-    # ---- small helpers ----
+    # ---- small helpers: one emitter per sequence that recurs ----
     def bitop3(self, d, a, b, c, fn):
         self.p.i("v_bitop3_b32", d, a, b, c, mods=f"bitop3:0x{ttbl(fn):02x}")
 
@@ -187,14 +89,112 @@ class Gen:
         self.p.i("s_branch", "@" + target)
 
     def ret(self):
-        self.p.i("s_add_u32", s(S_RET), s(S_RET), 4)
-        self.p.i("s_addc_u32", s(S_RET + 1), s(S_RET + 1), 0)
+        self.add64(S_RET, S_RET, 4)
         self.p.i("s_setpc_b64", sr(S_RET, 2))
+
+    def add64(self, d, a, lo, hi=0):
+        """s[d:d+1] = s[a:a+1] + hi:lo (operands)"""
+        self.p.i("s_add_u32", s(d), s(a), lo)
+        self.p.i("s_addc_u32", s(d + 1), s(a + 1), hi)
+
+    def mul64(self, lo, hi, a, b):
+        """s(hi):s(lo) = s(a) x s(b)"""
+        self.p.i("s_mul_i32", s(lo), s(a), s(b))
+        self.p.i("s_mul_hi_u32", s(hi), s(a), s(b))
+
+    def karg_load(self, dst, name, n=2, wait=False):
+        """s(dst) (n = 1) or s[dst:dst+1] <- the kernel argument `name`"""
+        self.p.i("s_load_dwordx2" if n == 2 else "s_load_dword", sr(dst, 2) if n == 2 else s(dst), sr(S_KARG, 2), hex(KARG[name]))
+        if wait:
+            self.p.i("s_waitcnt", "lgkmcnt(0)")
+
+    def unless_flag(self, bit, target):
+        """branch to target if bit `bit` of S_USELOG (F_USELOG, F_RAGGED, F_DRAIN) is clear"""
+        self.p.i("s_bitcmp1_b32", s(S_USELOG), bit)
+        self.p.i("s_cbranch_scc0", "@" + target)
+
+    def mbcnt(self, dst, lo, hi):
+        """v(dst) = set bits of the 64-bit mask hi:lo (operands) below the lane"""
+        self.p.i("v_mbcnt_lo_u32_b32", v(dst), lo, 0)
+        self.p.i("v_mbcnt_hi_u32_b32", v(dst), hi, v(dst))
+
+    def f1_add(self, n):
+        """F1 += s(n) (the timing build keeps its clocks there)"""
+        if not self.on("timers"):
+            self.add64(S_F1ACC, S_F1ACC, s(n))
+
+    def valid_reads(self, dst):
+        """s(dst) = valid reads of the tile being walked: all 2048 but in a partial last tile"""
+        p = self.p
+        p.i("s_add_u32", s(dst), s(S_WT), 1)
+        p.i("s_cmp_eq_u32", s(dst), s(S_NTILES))
+        p.i("s_cselect_b32", s(dst), s(S_NVLAST), 2048)
+
+    def prefix_mask(self, dst, n, signed):
+        """v(dst) bit m = (64 m + lane < s(n)): cnt = clamp((n - lane + 63) >> 6, 0, 32) low bits set (n <= 2048).  signed: n - lane may be
+        negative (n = 0 .. lane: no bit); unsigned: n >= 1 and lane <= 63, never negative.  Scratch: V_MISC, V_MISC + 1"""
+        p = self.p
+        T = V_MISC
+        p.i("v_lshrrev_b32", v(T), 2, v(V_LANE4))
+        p.i("v_sub_u32", v(T), s(n), v(T))                      # n - lane
+        p.i("v_add_u32", v(T), 63, v(T))
+        if signed:
+            p.i("v_ashrrev_i32", v(T), 6, v(T))
+            p.i("v_max_i32", v(T), 0, v(T))
+        else:
+            p.i("v_lshrrev_b32", v(T), 6, v(T))                 # groups m with 64 m + lane < n
+        p.i("v_min_u32", v(T), 32, v(T))
+        p.i("v_cmp_gt_u32_e32", "vcc", 32, v(T))
+        p.i("v_lshlrev_b32", v(T + 1), v(T), v(V_ONE))
+        p.i("v_add_u32", v(T + 1), -1, v(T + 1))
+        p.i("v_cndmask_b32_e64", v(dst), -1, v(T + 1), "vcc")
+
+    def block_masks(self):
+        """V_CMASK / V_DMASK of the block from V_D0 .. V_D2 and V_VMASK: candidates are dropped (become suspects) wherever one of the block's
+        three chunks holds a dirty piece of the read.  Scratch: V_MISC"""
+        p = self.p
+        p.i("v_or3_b32", v(V_MISC), v(V_D0), v(V_D1), v(V_D2))
+        self.bitop3(v(V_CMASK), v(V_MISC), v(V_VMASK), v(V_VMASK), lambda x, y, z: (1 ^ x) & y)
+        p.i("v_and_b32", v(V_DMASK), v(V_MISC), v(V_VMASK))
+
+    def load_slot(self, i):
+        """raw slot i <- 1024 bytes at soffset S_A (slots 0 .. 3) / S_B (4 .. 7) of the tile in S_DESC"""
+        if not self.on("noload"):
+            self.p.i("buffer_load_dwordx4", vr(V_RAW + 4 * i, 4), v(V_LANE16), sr(S_DESC, 4), s(S_A if i < 4 else S_B), mods=f"offen offset:{(i & 3) * 1024} nt")
+
+    def load_slots(self):
+        """the eight loads of one batch, in slot order (pack_batch counts on that order)"""
+        for i in range(8):
+            self.load_slot(i)
+
+    def shift_planes(self):
+        """(H0, H1) <- (H1, I)"""
+        for i in range(32):
+            self.p.i("v_mov_b32", v(V_H0 + i), v(V_H1 + i))
+        for i in range(32):
+            self.p.i("v_mov_b32", v(V_H1 + i), v(V_I + i))
+
+    def queue_put(self, slot, mslot, word, zr, meta, meta_or=None):
+        """one queue item (word, zr, meta) per lane of vcc, S_A = their number (a lane outside vcc writes the dummy slot).  slot, mslot: scratch;
+        meta_or: v(meta) = meta_or | 4 x lane on the way"""
+        p = self.p
+        self.mbcnt(slot, "vcc_lo", "vcc_hi")
+        p.i("v_lshl_add_u32", v(slot), v(slot), 2, s(S_QTAIL4))
+        p.i("v_and_b32", v(slot), v(V_CQMASK4), v(slot))
+        if meta_or is not None:
+            p.i("v_or_b32", v(meta), hex(meta_or), v(V_LANE4))
+        p.i("v_cndmask_b32_e64", v(slot), v(V_QDUMMY), v(slot), "vcc")     # V_QDUMMY = 4 QCAP: the dummy slot
+        p.i("v_lshrrev_b32", v(mslot), 1, v(slot))                          # (the meta array is 16 bits wide)
+        p.i("v_add_u32", v(mslot), v(V_QBASE), v(mslot))
+        p.i("v_add_u32", v(slot), v(V_QBASE), v(slot))
+        p.i("ds_write2_b32", v(slot), v(word), v(zr), mods=f"offset0:0 offset1:{QSTRIDE}")
+        p.i("ds_write_b16", v(mslot), v(meta), mods=f"offset:{Q_META_OFF}")
+        p.i("s_lshl2_add_u32", s(S_QTAIL4), s(S_A), s(S_QTAIL4))
 
     def probe(self, sec):
         """timing build (K1H_EXP=timers): the clocks since the last probe go to section `sec` (0 walk + test + push, 1 pack, 2 resolve
         passes, 3 end of block); the four sums are added to f1[1 .. 4] at the end (bench.py --k1h-timers).  F1 itself is not kept."""
-        if "timers" not in self.exp:
+        if not self.on("timers"):
             return
         p = self.p
         p.i("s_memtime", sr(S_TMP, 2))
@@ -282,39 +282,23 @@ class Gen:
         prefix of it (longest first): the candidate masks shrink to it (they only ever shrink until the tile ends: the steps in the last piece come in the
         order of d) and F1 takes n windows."""
         p = self.p
-        T = V_T0
         p.label("tailsub")
-        p.i("s_load_dwordx2", sr(S_TMP, 2), sr(S_KARG, 2), hex(KARG["tails"]))
+        self.karg_load(S_TMP, "tails")
         p.i("s_lshl_b32", s(S_A), s(S_WT), 6)
         p.i("s_add_u32", s(S_A), s(S_A), s(S_B))
         p.i("s_waitcnt", "lgkmcnt(0)")
         p.i("s_load_dword", s(S_A), sr(S_TMP, 2), s(S_A))
         p.i("s_waitcnt", "lgkmcnt(0)")
-        if "timers" not in self.exp:
-            p.i("s_add_u32", s(S_F1ACC), s(S_F1ACC), s(S_A))
-            p.i("s_addc_u32", s(S_F1ACC + 1), s(S_F1ACC + 1), 0)
-        # bit m of the prefix mask = (64 m + lane < n): cnt = clamp((n - lane + 63) >> 6, 0, 32) low bits (n <= 2048; n = 0: none)
-        p.i("v_lshrrev_b32", v(T), 2, v(V_LANE4))
-        p.i("v_sub_u32", v(T), s(S_A), v(T))                    # n - lane (may be negative: lane >= n)
-        p.i("v_add_u32", v(T), 63, v(T))
-        p.i("v_ashrrev_i32", v(T), 6, v(T))
-        p.i("v_max_i32", v(T), 0, v(T))
-        p.i("v_min_u32", v(T), 32, v(T))
-        p.i("v_cmp_gt_u32_e32", "vcc", 32, v(T))
-        p.i("v_lshlrev_b32", v(T + 1), v(T), v(V_ONE))
-        p.i("v_add_u32", v(T + 1), -1, v(T + 1))
-        p.i("v_cndmask_b32_e64", v(T + 1), -1, v(T + 1), "vcc")
-        p.i("v_and_b32", v(V_VMASK), v(V_VMASK), v(T + 1))
-        p.i("v_or3_b32", v(T), v(V_D0), v(V_D1), v(V_D2))
-        self.bitop3(v(V_CMASK), v(T), v(V_VMASK), v(V_VMASK), lambda x, y, z: (1 ^ x) & y)
-        p.i("v_and_b32", v(V_DMASK), v(T), v(V_VMASK))
+        self.f1_add(S_A)
+        self.prefix_mask(V_MISC + 1, S_A, signed=True)          # (lane >= n: no read of the lane is that long)
+        p.i("v_and_b32", v(V_VMASK), v(V_VMASK), v(V_MISC + 1))
+        self.block_masks()
         self.ret()
 
     def walk_step(self, a):
         i0, i1, o0, o1 = self.planes_of_step(a)
-        tpool = [V_T0 + 1 + i for i in range(22)][::-1]  # function planes: V_T0 + 1 ..; V_T0 = the wrap-around copy
+        tpool = [V_WALK + i for i in range(N_WALK)][::-1]  # function planes
         cin, cout, clv, cen = {}, {}, {}, {}
-        tmp = V_T0
         if self.gap:
             l0 = self.plane_back(a, self.k - self.g0)       # leaves the don't-care block (window index g0 -> g0 - 1)
             e0 = self.plane_back(a, self.k - 1 - self.g1)   # enters it (g1 + 1 -> g1)
@@ -394,24 +378,24 @@ class Gen:
     def flags_and_push(self, a):
         """candidate planes of step a (exact per strand), tie plane, then the two pushes"""
         p = self.p
-        T = V_T0
-        fo = dict(a=T + 1, g=T + 2, b=T + 3, nz=T + 4, t1=T + 9, t2=T + 10)
-        ro = dict(a=T + 5, g=T + 6, b=T + 7, nz=T + 8, t1=T + 9, t2=T + 10)
+        T = V_TEST
+        fo = dict(a=T + 0, g=T + 1, b=T + 2, nz=T + 3, t1=T + 8, t2=T + 9)
+        ro = dict(a=T + 4, g=T + 5, b=T + 6, nz=T + 7, t1=T + 8, t2=T + 9)
         self.strand_flags(V_F, fo)
         self.strand_flags(V_R, ro, top=V_WRAPR if a % 2 == 0 else V_R + 30)  # (behind an even step R's bit 30 sits in its second register)
-        cf, cr, tie = T + 11, T + 12, T + 13
+        cf, cr, tie = T + 10, T + 11, T + 12
         if self.sb == 7:
-            p.i("v_and_b32", v(T + 9), v(fo["b"]), v(ro["nz"]))
-            self.bitop3(v(cf), v(fo["a"]), v(ro["g"]), v(T + 9), lambda x, y, z: (x & y) | z)
-            p.i("v_and_b32", v(T + 9), v(ro["b"]), v(fo["nz"]))
-            self.bitop3(v(cr), v(ro["a"]), v(fo["g"]), v(T + 9), lambda x, y, z: (x & y) | z)
+            p.i("v_and_b32", v(T + 8), v(fo["b"]), v(ro["nz"]))
+            self.bitop3(v(cf), v(fo["a"]), v(ro["g"]), v(T + 8), lambda x, y, z: (x & y) | z)
+            p.i("v_and_b32", v(T + 8), v(ro["b"]), v(fo["nz"]))
+            self.bitop3(v(cr), v(ro["a"]), v(fo["g"]), v(T + 8), lambda x, y, z: (x & y) | z)
         else:
             self.bitop3(v(cf), v(fo["a"]), v(ro["g"]), v(fo["b"]), lambda x, y, z: (x & y) | z)
             self.bitop3(v(cr), v(ro["a"]), v(fo["g"]), v(ro["b"]), lambda x, y, z: (x & y) | z)
         p.i("v_and_b32", v(tie), v(cf), v(cr))
         self.bitop3(v(V_PX), v(cf), v(V_CMASK), v(tie), lambda x, y, z: x & y & (1 ^ z))
         self.bitop3(v(V_RX), v(cr), v(V_CMASK), v(tie), lambda x, y, z: x & y & (1 ^ z))
-        sus = "timers" not in self.exp
+        sus = not self.on("timers")
         if sus:
             # suspects: candidates of reads with a dirty piece near by — resolved like the others, then parked for K1f, which knows the bytes
             # ... and windows whose strands tie on the top bits: items of their own, marked as ties (K1f re-derives a tie's hash from the bytes, so
@@ -425,11 +409,11 @@ class Gen:
         self.push_items(a, V_PX, V_RX, 0)
         if sus:
             nosus, notdirty = self.lbl("nosus"), self.lbl("notdirty")
-            p.i("v_or3_b32", v(T + 4), v(V_SXF), v(V_SXR), v(V_TIEW))
-            p.i("v_cmp_ne_u32_e32", "vcc", 0, v(T + 4))
+            p.i("v_or3_b32", v(T + 3), v(V_SXF), v(V_SXR), v(V_TIEW))
+            p.i("v_cmp_ne_u32_e32", "vcc", 0, v(T + 3))
             p.i("s_cbranch_vccz", "@" + nosus)                 # (the common case: no suspect in this step)
-            p.i("v_or_b32", v(T + 4), v(V_SXF), v(V_SXR))
-            p.i("v_cmp_ne_u32_e32", "vcc", 0, v(T + 4))
+            p.i("v_or_b32", v(T + 3), v(V_SXF), v(V_SXR))
+            p.i("v_cmp_ne_u32_e32", "vcc", 0, v(T + 3))
             p.i("s_cbranch_vccz", "@" + notdirty)
             self.push_items(a, V_SXF, V_SXR, 1)
             p.label(notdirty)
@@ -448,11 +432,11 @@ class Gen:
         """queue the hit words of step a (xf: forward-strand candidates, xr: reverse; a read is never in both — ties are masked out or ride in
         xf alone): ONE item per lane = (xf | xr, meta, xr); resolve passes first while the queue lacks room"""
         p = self.p
-        T = V_TP
+        slot, word, meta, mslot = [V_PUSH + i for i in range(4)]
         chk, go = self.lbl("chk"), self.lbl("go")
         p.label(chk)
-        p.i("v_or_b32", v(T + 2), v(xf), v(xr))
-        p.i("v_cmp_ne_u32_e32", "vcc", 0, v(T + 2))
+        p.i("v_or_b32", v(word), v(xf), v(xr))
+        p.i("v_cmp_ne_u32_e32", "vcc", 0, v(word))
         p.i("s_bcnt1_i32_b64", s(S_A), "vcc")
         p.i("s_sub_u32", s(S_N), s(S_QTAIL4), s(S_QHEAD4))
         p.i("s_lshr_b32", s(S_N), s(S_N), 2)
@@ -463,29 +447,18 @@ class Gen:
 
         def cold_pass(full=full, chk=chk):
             p.label(full)
-            self.call("pass")                                    # (keeps V_T .. V_T + 7: the four hit words)
+            self.call("pass")                                    # (keeps the range "items": the four hit words)
             p.i("s_branch", "@" + chk)
         self.cold.append(cold_pass)
-        p.label(go)
-        meta = ((2 * a) << 9) | (suspect << 15) | (tie << 8)     # bits 0 .. 7: 4 x lane (added below)
-        p.i("v_mbcnt_lo_u32_b32", v(T + 1), "vcc_lo", 0)
-        p.i("v_mbcnt_hi_u32_b32", v(T + 1), "vcc_hi", v(T + 1))
-        p.i("v_lshl_add_u32", v(T + 1), v(T + 1), 2, s(S_QTAIL4))
-        p.i("v_and_b32", v(T + 1), v(V_CQMASK4), v(T + 1))
-        p.i("v_or_b32", v(T + 3), hex(meta), v(V_LANE4))
-        p.i("v_cndmask_b32_e64", v(T + 1), v(V_QDUMMY), v(T + 1), "vcc")   # V_QDUMMY = 4 QCAP: the dummy slot
-        p.i("v_lshrrev_b32", v(T + 4), 1, v(T + 1))                         # (the meta array is 16 bits wide)
-        p.i("v_add_u32", v(T + 4), v(V_QBASE), v(T + 4))
-        p.i("v_add_u32", v(T + 1), v(V_QBASE), v(T + 1))
-        p.i("ds_write2_b32", v(T + 1), v(T + 2), v(xr), mods=f"offset0:0 offset1:{QSTRIDE}")
-        p.i("ds_write_b16", v(T + 4), v(T + 3), mods=f"offset:{Q_META_OFF}")
-        p.i("s_lshl2_add_u32", s(S_QTAIL4), s(S_A), s(S_QTAIL4))
+        p.label(go)                                              # (nothing branches here; the label stays: it ends a scheduling region, and the output is pinned)
+        # meta bits 0 .. 7: 4 x lane (added by queue_put)
+        self.queue_put(slot, mslot, word, xr, meta, meta_or=((2 * a) << 9) | (suspect << 15) | (tie << 8))
 
     # ---- pack one group of 64 pieces: RAW slot i -> packed word in register dst; then reload the slot ----
-    def pack_group(self, i, dst, reload):
+    def pack_group(self, i, dst):
         p = self.p
         r = V_RAW + 4 * i
-        t = [V_T0 + 12 + 6 * (i % 3) + x for x in range(6)]  # three sets of scratch registers: the scheduler interleaves neighbouring groups
+        t = [V_PACK + 6 * (i % 3) + x for x in range(6)]  # three sets of scratch registers: the scheduler interleaves neighbouring groups
         # 2 x code of every byte: (ascii >> 1) & 3 = A 0, C 1, T / U 2, G 3 — the multiply-gather's input AND the index of the validity look-up:
         # the letter that code stands for (A, C, T, G), XORed with the byte, is zero or the case bit for exactly the bytes ACGTacgt.  (Round 4 looked
         # the letter up by byte & 7, which told U from T at the price of four more v_and per 16 bases; now a U is "dirty": its windows are K1f's,
@@ -499,7 +472,7 @@ class Gen:
                 p.i("v_xor_b32", v(x), v(e), v(r + q))
             else:
                 self.bitop3(v(x), v(e), v(r + q), v(x), lambda a, b, c: (a ^ b) | c)
-            if "nomul" in self.exp:
+            if self.on("nomul"):
                 p.i("v_lshlrev_b32", v(t[q]), 3, v(t[q]))
             else:
                 p.i("v_mul_lo_u32", v(t[q]), v(t[q]), v(V_CMUL))
@@ -507,23 +480,19 @@ class Gen:
         p.i("v_perm_b32", v(t[2]), v(t[3]), v(t[2]), v(V_CPERMHI))
         p.i("v_or_b32", v(dst), v(t[0]), v(t[2]))
         p.i("v_and_b32", v(x), "0xdfdfdfdf", v(x))
-        if "nocarry" in self.exp:
+        if self.on("nocarry"):
             p.i("v_or_b32", v(V_DN), v(V_DN), v(x))
         else:
             p.i("v_add_co_u32", v(t[5]), "vcc", -1, v(x))          # carry = (x != 0)
             p.i("v_addc_co_u32", v(V_DN), "vcc", v(V_DN), v(V_DN), "vcc")  # dirty bits, group m ends up at bit 31 - m
-        if reload is not None and "noload" not in self.exp:
-            soff, imm = reload
-            p.i("buffer_load_dwordx4", vr(r, 4), v(V_LANE16), sr(S_DESC, 4), s(soff), mods=f"offen offset:{imm} nt")
+        self.load_slot(i)
 
     def issue_batch(self, b, soff_base):
         """loads of batch b (groups 8 b .. 8 b + 7) of the chunk at soffset soff_base: S_A / S_B as scratch soffsets"""
         p = self.p
         p.i("s_add_u32", s(S_A), s(soff_base), b * 8192)
         p.i("s_add_u32", s(S_B), s(soff_base), b * 8192 + 4096)
-        for i in range(8):
-            if "noload" not in self.exp:
-                p.i("buffer_load_dwordx4", vr(V_RAW + 4 * i, 4), v(V_LANE16), sr(S_DESC, 4), s(S_A if i < 4 else S_B), mods=f"offen offset:{(i & 3) * 1024} nt")
+        self.load_slots()
 
     def pack_batch(self, b):
         """pack batch b of the chunk P into H0[8 b ..]; reload every slot with batch b + 1 of P, or — behind batch 3 — with batch 0 of
@@ -544,9 +513,8 @@ class Gen:
             p.label(notreal)
             for i in range(8):  # a chunk that does not exist: 'A's
                 p.i("v_mov_b32", v(V_H0 + 8 * b + i), 0)
-            if b == 3 and "noload" not in self.exp:          # the next chunk's first loads all the same
-                for i in range(8):
-                    p.i("buffer_load_dwordx4", vr(V_RAW + 4 * i, 4), v(V_LANE16), sr(S_DESC, 4), s(S_A if i < 4 else S_B), mods=f"offen offset:{(i & 3) * 1024} nt")
+            if b == 3:          # the next chunk's first loads all the same
+                self.load_slots()
             p.i("s_branch", "@" + skip)
         self.cold.append(cold_none)
         p.label(real)
@@ -554,12 +522,12 @@ class Gen:
         # the first four slots have arrived — and again, behind their four reloads, the other four.  vmcnt(0) would also wait for every STORE a
         # resolve pass has just issued (hit log, suspects: stores count in vmcnt on gfx9 and take a microsecond to be acknowledged).
         p.i("s_waitcnt", "vmcnt(4)")
-        if "nopack" in self.exp:
+        if self.on("nopack"):
             p.i("s_branch", "@" + skip)
         for i in range(8):
             if i == 4:
                 p.i("s_waitcnt", "vmcnt(4)")
-            self.pack_group(i, V_H0 + 8 * b + i, (S_A if i < 4 else S_B, (i & 3) * 1024))
+            self.pack_group(i, V_H0 + 8 * b + i)
         p.label(skip)
         self.probe(1)
 
@@ -574,23 +542,20 @@ class Gen:
         and H1 for I's; the second stage lands in I"""
         p = self.p
         A = [V_H0 + i for i in range(32)]
-        B = [V_T + i for i in range(32)]
+        B = [V_XPOSE + i for i in range(32)]
         O = [V_I + i for i in range(32)]
         for kk in range(32):  # J = 16: A -> B
             if kk & 16 == 0:
                 p.i("v_perm_b32", v(B[kk]), v(A[kk + 16]), v(A[kk]), v(V_CP16A))
                 p.i("v_perm_b32", v(B[kk + 16]), v(A[kk + 16]), v(A[kk]), v(V_CP16B))
-        for i in range(32):
-            p.i("v_mov_b32", v(V_H0 + i), v(V_H1 + i))
-        for i in range(32):
-            p.i("v_mov_b32", v(V_H1 + i), v(V_I + i))
+        self.shift_planes()
         for kk in range(32):  # J = 8: B -> O
             if kk & 8 == 0:
                 p.i("v_perm_b32", v(O[kk]), v(B[kk + 8]), v(B[kk]), v(V_CP8A))
                 p.i("v_perm_b32", v(O[kk + 8]), v(B[kk + 8]), v(B[kk]), v(V_CP8B))
 
     def transpose_quarter(self, q):
-        """I[8 q .. 8 q + 7]: quarter-major bytes -> the 8 planes of the bases 4 q .. 4 q + 3 (temps: V_T .. V_T + 7)"""
+        """I[8 q .. 8 q + 7]: quarter-major bytes -> the 8 planes of the bases 4 q .. 4 q + 3 (temps: V_XPOSE .. V_XPOSE + 7)"""
         p = self.p
         O = [V_I + 8 * q + i for i in range(8)]
         n = 0
@@ -598,7 +563,7 @@ class Gen:
             for kk in range(8):
                 if kk & J == 0:
                     x, y = O[kk], O[kk + J]
-                    b0, b1 = V_T + 2 * (n % 4), V_T + 2 * (n % 4) + 1  # (four pairs of temps: the pairs of a stage are independent of each other)
+                    b0, b1 = V_XPOSE + 2 * (n % 4), V_XPOSE + 2 * (n % 4) + 1  # (four pairs of temps: the pairs of a stage are independent of each other)
                     n += 1
                     p.i("v_lshlrev_b32", v(b0), J, v(y))
                     p.i("v_lshrrev_b32", v(b1), J, v(x))
@@ -632,29 +597,35 @@ class Gen:
         for i in range(self.rq - 1):
             p.i("s_mov_b32", s(S_RQ[i]), s(S_RQ[i + 1]))
         p.i("s_mov_b32", s(S_RQ[self.rq - 1]), s(S_A))
-        p.i("v_add_u32", v(V_T0 + 2), s(S_A), v(V_LANE4))
+        p.i("v_add_u32", v(V_MISC + 2), s(S_A), v(V_LANE4))
         for i in range(0, 8, 2):  # (offsets in units of 64 dwords: the slot's rows are 256 bytes apart)
-            p.i("ds_write2st64_b32", v(V_T0 + 2), v(V_I + 8 * q + i), v(V_I + 8 * q + i + 1), mods=f"offset0:{i} offset1:{i + 1}")
+            p.i("ds_write2st64_b32", v(V_MISC + 2), v(V_I + 8 * q + i), v(V_I + 8 * q + i + 1), mods=f"offset0:{i} offset1:{i + 1}")
         self.transpose_quarter(q)
         self.probe(3)
 
-    # ---- the resolve pass (subroutine) ----------------------------------------------------------------------
+    # ---- the resolve pass (subroutine), in six stages; its registers: class PS (k1h_regs.py) ------------------------
     def emit_pass(self):
+        self.pass_take_items()
+        self.pass_window()
+        self.pass_key()
+        self.pass_log()
+        self.pass_suspects()
+        self.pass_logswitch()
+
+    def pass_take_items(self):
+        """queue -> lanes.  Leaves: exec = the lanes with an item; per lane PS.m = the read group of the candidate being resolved (lowest set bit of the
+        hit word), PS.y = the item's meta, PS.tb = its strand; S_CC = the number of lanes.  What is left of a hit word is back in the queue."""
         p = self.p
-        T = V_TP
-        item = T            # (x, y)
-        m, rest, col, a0, a1, a2 = T + 2, T + 3, T + 4, T + 5, T + 6, T + 7
-        lo, hi, mid, tb, key, key1, t1 = T + 8, T + 9, T + 10, T + 11, T + 12, T + 13, T + 14
-        fld = [T + 15 + g for g in range(11)]
+        m, rest, col, tb, t1 = PS.m, PS.rest, PS.col, PS.tb, PS.t1
         p.label("pass")
         self.probe(0)
         # A resolving wave goes first on its SIMD: the pass is chains of LDS round trips and slow-class VALU instructions (v_bfe, v_lshl_add, v_perm
         # class: no overlap with the other wave's instructions, profiles/r05_ubench_op_classes.txt), the other wave of the SIMD is most likely walking
         # (full-rate v_bitop3 that fills any gap).  -4 % hash time (profiles/r05_k1h_priority_ab.txt); s_setprio around every run of slow-class
         # instructions gives the same, raising the WALK's priority nothing.
-        if "noprio" not in self.exp:
+        if not self.on("noprio"):
             p.i("s_setprio", 3)
-        if "nopass" in self.exp:
+        if self.on("nopass"):
             p.i("s_mov_b32", s(S_QHEAD4), s(S_QTAIL4))
             self.ret()
         # Items -> lanes, in rounds: the first round takes min(64, count) items.  A word with more than one candidate goes back to the END of the queue
@@ -662,8 +633,8 @@ class Gen:
         # are still idle take them in the next round (and so on for third candidates).  Without this a queue that has to be EMPTIED — before every
         # quarter of a block, quarter_enter — would end in passes of a handful of second and third candidates: 13.9 passes per block measured
         # against 8.6 with whole-chunk ring slots; with it a quarter's ~110 items are two passes.
-        x, zr = lo, hi                                        # the item's hit word and reverse-strand mask (until the requeue below: lo / hi are free until the window's bytes are in)
-        y = item + 1                                          # its meta (16 bits)
+        x, zr = PS.lo, PS.hi                                  # the item's hit word and reverse-strand mask (until the requeue below: lo / hi are free until the window's bytes are in)
+        y = PS.y                                              # its meta (16 bits)
         p.i("s_mov_b32", s(S_CC), 0)                          # lanes filled so far
         p.label("passload")
         p.i("s_sub_u32", s(S_N), s(S_QTAIL4), s(S_QHEAD4))
@@ -690,22 +661,12 @@ class Gen:
         p.i("v_and_b32", v(rest), v(rest), v(x))
         p.i("v_lshrrev_b32", v(tb), v(m), v(zr))
         p.i("v_and_b32", v(tb), 1, v(tb))                     # strand of the read being resolved
-        # ---- what is left of each word goes to the back of the queue (exec = the items of this round) ----
+        # ---- what is left of each word goes to the back of the queue (exec = the items of this round; a spent word goes to the dummy slot) ----
         p.i("v_cmp_ne_u32_e32", "vcc", 0, v(rest))
         p.i("s_bcnt1_i32_b64", s(S_A), "vcc")
-        p.i("v_mbcnt_lo_u32_b32", v(t1), "vcc_lo", 0)
-        p.i("v_mbcnt_hi_u32_b32", v(t1), "vcc_hi", v(t1))
-        p.i("v_lshl_add_u32", v(t1), v(t1), 2, s(S_QTAIL4))
-        p.i("v_and_b32", v(t1), v(V_CQMASK4), v(t1))
-        p.i("v_cndmask_b32_e64", v(t1), v(V_QDUMMY), v(t1), "vcc")   # (a spent word goes to the dummy slot)
-        p.i("v_lshrrev_b32", v(col), 1, v(t1))
-        p.i("v_add_u32", v(col), v(V_QBASE), v(col))
-        p.i("v_add_u32", v(t1), v(V_QBASE), v(t1))
-        p.i("ds_write2_b32", v(t1), v(rest), v(zr), mods=f"offset0:0 offset1:{QSTRIDE}")
-        p.i("ds_write_b16", v(col), v(y), mods=f"offset:{Q_META_OFF}")
-        p.i("s_lshl2_add_u32", s(S_QTAIL4), s(S_A), s(S_QTAIL4))
-        p.i("s_bitcmp1_b32", s(S_USELOG), F_DRAIN)            # another round?  only when the queue is being emptied (drain: a pass run for want of room
-        p.i("s_cbranch_scc0", "@passloaded")                  # leaves the words it puts back to the next one, which costs nothing) ...
+        self.queue_put(t1, col, rest, zr, y)
+        self.unless_flag(F_DRAIN, "passloaded")               # another round?  only when the queue is being emptied (drain: a pass run for want of room
+        #                                                       leaves the words it puts back to the next one, which costs nothing) ...
         p.i("s_cmp_lt_u32", s(S_CC), 64)                      # ... with idle lanes ...
         p.i("s_cbranch_scc0", "@passloaded")
         p.i("s_cmp_lg_u32", s(S_QTAIL4), s(S_QHEAD4))         # ... and items (then the queue holds nothing but the words this round has put back)
@@ -714,11 +675,17 @@ class Gen:
         p.i("s_bfm_b64", "exec", s(S_CC), 0)
         p.i("s_cmp_eq_u32", s(S_CC), 64)
         p.i("s_cselect_b64", "exec", -1, "exec")
+
+    def pass_window(self):
+        """the candidate's window from the ring.  Reads PS.m, PS.y, PS.tb, S_RQ; leaves its 2-bit codes in PS.hi:PS.lo (base 0 in the lowest bits) and the
+        LDS address of its strand's table in PS.tb"""
+        p = self.p
+        m, col, a0, lo, hi, tb, t1, fld, y = PS.m, PS.col, PS.a0, PS.lo, PS.hi, PS.tb, PS.t1, PS.fld, PS.y
         # the window's bytes: byte i lies in quarter-slot S_RQ[i], row m & 7, lane, byte m >> 3 (every byte is loaded into a register of its own,
         # zero-extended: a d16 load keeps or clears the other half of its register depending on the ECC mode of the part)
         nby = self.nby
         addr = fld[:nby]                                      # (address registers now, fields later)
-        byt = [a0, a1, a2, lo, hi, key, key1, fld[9], fld[10]][:nby]
+        byt = [a0, PS.a1, PS.a2, lo, hi, PS.key, PS.key1, fld[9], fld[10]][:nby]
         p.i("v_and_b32", v(col), 0xff, v(y))                  # 4 x lane
         p.i("v_lshl_or_b32", v(a0), v(m), 11, v(m))
         p.i("v_lshrrev_b32", v(a0), 3, v(a0))
@@ -753,6 +720,11 @@ class Gen:
                     p.i("v_lshrrev_b32", v(hi), v(t1), v(w1))
                 else:
                     p.i("v_alignbit_b32", v(hi), v(w2), v(w1), v(t1))  # bases 16 .. 31
+
+    def pass_key(self):
+        """table look-ups.  Reads PS.hi:PS.lo, PS.tb, PS.y; leaves the counter index in PS.key and in PS.sflag 0: a hit to log, bit 0: suspect, bit 1: no hit"""
+        p = self.p
+        lo, hi, mid, tb, key, fld, y = PS.lo, PS.hi, PS.mid, PS.tb, PS.key, PS.fld, PS.y
         # 3 bases per look-up: field g = bits [6 g, 6 g + 6) of hi:lo
         for g in range(self.ng):
             bit = 6 * g
@@ -783,13 +755,13 @@ class Gen:
         w = words[0]
         p.i("v_and_b32", v(key), s(S_RMASK2), v(w))          # low rBits bits + the sample bit right above them
         p.i("v_add_u32", v(key), s(S_KEYBASE), v(key))
-        sflag = a0                                            # (the ring words are spent) 0: a hit to log, bit 0: suspect, bit 1: no hit
+        sflag = PS.sflag                                      # (the ring words are spent)
         p.i("v_bfe_u32", v(sflag), v(y), 15, 1)
         if self.sb != 7:
             # s_bits >= 8: the walk only saw the 8-bit prefixes of ntComp's patterns; the table word carries the s_bits - 7 hash bits below them
             # (bits 55 .. 63 - s_bits, above the sample bit).  Sample 1 (0 1..1) needs all but the lowest of them set, sample 0 (0..0 1)
             # exactly the lowest; S_SPARE = 2^(s_bits - 7) - 1
-            smp, ext = a1, a2
+            smp, ext = PS.a1, PS.a2
             p.i("s_bcnt1_i32_b32", s(S_B), s(S_RMASK2))      # r_bits + 1
             p.i("v_lshrrev_b32", v(ext), s(S_B), v(w))
             p.i("s_sub_u32", s(S_B), s(S_B), 1)
@@ -803,7 +775,11 @@ class Gen:
             p.i("v_cmp_ne_u32_e32", "vcc", 0, v(smp))
             p.i("v_cndmask_b32_e64", v(mid), v(ext), v(mid), "vcc")     # 2 where the candidate's own pattern fails
             p.i("v_or_b32", v(sflag), v(sflag), v(mid))
-        # ---- clean hits: append to the hit log ----
+
+    def pass_log(self):
+        """clean hits (PS.sflag == 0): PS.key -> the hit log, or — no log — ntComp's increment as a device atomic.  Leaves vcc = the suspects"""
+        p = self.p
+        lo, key, key1, t1, fld, sflag = PS.lo, PS.key, PS.key1, PS.t1, PS.fld, PS.sflag
         nolog, logged = self.lbl("nolog"), self.lbl("logged")
         p.label("logswitch_back")
         if self.sb == 7:
@@ -813,13 +789,11 @@ class Gen:
             p.i("v_cmp_ne_u32_e32", "vcc", 0, v(t1))
         p.i("v_cmp_eq_u32_e64", sr(S_TMP, 2), 0, v(sflag))    # S_TMP = hits to log
         p.i("s_bcnt1_i32_b64", s(S_B), sr(S_TMP, 2))
-        p.i("s_bitcmp1_b32", s(S_USELOG), F_USELOG)
-        p.i("s_cbranch_scc0", "@" + nolog)
+        self.unless_flag(F_USELOG, nolog)
         p.i("s_lshl2_add_u32", s(S_A), s(S_B), s(S_LFILL4))
         p.i("s_cmp_le_u32", s(S_A), s(S_LOGCAP4))
         p.i("s_cbranch_scc0", "@logswitch")
-        p.i("v_mbcnt_lo_u32_b32", v(t1), s(S_TMP), 0)
-        p.i("v_mbcnt_hi_u32_b32", v(t1), s(S_TMP + 1), v(t1))
+        self.mbcnt(t1, s(S_TMP), s(S_TMP + 1))
         p.i("v_lshl_add_u32", v(t1), v(t1), 2, s(S_LFILL4))
         p.i("s_mov_b64", "exec", sr(S_TMP, 2))
         p.i("global_store_dword", v(t1), v(key), sr(S_LOGBASE, 2))
@@ -835,15 +809,18 @@ class Gen:
         # WRITES its counts instead of adding them (ntc_apply.hip, count_kernel) unless this word says otherwise.  Rare path: engines without a log
         # (their pointer is NULL) and waves that ran out of log regions.
         skipflag = self.lbl("skipflag")
-        p.i("s_load_dwordx2", sr(S_TMP, 2), sr(S_KARG, 2), hex(KARG["sk_dirty"]))
-        p.i("s_waitcnt", "lgkmcnt(0)")
+        self.karg_load(S_TMP, "sk_dirty", wait=True)
         p.i("s_cmp_eq_u64", sr(S_TMP, 2), 0)
         p.i("s_cbranch_scc1", "@" + skipflag)
         p.i("v_mov_b32", v(fld[2]), 0)
         p.i("global_store_dword", v(fld[2]), v(V_ONE), sr(S_TMP, 2))
         p.label(skipflag)
         p.label(logged)
-        # ---- suspects: (key, tile, read | window << 11) -> this wave's region of the suspect list ----
+
+    def pass_suspects(self):
+        """suspects (vcc): (key, tile, read | window << 11, marks) -> this wave's region of the suspect list; then the pass returns, exec = all lanes"""
+        p = self.p
+        m, key, t1, fld, sflag, y = PS.m, PS.key, PS.t1, PS.fld, PS.sflag, PS.y
         nosus, susfull = self.lbl("nosus"), self.lbl("susfull")
         p.i("s_cbranch_vccz", "@" + nosus)
         p.i("s_mov_b64", "exec", "vcc")
@@ -852,8 +829,7 @@ class Gen:
         p.i("s_add_u32", s(S_A), s(S_SUSOFF), s(S_B))
         p.i("s_cmp_le_u32", s(S_A), s(S_SUSCAP))
         p.i("s_cbranch_scc0", "@" + susfull)
-        p.i("v_mbcnt_lo_u32_b32", v(t1), "vcc_lo", 0)
-        p.i("v_mbcnt_hi_u32_b32", v(t1), "vcc_hi", v(t1))
+        self.mbcnt(t1, "vcc_lo", "vcc_hi")
         p.i("v_lshl_add_u32", v(t1), v(t1), 4, s(S_SUSOFF))
         sx = fld[1]                                           # four consecutive registers from an even one: the entry
         assert sx % 2 == 0
@@ -894,13 +870,16 @@ class Gen:
         p.i("s_mov_b64", "exec", -1)
         p.i("s_waitcnt", "lgkmcnt(0)")
         self.probe(2)
-        if "noprio" not in self.exp:
+        if not self.on("noprio"):
             p.i("s_setprio", 0)
         self.ret()
-        # ---- rare: the log region is full ----
+
+    def pass_logswitch(self):
+        """rare, out of line: the log region is full — this wave's next region, or device atomics from here on; back to pass_log with exec restored"""
+        p = self.p
         p.label("logswitch")
         p.i("s_mov_b64", "vcc", "exec")
-        self.store_log_fill(fld[1])
+        self.store_log_fill()
         p.i("s_add_u32", s(S_LREG), s(S_LREG), s(S_NWAVES))
         p.i("s_cmp_lt_u32", s(S_LREG), s(S_LOGREG))
         ok = self.lbl("lsw_ok")
@@ -913,16 +892,16 @@ class Gen:
         p.i("s_mov_b64", "exec", "vcc")
         p.i("s_branch", "@logswitch_back")
 
-    def store_log_fill(self, T=V_TP + 16):
-        """log_fill[LREG] = LFILL (one lane); T, T + 1: scratch"""
+    def store_log_fill(self):
+        """log_fill[LREG] = LFILL (one lane); scratch: PS.fld[1], PS.fld[2] (free wherever this is called: they hold look-up fields or nothing)"""
         p = self.p
+        T = PS.fld[1]
         p.i("s_mov_b64", "exec", 1)
         p.i("s_lshl_b32", s(S_B), s(S_LREG), 2)
         p.i("s_lshr_b32", s(S_CC), s(S_LFILL4), 2)
         p.i("v_mov_b32", v(T), s(S_B))
         p.i("v_mov_b32", v(T + 1), s(S_CC))
-        p.i("s_load_dwordx2", sr(S_TMP, 2), sr(S_KARG, 2), hex(KARG["log_fill"]))
-        p.i("s_waitcnt", "lgkmcnt(0)")
+        self.karg_load(S_TMP, "log_fill", wait=True)
         p.i("global_store_dword", v(T), v(T + 1), sr(S_TMP, 2))
         p.i("s_mov_b64", "exec", -1)
 
@@ -930,14 +909,12 @@ class Gen:
         """LFILL4 and the buffer descriptor of region LREG"""
         p = self.p
         p.i("s_lshl_b32", s(S_B), s(S_LREG), 2)
-        p.i("s_load_dwordx2", sr(S_TMP, 2), sr(S_KARG, 2), hex(KARG["log_fill"]))
-        p.i("s_load_dwordx2", sr(S_LOGBASE, 2), sr(S_KARG, 2), hex(KARG["log"]))
+        self.karg_load(S_TMP, "log_fill")
+        self.karg_load(S_LOGBASE, "log")
         p.i("s_waitcnt", "lgkmcnt(0)")
         p.i("s_load_dword", s(S_LFILL4), sr(S_TMP, 2), s(S_B))
-        p.i("s_mul_i32", s(S_TMP), s(S_LREG), s(S_LOGCAP4))
-        p.i("s_mul_hi_u32", s(S_TMP + 1), s(S_LREG), s(S_LOGCAP4))
-        p.i("s_add_u32", s(S_LOGBASE), s(S_LOGBASE), s(S_TMP))
-        p.i("s_addc_u32", s(S_LOGBASE + 1), s(S_LOGBASE + 1), s(S_TMP + 1))
+        self.mul64(S_TMP, S_TMP + 1, S_LREG, S_LOGCAP4)
+        self.add64(S_LOGBASE, S_LOGBASE, s(S_TMP), s(S_TMP + 1))
         p.i("s_waitcnt", "lgkmcnt(0)")
         p.i("s_lshl_b32", s(S_LFILL4), s(S_LFILL4), 2)
 
@@ -959,18 +936,42 @@ class Gen:
 
     def set_desc(self, t):
         """S_DESC = slots of tile t"""
-        p = self.p
-        p.i("s_mul_i32", s(S_TMP), s(t), s(S_CHUNKB))
-        p.i("s_mul_hi_u32", s(S_TMP + 1), s(t), s(S_CHUNKB))
-        p.i("s_add_u32", s(S_DESC), s(S_TILES), s(S_TMP))
-        p.i("s_addc_u32", s(S_DESC + 1), s(S_TILES + 1), s(S_TMP + 1))
+        self.mul64(S_TMP, S_TMP + 1, t, S_CHUNKB)
+        self.add64(S_DESC, S_TILES, s(S_TMP), s(S_TMP + 1))
 
-    # ---- the whole kernel body ------------------------------------------------------------------------------
+    # ---- the whole kernel body: build() strings the stages below together ----------------------------------------------
     def build(self, emu=False):
         p = self.p
-        k, phi = self.k, self.phi
-        # -- inputs -> fixed registers (operands %0 .. are the compiler's; the emulator finds them in s0 ..)
-        inp = {name: (s(i) if emu else f"%{i}") for i, name in enumerate(INPUTS)}
+        # inputs -> fixed registers (operands %0 .. are the compiler's; the emulator finds them in s0 ..)
+        self.inp = {name: (s(i) if emu else f"%{i}") for i, name in enumerate(INPUTS)}
+        self.prologue()
+        self.log_setup()
+        self.first_share()
+        p.label("iter")
+        self.chunk_loop()
+        self.end_of_block()
+        self.advance()
+        self.new_tile()
+        self.block_setup()
+        p.i("s_branch", "@iter")
+        for frag in self.cold:                                   # out-of-line: the rare sides of the loop's tests
+            frag()
+        self.cold = []
+        self.epilogue()
+        self.emit_pass()
+        self.emit_tail_step()
+        p.label("end")
+        if not self.on("nosched"):
+            schedule(p)
+        phase_fix(p, self.exp)
+        return p
+
+    def prologue(self):
+        """the asm statement's inputs and the kernel arguments -> S_KARG, S_WT (the wave's number, until the first block), S_NWAVES, the pointers S_TILES ..
+        S_SUS (this wave's region), the geometry S_NTILES .. S_LOGCAP4 (x 4), S_SUSCAP (bytes), S_CHUNKB, S_NB; S_USELOG = the ragged bit; S_DESC's constant
+        half; VCONST and the lane constants V_LANE4 .. V_EXP1; the ring's slots S_RQ and an empty queue; F1 = 0"""
+        p = self.p
+        inp, phi = self.inp, self.phi
         p.i("s_mov_b32", s(S_KARG), inp["karg_lo"])
         p.i("s_mov_b32", s(S_KARG + 1), inp["karg_hi"])
         p.i("s_mov_b32", s(S_WT), inp["wave_gid"])
@@ -979,26 +980,22 @@ class Gen:
         p.i("s_mov_b32", s(S_NWAVES), inp["n_waves"])
         p.i("s_mov_b32", s(S_RQ[0]), inp["lds_wbase"])
         for reg, name in ((S_TILES, "tiles"), (S_SK, "sketch0"), (S_DIRTY, "dirty"), (S_TIE, "tie"), (S_SUS, "sus")):
-            p.i("s_load_dwordx2", sr(reg, 2), sr(S_KARG, 2), hex(KARG[name]))
+            self.karg_load(reg, name)
         for reg, name in ((S_NTILES, "n_tiles"), (S_C, "n_chunks"), (S_L, "read_len"), (S_NVLAST, "nv_last"), (S_KEYBASE, "key_base"), (S_RMASK2, "rmask2"),
                           (S_LOGREG, "log_regions"), (S_LOGCAP4, "log_region_cap"), (S_SUSCAP, "sus_cap")):
-            p.i("s_load_dword", s(reg), sr(S_KARG, 2), hex(KARG[name]))
+            self.karg_load(reg, name, n=1)
         p.i("s_waitcnt", "lgkmcnt(0)")
-        p.i("s_load_dwordx2", sr(S_TMP, 2), sr(S_KARG, 2), hex(KARG["tails"]))
-        p.i("s_waitcnt", "lgkmcnt(0)")
+        self.karg_load(S_TMP, "tails", wait=True)
         p.i("s_cmp_lg_u64", sr(S_TMP, 2), 0)
         p.i("s_cselect_b32", s(S_USELOG), 1 << F_RAGGED, 0)   # (bit F_USELOG joins it below)
         p.i("s_lshl_b32", s(S_LOGCAP4), s(S_LOGCAP4), 2)
         p.i("s_lshl_b32", s(S_SUSCAP), s(S_SUSCAP), 4)         # bytes
-        p.i("s_mul_i32", s(S_A), s(S_WT), s(S_SUSCAP))
-        p.i("s_mul_hi_u32", s(S_B), s(S_WT), s(S_SUSCAP))
-        p.i("s_add_u32", s(S_SUS), s(S_SUS), s(S_A))
-        p.i("s_addc_u32", s(S_SUS + 1), s(S_SUS + 1), s(S_B))
+        self.mul64(S_A, S_B, S_WT, S_SUSCAP)
+        self.add64(S_SUS, S_SUS, s(S_A), s(S_B))
         p.i("s_mov_b32", s(S_SUSOFF), 0)
         p.i("s_mov_b32", s(S_EXP0), "0xff47ff54")         # validity look-up, codes 2 and 3: T, G
         if self.sb != 7:
-            p.i("s_load_dword", s(S_SPARE), sr(S_KARG, 2), hex(KARG["s_bits"]))
-            p.i("s_waitcnt", "lgkmcnt(0)")
+            self.karg_load(S_SPARE, "s_bits", n=1, wait=True)
             p.i("s_sub_u32", s(S_SPARE), s(S_SPARE), 7)
             p.i("s_bfm_b32", s(S_SPARE), s(S_SPARE), 0)       # 2^(s_bits - 7) - 1
         for reg, val in VCONST:
@@ -1007,8 +1004,7 @@ class Gen:
         p.i("s_mov_b32", s(S_DESC + 3), "0x00020000")
         p.i("s_lshl_b32", s(S_CHUNKB), s(S_C), 15)             # bytes of one tile
         # lane constants
-        p.i("v_mbcnt_lo_u32_b32", v(V_LANE4), -1, 0)
-        p.i("v_mbcnt_hi_u32_b32", v(V_LANE4), -1, v(V_LANE4))
+        self.mbcnt(V_LANE4, -1, -1)
         p.i("v_lshlrev_b32", v(V_LANE16), 4, v(V_LANE4))
         p.i("v_lshlrev_b32", v(V_LANE4), 2, v(V_LANE4))
         p.i("v_mov_b32", v(V_ONE), 1)
@@ -1021,13 +1017,16 @@ class Gen:
         p.i("s_mov_b32", s(S_QHEAD4), 0)
         p.i("s_mov_b32", s(S_QTAIL4), 0)
         p.i("s_mov_b64", sr(S_F1ACC, 2), 0)
-        if "timers" in self.exp:
+        if self.on("timers"):
             p.i("s_mov_b32", s(S_SPARE), 0)
         # geometry: W = L - k + 1, NB = ((L - 1 + 16 - phi) >> 4) + 1
         p.i("s_add_u32", s(S_NB), s(S_L), 15 - phi)
         p.i("s_lshr_b32", s(S_NB), s(S_NB), 4)
         p.i("s_add_u32", s(S_NB), s(S_NB), 1)
-        # hit log: this wave's first region
+
+    def log_setup(self):
+        """hit log: this wave's first region.  Reads S_WT (the wave's number), S_LOGREG; leaves S_LREG, S_LFILL4, S_LOGBASE and bit F_USELOG of S_USELOG"""
+        p = self.p
         p.i("s_cmp_lg_u32", s(S_LOGREG), 0)
         p.i("s_cselect_b32", s(S_A), 1, 0)
         p.i("s_mov_b32", s(S_LREG), s(S_WT))
@@ -1036,15 +1035,21 @@ class Gen:
         p.i("s_cselect_b32", s(S_A), s(S_A), 0)
         p.i("s_or_b32", s(S_USELOG), s(S_USELOG), s(S_A))
         nolog0 = self.lbl("nolog0")
-        p.i("s_bitcmp1_b32", s(S_USELOG), F_USELOG)
-        p.i("s_cbranch_scc0", "@" + nolog0)
+        self.unless_flag(F_USELOG, nolog0)
         self.load_log_region()
         p.label(nolog0)
+
+    def first_share(self):
+        """the wave's share of the blocks and its first loads.  Leaves S_F0, S_FEND (the blocks it owns), S_S0 (the first it walks), S_WF = S_S0 - 1, the
+        cursors P (chunk to pack: S_PT, S_PN, S_PREAL, S_PSOFF) and Q (to load next), S_DESC -> P's tile with P's first batch of loads in flight,
+        S_WN = -1 and an empty step mask (the first iteration is a dummy: it walks nothing and packs P), V_DN = V_TACC = V_CMASK = 0"""
+        p = self.p
+        inp = self.inp
         # This wave's share: the blocks of all tiles form one sequence (tile * NB + block); the wave owns [first_block, end_block) of it (the
         # kernel's prologue shares a workgroup's blocks out by where its waves sit: a wave alone on its SIMD gets through more than one of a pair)
         # — tiles are split wherever a boundary falls (19 tiles per CU over 6 waves are 4 rounds of whole tiles but 3.2 of blocks).
         # A wave that starts inside a tile first walks up to two blocks it does not own, masked: they fill the window (k - 1 <= 31 bases).
-        p.i("s_load_dword", s(S_B), sr(S_KARG, 2), hex(KARG["nb_magic"]))
+        self.karg_load(S_B, "nb_magic", n=1)
         p.i("s_mul_i32", s(S_CC), s(S_NTILES), s(S_NB))          # blocks of the batch
         p.i("s_mov_b32", s(S_F0), inp["first_block"])
         p.i("s_min_u32", s(S_FEND), inp["end_block"], s(S_CC))
@@ -1085,27 +1090,32 @@ class Gen:
         self.issue_batch(0, S_PSOFF)
         p.label(nofirst)
 
-        if "timers" in self.exp:
+        if self.on("timers"):
             p.i("s_memtime", sr(S_TMP, 2))
             p.i("s_waitcnt", "lgkmcnt(0)")
             p.i("s_mov_b32", s(S_SUSCAP), s(S_TMP))
             p.i("s_mov_b64", sr(S_F1ACC, 2), 0)
-        # ================================ the chunk loop ================================
-        p.label("iter")
+
+    def chunk_loop(self):
+        """the 16 steps of block W = (S_WT, S_WN): walk, test + push where S_STEPMASK says so, and between them the pack of chunk P into H0 (its loads
+        replaced by the next batch's, at last by chunk Q's first).  Reads the state planes, H0 / H1 / I, the block's masks; leaves candidates in the queue,
+        ties in V_TACC, P's packed words in H0 and its dirty bits in V_DN"""
+        p = self.p
         for a in range(16):
             if a % 4 == 0:
                 self.quarter_enter(a // 4)
             self.walk_step(a)
-            skip, notstep, dostep, tailp = self.lbl("nostep"), self.lbl("notstep"), self.lbl("dostep"), self.lbl("tailstep")
+            # ("tailstep" names nothing: the call is kept because it numbers the labels behind it, and the output is pinned)
+            skip, notstep, dostep, _reserved = self.lbl("nostep"), self.lbl("notstep"), self.lbl("dostep"), self.lbl("tailstep")
             p.i("s_bitcmp1_b32", s(S_STEPMASK), a)
             p.i("s_cbranch_scc0", "@" + notstep)
-            if "noflags" in self.exp:
+            if self.on("noflags"):
                 p.i("s_branch", "@" + skip)
             p.label(dostep)
             self.flags_and_push(a)
             p.label(skip)
 
-            def cold_tail(a=a, skip=skip, notstep=notstep, dostep=dostep, tailp=tailp):
+            def cold_tail(a=a, skip=skip, notstep=notstep, dostep=dostep):
                 # a step the mask leaves out (a filling block, the steps behind the read) — or, in a ragged batch, one that ends in the reads' last piece
                 p.label(notstep)
                 p.i("s_bitcmp1_b32", s(S_STEPMASK), 16 + a)
@@ -1130,7 +1140,11 @@ class Gen:
                 p.i("s_mov_b32", s(S_CC), s(S_QSOFF))
                 p.label(noq)
                 self.pack_batch(3)
-        # -- end of block: empty the queue (the next quarter_enter recycles the oldest quarter-slot of the ring)
+
+    def end_of_block(self):
+        """empties the queue (the next quarter_enter recycles the oldest quarter-slot of the ring); V_TACC -> tie[] and 0; V_DN -> dirty[]; the planes rotate:
+        (H0, H1, I) <- (H1, I, P's packed words as quarter-major bytes) and (V_D0, V_D1, V_D2, V_DN) <- (V_D1, V_D2, V_DN, 0)"""
+        p = self.p
         self.drain()
         self.probe(0)
         # -- tie bits of this block -> tie[(WT * NB + WN) * 64 + lane]
@@ -1139,8 +1153,8 @@ class Gen:
         p.i("s_cmp_gt_u32", s(S_A), s(S_F0))
         p.i("s_cbranch_scc0", "@" + notie)
         p.i("s_lshl_b32", s(S_A), s(S_WF), 8)
-        p.i("v_add_u32", v(V_T0), s(S_A), v(V_LANE4))
-        p.i("global_store_dword", v(V_T0), v(V_TACC), sr(S_TIE, 2))
+        p.i("v_add_u32", v(V_MISC), s(S_A), v(V_LANE4))
+        p.i("global_store_dword", v(V_MISC), v(V_TACC), sr(S_TIE, 2))
         p.label(notie)
         p.i("v_mov_b32", v(V_TACC), 0)
         # -- chunk P: dirty bits -> dirty[(PT * C + PN) * 64 + lane], packed words -> quarter-major bytes in I (ring and planes: quarter_enter)
@@ -1151,17 +1165,14 @@ class Gen:
         p.i("s_mul_i32", s(S_A), s(S_PT), s(S_C))
         p.i("s_add_u32", s(S_A), s(S_A), s(S_PN))
         p.i("s_lshl_b32", s(S_A), s(S_A), 8)
-        p.i("v_add_u32", v(V_T0), s(S_A), v(V_LANE4))
-        p.i("global_store_dword", v(V_T0), v(V_DN), sr(S_DIRTY, 2))
+        p.i("v_add_u32", v(V_MISC), s(S_A), v(V_LANE4))
+        p.i("global_store_dword", v(V_MISC), v(V_DN), sr(S_DIRTY, 2))
         # -- rotate: planes (H0, H1, I) <- (H1, I, new), dirty words
         self.perm_rotate()
         rotated = self.lbl("rotated")
         p.i("s_branch", "@" + rotated)
         p.label(nopk)                                           # no chunk P (behind a tile's last one): its planes are all 'A'
-        for i in range(32):
-            p.i("v_mov_b32", v(V_H0 + i), v(V_H1 + i))
-        for i in range(32):
-            p.i("v_mov_b32", v(V_H1 + i), v(V_I + i))
+        self.shift_planes()
         for i in range(32):
             p.i("v_mov_b32", v(V_I + i), 0)
         p.label(rotated)
@@ -1169,7 +1180,10 @@ class Gen:
         p.i("v_mov_b32", v(V_D1), v(V_D2))
         p.i("v_mov_b32", v(V_D2), v(V_DN))
         p.i("v_mov_b32", v(V_DN), 0)
-        # -- advance: W <- P, P <- Q, Q <- next(Q)
+
+    def advance(self):
+        """the cursors move on: W <- P, P <- Q, Q <- next(Q); the kernel ends (-> done) behind the wave's last block"""
+        p = self.p
         p.i("s_mov_b32", s(S_WT), s(S_PT))
         p.i("s_mov_b32", s(S_WN), s(S_PN))
         p.i("s_add_u32", s(S_WF), s(S_WF), 1)
@@ -1181,7 +1195,11 @@ class Gen:
         p.i("s_mov_b32", s(S_PSOFF), s(S_QSOFF))
         self.cursor_next(S_QT, S_QN, S_QREAL)
         p.i("s_lshl_b32", s(S_QSOFF), s(S_QN), 15)
-        # -- a new tile?
+
+    def new_tile(self):
+        """if W is block 0 of a tile (or the wave's first block, inside one): the state planes F, R start on the poly-A track, H0 / H1 / the carried pair and
+        V_D0 / V_D1 are cleared, V_VMASK = the tile's valid reads"""
+        p = self.p
         notile, newtile = self.lbl("notile"), self.lbl("newtile")
         p.i("s_cmp_eq_u32", s(S_WN), 0)
         p.i("s_cbranch_scc1", "@" + newtile)
@@ -1199,26 +1217,16 @@ class Gen:
         p.i("v_mov_b32", v(V_CARRY1), 0)
         p.i("v_mov_b32", v(V_D0), 0)
         p.i("v_mov_b32", v(V_D1), 0)
-        # valid reads of this tile: all 2048 but in a partial last tile
-        p.i("s_add_u32", s(S_A), s(S_WT), 1)
-        p.i("s_cmp_eq_u32", s(S_A), s(S_NTILES))
-        p.i("s_cselect_b32", s(S_A), s(S_NVLAST), 2048)
-        # VMASK bit m = (64 m + lane < valid): cnt = clamp((valid - lane + 63) >> 6, 0, 32) low bits set
-        T = V_T0
-        p.i("v_lshrrev_b32", v(T), 2, v(V_LANE4))
-        p.i("v_sub_u32", v(T), s(S_A), v(T))                    # valid - lane
-        p.i("v_add_u32", v(T), 63, v(T))
-        p.i("v_lshrrev_b32", v(T), 6, v(T))                     # (valid >= 1 and lane <= 63: never negative) groups m with 64 m + lane < valid
-        p.i("v_min_u32", v(T), 32, v(T))
-        p.i("v_cmp_gt_u32_e32", "vcc", 32, v(T))
-        p.i("v_lshlrev_b32", v(T + 1), v(T), v(V_ONE))
-        p.i("v_add_u32", v(T + 1), -1, v(T + 1))
-        p.i("v_cndmask_b32_e64", v(V_VMASK), -1, v(T + 1), "vcc")
+        self.valid_reads(S_A)
+        self.prefix_mask(V_VMASK, S_A, signed=False)
         p.label(notile)
-        # -- per block: candidates are dropped wherever one of the block's three chunks holds a dirty piece of the read
-        p.i("v_or3_b32", v(V_T0), v(V_D0), v(V_D1), v(V_D2))
-        self.bitop3(v(V_CMASK), v(V_T0), v(V_VMASK), v(V_VMASK), lambda x, y, z: (1 ^ x) & y)
-        p.i("v_and_b32", v(V_DMASK), v(V_T0), v(V_VMASK))
+
+    def block_setup(self):
+        """per block W: V_CMASK / V_DMASK; S_STEPMASK = the steps that complete a window (bits 16 .. 31: of a ragged batch's last piece, emit_tail_step);
+        F1 += the block's windows of every valid read"""
+        p = self.p
+        k, phi = self.k, self.phi
+        self.block_masks()
         # steps of this block that complete a window: e = 16 (n - 1) + phi + a in [k - 1, L - 1]
         p.i("s_lshl_b32", s(S_A), s(S_WN), 4)
         p.i("s_add_i32", s(S_A), s(S_A), phi - 16)              # e0
@@ -1236,11 +1244,10 @@ class Gen:
         p.i("s_cselect_b32", s(S_CC), s(S_CC), 0)
         # Ragged batch (round 5; ntRead takes any std::string, ntcard.cpp:173-189): the reads of a batch are 16 C - 15 .. 16 C bases long (read_len = 16 C) and
         # every tile's reads are sorted by length, longest first, so "the reads with a window ending at base 16 (C - 1) + d" are a PREFIX of the tile —
-        # tails[tile][d] of them.  The steps that end in the last piece (e >= 16 (C - 1)) leave the step mask for the tail mask: their code (tail_step,
+        # tails[tile][d] of them.  The steps that end in the last piece (e >= 16 (C - 1)) leave the step mask for the tail mask: their code (emit_tail_step,
         # out of line) narrows the candidate masks to that prefix and counts tails[tile][d] windows into F1 instead of one per read.
         noragged = self.lbl("noragged")
-        p.i("s_bitcmp1_b32", s(S_USELOG), F_RAGGED)
-        p.i("s_cbranch_scc0", "@" + noragged)
+        self.unless_flag(F_RAGGED, noragged)
         p.i("s_sub_u32", s(S_B), s(S_C), 1)
         p.i("s_lshl_b32", s(S_B), s(S_B), 4)
         p.i("s_sub_i32", s(S_B), s(S_B), s(S_A))                 # first step that ends in the last piece (e0 + a >= 16 (C - 1))
@@ -1254,29 +1261,22 @@ class Gen:
         p.i("s_or_b32", s(S_STEPMASK), s(S_STEPMASK), s(S_A))
         p.label(noragged)
         # F1 (ntcard.cpp:154): every window of every valid read counts here (K1f takes the invalid ones back)
-        p.i("s_add_u32", s(S_A), s(S_WT), 1)
-        p.i("s_cmp_eq_u32", s(S_A), s(S_NTILES))
-        p.i("s_cselect_b32", s(S_A), s(S_NVLAST), 2048)
+        self.valid_reads(S_A)
         p.i("s_mul_i32", s(S_B), s(S_A), s(S_CC))
-        if "timers" not in self.exp:
-            p.i("s_add_u32", s(S_F1ACC), s(S_F1ACC), s(S_B))
-            p.i("s_addc_u32", s(S_F1ACC + 1), s(S_F1ACC + 1), 0)
+        self.f1_add(S_B)
         self.probe(3)
-        p.i("s_branch", "@iter")
-        for frag in self.cold:                                   # out-of-line: the rare sides of the loop's tests
-            frag()
-        self.cold = []
 
-        # ================================ epilogue ================================
+    def epilogue(self):
+        """done: F1 (ntcard.cpp:154) and this wave's number of suspects leave by one lane (the timing build: its four section clocks); the log region's fill
+        goes to log_fill; every store is waited for"""
+        p = self.p
         p.label("done")
-        # F1 (ntcard.cpp:154)
-        T = V_T0
-        p.i("s_load_dwordx2", sr(S_TMP, 2), sr(S_KARG, 2), hex(KARG["f1"]))
-        p.i("s_waitcnt", "lgkmcnt(0)")
+        T = V_MISC
+        self.karg_load(S_TMP, "f1", wait=True)
         p.i("s_mov_b64", "exec", 1)
         p.i("v_mov_b32", v(T + 2), s(S_TMP))
         p.i("v_mov_b32", v(T + 3), s(S_TMP + 1))
-        if "timers" in self.exp:
+        if self.on("timers"):
             p.i("v_mov_b32", v(T + 1), 0)
             for sec in range(4):
                 p.i("v_mov_b32", v(T), s(S_TACC[sec]))
@@ -1286,7 +1286,7 @@ class Gen:
             p.i("v_mov_b32", v(T + 1), s(S_F1ACC + 1))
             p.i("global_atomic_add_x2", vr(T + 2, 2), vr(T, 2), "off")
             # suspects of this wave: their number (or all ones: the region overflowed, K1f falls back to walking every dirty block)
-            p.i("s_load_dwordx2", sr(S_TMP, 2), sr(S_KARG, 2), hex(KARG["sus_count"]))
+            self.karg_load(S_TMP, "sus_count")
             p.i("s_lshr_b32", s(S_A), s(S_SUSOFF), 4)
             p.i("s_cmp_le_u32", s(S_SUSOFF), s(S_SUSCAP))
             p.i("s_cselect_b32", s(S_A), s(S_A), -1)
@@ -1295,95 +1295,12 @@ class Gen:
             p.i("global_store_dword", v(V_WAVE4), v(T), sr(S_TMP, 2))
         p.i("s_mov_b64", "exec", -1)
         nofill = self.lbl("nofill")
-        p.i("s_bitcmp1_b32", s(S_USELOG), F_USELOG)
-        p.i("s_cbranch_scc0", "@" + nofill)
+        self.unless_flag(F_USELOG, nofill)
         self.store_log_fill()
         p.label(nofill)
         p.label("exit")
         p.i("s_waitcnt", "vmcnt(0) lgkmcnt(0)")
         p.i("s_branch", "@end")
-        self.emit_pass()
-        self.emit_tail_step()
-        p.label("end")
-        if "nosched" not in self.exp:
-            schedule(p)
-        self.phase_fix(p)
-        return p
-
-    # VALU instructions that a second wave on the SIMD overlaps with completely (profiles/r05_ubench_op_classes.txt): every other VALU
-    # instruction — and any of these with an SGPR source — occupies the pipe for a whole issue interval
-    FAST_VALU = {"v_bitop3_b32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_not_b32", "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_lshrrev_b32", "v_ashrrev_i32",
-                 "v_mov_b32"}
-
-    @classmethod
-    def is_slow_valu(cls, mnem, ops):
-        if not mnem.startswith("v_"):
-            return False
-        if mnem not in cls.FAST_VALU:
-            return True
-        return any(o.startswith("s") or o.startswith("vcc") or o.startswith("exec") for o in ops[1:])
-
-    def phase_fix(self, p):
-        """K1H_EXP=nopslow | noprun | priorun | priowalk (results stay RIGHT; with priorun / priowalk add noprio, which takes the pass's own s_setprio out): scalar no-ops / priority changes next to the slow-class VALU
-        instructions.  profiles/r05_ubench_sparse_slow.txt, r05_ubench_phase_fix.txt: one slow-class instruction drops a pair of waves into a
-        persistent phase in which they do not overlap any more, and a scalar instruction next to it brings the overlap back."""
-        if "priowalk" in self.exp:
-            out, code = [], p.code
-            i, n = 0, len(code)
-            while i < n:
-                c = code[i]
-                if c[0] == "i" and c[1].startswith("v_") and not self.is_slow_valu(c[1], c[2]):
-                    j = i
-                    while j < n and code[j][0] == "i" and code[j][1].startswith("v_") and not self.is_slow_valu(code[j][1], code[j][2]):
-                        j += 1
-                    if j - i >= 12:
-                        out.append(("i", "s_setprio", ["3"], ""))
-                        out.extend(code[i:j])
-                        out.append(("i", "s_setprio", ["0"], ""))
-                    else:
-                        out.extend(code[i:j])
-                    i = j
-                    continue
-                out.append(c)
-                i += 1
-            p.code = out
-            return
-        mode = [m for m in ("nopslow", "noprun", "priorun") if m in self.exp]
-        if not mode:
-            return
-        mode = mode[0]
-        out = []
-        pending = False   # a slow-class VALU instruction has been issued and neither a scalar instruction nor a fix since
-        for c in p.code:
-            if c[0] != "i":
-                out.append(c)
-                if c[0] == "l":
-                    pending = False if mode != "priorun" else pending
-                continue
-            mnem, ops = c[1], c[2]
-            if mnem.startswith("v_"):
-                slow = self.is_slow_valu(mnem, ops)
-                if slow:
-                    if mode == "priorun" and not pending:
-                        out.append(("i", "s_setprio", ["3"], ""))
-                    out.append(c)
-                    if mode == "nopslow":
-                        out.append(("i", "s_nop", ["0"], ""))
-                    else:
-                        pending = True
-                    continue
-                if pending:
-                    out.append(("i", "s_nop", ["0"], "") if mode == "noprun" else ("i", "s_setprio", ["0"], ""))
-                    pending = False
-                out.append(c)
-                continue
-            if mnem.startswith("s_") and mode != "priorun":
-                pending = False   # a scalar instruction does what the no-op would
-            if mode == "priorun" and pending and (mnem.startswith("s_cbranch") or mnem in ("s_branch", "s_setpc_b64", "s_endpgm")):
-                out.append(("i", "s_setprio", ["0"], ""))
-                pending = False
-            out.append(c)
-        p.code = out
 
 
 def render_inc(k, sb, gap=0):
@@ -1402,6 +1319,10 @@ PARTS = 4                      # the kernels are spread over this many objects (
 
 
 if __name__ == "__main__":
+    try:
+        parse_exp()
+    except ValueError as e:
+        sys.exit(str(e))
     out = sys.argv[1] if len(sys.argv) > 1 else "ntc_k1h_gen.inc"
     defs = out.replace(".inc", "_defs.inc")
     with open(defs, "w") as f:
@@ -1410,6 +1331,8 @@ if __name__ == "__main__":
         f.write("#define K1H_VARIANTS_ALL(X) " + " ".join(f"X({k}, {g})" for k, g in VARIANTS) + "\n")
         for part in range(PARTS):
             f.write(f"#define K1H_VARIANTS_P{part}(X) " + " ".join(f"X({k}, {g})" for k, g in VARIANTS if k % PARTS == part) + "\n")
+        # the byte offsets the generated code reads its arguments at (k1h_regs.KARG): ntc_sketch_k1h_body.hip checks each against struct K1hArgs
+        f.write("#define K1H_GEN_KARGS(X) " + " ".join(f"X({name}, {off})" for name, off in KARG.items()) + "\n")
     with open(out, "w") as f:
         f.write("// ntc_k1h_gen.inc — GENERATED by gen_k1h.py (do not edit): one assembly string per (k, gap, sBits class)\n")
         for k, gap in VARIANTS:

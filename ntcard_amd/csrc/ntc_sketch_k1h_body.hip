@@ -18,13 +18,10 @@ namespace {
 #include "ntc_k1h_gen_defs.inc"
 #include "ntc_k1h_gen.inc" // (only the strings of this part: #if K1H_PART == ...)
 
-static_assert(offsetof(K1hArgs, tiles) == 0 && offsetof(K1hArgs, log) == 8 && offsetof(K1hArgs, log_fill) == 16 && offsetof(K1hArgs, sketch0) == 24 &&
-                  offsetof(K1hArgs, f1) == 32 && offsetof(K1hArgs, dirty) == 40 && offsetof(K1hArgs, tie) == 48 && offsetof(K1hArgs, n_tiles) == 56 &&
-                  offsetof(K1hArgs, n_chunks) == 60 && offsetof(K1hArgs, read_len) == 64 && offsetof(K1hArgs, nv_last) == 68 && offsetof(K1hArgs, key_base) == 72 &&
-                  offsetof(K1hArgs, rmask2) == 76 && offsetof(K1hArgs, log_regions) == 80 && offsetof(K1hArgs, log_region_cap) == 84 && offsetof(K1hArgs, table) == 88 &&
-                  offsetof(K1hArgs, blocks_per_wave) == 104 && offsetof(K1hArgs, nb_magic) == 108 && offsetof(K1hArgs, sus) == 112 &&
-                  offsetof(K1hArgs, sus_count) == 120 && offsetof(K1hArgs, sus_cap) == 128 && offsetof(K1hArgs, tails) == 144 && offsetof(K1hArgs, sk_dirty) == 160,
-              "gen_k1h.KARG");
+// every offset the generated code reads its arguments at (k1h_regs.KARG, written into the defs file as K1H_GEN_KARGS) is the field's
+#define K1H_KARG_CHECK(name, off) static_assert(offsetof(K1hArgs, name) == off, "K1hArgs." #name " is not where k1h_regs.KARG has it");
+K1H_GEN_KARGS(K1H_KARG_CHECK)
+#undef K1H_KARG_CHECK
 constexpr uint32_t kK1hWaves = K1H_GEN_WAVES;
 constexpr uint32_t kK1hWArea = K1H_GEN_WAREA;
 static_assert(kK1hWaves == 8, "the launch (512 threads: two waves on every SIMD) assumes eight waves per workgroup");

@@ -66,7 +66,7 @@ def run_ragged(n, C, k, p_bad=0.0, r_bits=14, n_waves=2, seed=1, s_bits=7, gap=0
                                                  (2500, 2, 12, 0.02, 2), (4100, 5, 17, 0.0, 4), (2048, 3, 31, 0.02, 1), (2048, 2, 20, 0.01, 2), (2300, 1, 12, 0.0, 2)])
 def test_k1h_emulated_ragged_batches(n, C, k, p_bad, n_waves):
     """reads of unequal length (ntRead takes any string, ntcard.cpp:173-189): a batch of reads 16 C - 15 .. 16 C bases long, tiles sorted longest first,
-    the steps that end in the last piece masked to the prefix of the tile that is long enough (gen_k1h.Gen.tail_step)"""
+    the steps that end in the last piece masked to the prefix of the tile that is long enough (gen_k1h.Gen.emit_tail_step)"""
     run_ragged(n, C, k, p_bad, n_waves=n_waves, seed=n + C)
 
 
@@ -129,7 +129,16 @@ def test_k1h_generator_budgets():
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ntcard_amd", "csrc"))
     import gen_k1h
+    import k1h_exp
     assert gen_k1h.S_END <= 100 and gen_k1h.V_CQMASK4 <= 254
+    gen_k1h.check_register_map()  # no two VGPR ranges share a register unless the map declares the pair
+    ranges = dict(gen_k1h.V_RANGES, **{"pack": (gen_k1h.V_CMUL - 17, 18, "moved onto VCONST")})
+    with pytest.raises(AssertionError, match="pack .* and vconst .* overlap and are not declared"):
+        gen_k1h.check_register_map(ranges)
+    with pytest.raises(ValueError, match="unknown switch notaswitch; the switches are timers, noload"):
+        k1h_exp.parse_exp("noload,notaswitch")
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools", "README.md"), encoding="utf-8") as f:
+        assert k1h_exp.readme_sentence() in f.read()  # the switches are spelt in one table, and the tools' README agrees with it
     for k, gap in gen_k1h.VARIANTS:
         assert gen_k1h.TABLE_OFF + gen_k1h.table_bytes(k) <= gen_k1h.LDS_BYTES
         for sb in (7, 8):

@@ -52,7 +52,7 @@ def main():
     pack = sum((part(g2, lambda b=b: g2.pack_batch(b)) for b in range(4)), collections.Counter())
     rows.append(("pack, 4 batches of 8 read groups (both branches: real chunk / chunk that does not exist)", pack))
     g3 = gen_k1h.Gen(k, sb, gap)
-    rows.append(("transpose + plane rotation", part(g3, g3.transpose_rotate)))
+    rows.append(("transpose + plane rotation", part(g3, lambda: (g3.perm_rotate(), [g3.transpose_quarter(q) for q in range(4)]))))
     g4 = gen_k1h.Gen(k, sb, gap)
     rows.append(("one resolve pass (subroutine; log switch and suspect store included: rarely run)", part(g4, g4.emit_pass)))
     full = gen_k1h.Gen(k, sb, gap).build()

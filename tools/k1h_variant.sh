@@ -1,6 +1,6 @@
 #!/bin/bash
-# tools/k1h_variant.sh <name> <K1H_EXP list> — timing-experiment build of K1h (gen_k1h.py: K1H_EXP=noload,nopass,... — results are WRONG,
-# only the clock is of interest; `timers` keeps the results and adds section clocks) linked against the in-tree objects into
+# tools/k1h_variant.sh <name> <K1H_EXP list> — timing-experiment build of K1h (gen_k1h.py: K1H_EXP=noload,nopass,... — the switches and what each
+# does to the results: k1h_exp.py, which rejects a name it does not know; `timers` adds section clocks) linked against the in-tree objects into
 # tools/lib_k1h_<name>.so (bench.py --lib ...).  K1H_CXXFLAGS adds compiler flags (-DK1H_STATIC_PRIO=1).
 set -e
 NAME=$1; EXP=$2
