@@ -160,7 +160,8 @@ int ntc_submit_spans(ntc_engine *e, const char *buf, const uint64_t *starts, con
  * Asynchronous on the engine's stream: the buffer may be reused as soon as the stream has passed the call (stream-ordered,
  * like a kernel launch) — unless the engine was created with NTC_FLAG_DEFER_REDO, see there.
  * A wave parks its 64 slots in LDS, so stride is limited to about 2.4 KB (64 * stride + tables <= 160 KiB);
- * longer sequences go through ntc_submit, which splits them into overlapping chunks.            */
+ * longer sequences go through ntc_submit, which splits them into overlapping chunks, or — device-resident — through
+ * ntc_submit_long_device.                                                                       */
 int ntc_submit_device(ntc_engine *e, const void *d_slots, uint64_t n_reads, uint32_t read_len,
                       uint32_t stride);
 
@@ -202,6 +203,37 @@ int ntc_submit_tiled_ragged_device(ntc_engine *e, const void *d_tiles, uint64_t 
  * small launches (four 2.5 M-read bins: 0.55 ms one by one, 0.39 ms together).  Empty bins are skipped.  NTC_ERR_ARG as for the single calls.    */
 int ntc_submit_tiled_bins_device(ntc_engine *e, uint32_t n_bins, const void *const *d_tiles, const uint64_t *n_reads, const uint32_t *read_len,
                                  const uint32_t *const *d_tails);
+
+/* LONG sequences that are already DEVICE-resident — a chromosome or contig, HiFi / ONT reads, an assembler's or a decompressor's output: what the reference's
+ * FASTA / SAM parsers hand to ntRead one sequence at a time (ntcard.cpp:147-158,173-208) — additive to ABI 6.  d_bases is device memory holding the
+ * concatenated raw bytes (any byte: N, IUPAC, lower case; any alignment), sequence i = d_bases[offsets[i], offsets[i + 1]), offsets a HOST array of
+ * n_seqs + 1 non-decreasing entries.  Stream-ordered: d_bases may be reused as soon as the stream has passed the call, under NTC_FLAG_DEFER_REDO too (the
+ * engine counts from scratch of its own, so this call never defers); offsets is free on return.  The kernels read d_bases in aligned 4-byte words, and only
+ * words that hold at least one byte of a sequence.
+ * On an engine with ONE plane that is the tiled kernels' (plain k = 12 .. 32 or the two tiled -g seeds, canonical, sBits >= 7) every sequence of n >= piece_len
+ * bytes is cut on the device into ntc_long_plan()'s full pieces [j S, j S + piece_len), S = piece_len - (k - 1) — an equal-length tiled batch, counted by
+ * K1h + K1f at their rate, each window of k bases in exactly one piece — and its remainder, like every shorter sequence, is gathered into row slots for the
+ * general kernel.  piece_len: 0 = the engine's choice (1008), or a multiple of 16 with k + 15 <= piece_len <= 65520.  The work goes in rounds of at most
+ * 1 GiB of engine scratch, whatever the input's size; the tables cost 8 B per piece.
+ * On every other engine (k lists, k > 32, other seeds, a strand, nthll, sBits < 7, NTC_FLAG_LANE_KERNEL, NTC_FLAG_SIMPLE_KERNEL) every sequence is gathered
+ * whole: exactly ntc_submit's results — with NTC_FLAG_REQUIRE_TILED the call fails with NTC_ERR_ARG instead and counts nothing.
+ * NTC_ERR_ARG for null pointers, a bad piece_len or offsets that decrease, checked before a device is looked for.
+ * ntc_submit / ntc_submit_spans take the same path for the long sequences of a host batch on such an engine: the sequences of two or more full pieces
+ * (piece_len 1008) are copied raw into staging and cut on the device once together they hold 32768 full pieces (about 32 MB; below that row slots are as fast
+ * or faster, profiles/long_seq.txt); the environment variable NTC_LONG_MIN, read per call, sets another number (0: never).  Same counts either way. */
+int ntc_submit_long_device(ntc_engine *e, const void *d_bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t piece_len);
+
+/* The cut ntc_submit_long_device makes of ONE sequence of len bytes (a pure host function; ntRead's window loop, ntcard.cpp:147-158,173-208, split
+ * into ranges): *pieces = m full pieces [j S, j S + piece_len), j < m, S = piece_len - (k - 1); *rem_start = m S: the remainder [m S, len) — the whole
+ * sequence when len < piece_len (m = 0), else k - 1 .. piece_len - 1 bytes — holds a window iff len - m S >= k.  The windows of the pieces and of the
+ * remainder are the sequence's windows, each once.  NTC_ERR_ARG unless piece_len is a multiple of 16 with k + 15 <= piece_len <= 65520. */
+int ntc_long_plan(uint32_t k, uint32_t piece_len, uint64_t len, uint64_t *pieces, uint64_t *rem_start);
+
+/* cumulative since create / reset: the full pieces ntc_submit_long_device (and the host path behind NTC_LONG_MIN) has cut for the tiled kernels and the
+ * sequences that contributed one (ntcard.cpp:147-158,173-208: the ntRead calls that went that way) — a diagnostic, like ntc_merge_allocations */
+int ntc_long_stats(ntc_engine *e, uint64_t *pieces, uint64_t *sequences);
+/* milliseconds of the cut and of the gather kernels while profiling (ntc_set_profiling), outside ntc_kernel_time's spans; either pointer may be NULL */
+int ntc_long_time(ntc_engine *e, double *cut_ms, double *gather_ms);
 
 int ntc_sync(ntc_engine *e); /* wait for all submitted work */
 

@@ -19,6 +19,7 @@ ABI_SYMBOLS = [
     "ntc_narrow_u16_device", "ntc_sum_slices_u16_device", "ntc_value_hist_u16_device",
     "ntc_log_export_device", "ntc_log_replace_device",
     "ntc_create_seeded", "ntc_hash_dump_seed_device", "ntc_hash_dump_strand_device",
+    "ntc_submit_long_device", "ntc_long_plan", "ntc_long_stats", "ntc_long_time",
 ]
 
 
@@ -80,6 +81,10 @@ def lib():
     L.ntc_tiled_bytes.argtypes = [u64, u32]
     L.ntc_tiled_bytes.restype = u64
     L.ntc_gen_reads_tiled_device.argtypes = [i32, p, p, u64, u64, u64, u32, u32, u64]
+    L.ntc_submit_long_device.argtypes = [p, p, p, u64, u32]
+    L.ntc_long_plan.argtypes = [u32, u32, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.ntc_long_stats.argtypes = [p, C.POINTER(u64), C.POINTER(u64)]
+    L.ntc_long_time.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ntc_sync.argtypes = [p]
     L.ntc_finish.argtypes = [p, p, p, p]
     L.ntc_merge_counters.argtypes = [p, p, p]

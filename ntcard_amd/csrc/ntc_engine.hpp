@@ -232,6 +232,12 @@ struct ntc_engine {
 	bool defer_redo = false;        // NTC_FLAG_DEFER_REDO
 	uint32_t strand = 0;            // 0 canonical; 1 NTC_FLAG_STRAND_FORWARD, 2 NTC_FLAG_STRAND_REVERSE: every batch is K1's one-strand form (no k is K1h's)
 	DevBuf<unsigned char> d_untile; // row-major scratch for tiled batches of configurations K1h is not built for
+	// ntc_submit_long_device (ntc_submit.hip): the scratch of one round — the tiles its pieces are cut into, or its row slots and their slot table — grown like
+	// d_untile; what ntc_long_stats and ntc_long_time report
+	DevBuf<unsigned char> d_long;
+	uint64_t long_pieces = 0, long_seqs = 0;
+	std::vector<ntc_eng::Span> long_cut_events, long_gather_events; // (filled while profiling, like `pending`)
+	double long_cut_ms = 0.0, long_gather_ms = 0.0;
 	DevBuf<uint32_t> d_tmeta;       // K1's slot table (len | len << 16 per read) of a RAGGED tiled batch under a list of which a part is K1's
 	uint32_t hll_bits = 0;          // != 0: nthll engine (d_sketch holds uint32 M[1<<hll_bits])
 	DevBuf<uint32_t> d_hll_thr;

@@ -154,6 +154,17 @@ hipError_t launch_gen_tiled(unsigned char* out, uint64_t seed, uint64_t first, u
 hipError_t launch_untile(const unsigned char* tiles, unsigned char* slots, uint64_t n_reads, uint32_t read_len, uint32_t stride, hipStream_t st);
 // a ragged tiled batch for K1 (round 6): meta[i] = len | len << 16 of read i from tails[tile][16] (the reads of a tile are sorted longest first)
 hipError_t launch_tails_to_meta(const uint32_t* tails, uint64_t n_reads, uint32_t n_chunks, uint32_t* meta, hipStream_t st);
+// ---- long sequences (ntc_long.hip; ntc_submit_long_device) ----
+// pieces -> tiles: piece p = the piece_len (= 16 x chunks) source bytes from src + piece_off[p], of any alignment, becomes "read p" of an equal-length tiled
+// batch (ntc_tiled_bytes(n_pieces, piece_len) bytes at `tiles`; the slots behind the last piece stay unwritten)
+hipError_t launch_cut_tiles(const unsigned char* src, const uint64_t* piece_off, uint64_t n_pieces, uint32_t piece_len, unsigned char* tiles, hipStream_t st);
+// spans -> row slots: slot i = `bytes` source bytes from src + spans[i].src, then 'A' up to the stride (a multiple of 4; slots 4-byte aligned);
+// meta[i] = bytes | limit << 16 (HashArgs::meta)
+struct LongSpan {
+	uint64_t src;
+	uint32_t bytes, limit;
+};
+hipError_t launch_gather_slots(const unsigned char* src, const LongSpan* spans, uint64_t n_slots, uint32_t stride, unsigned char* slots, uint32_t* meta, hipStream_t st);
 
 // ---- deferred sketch update (ntc_apply.hip) ----
 // A1/A2: radix partition of key runs.  Input run `seg` = in[seg * in_cap, +min(in_cnt[seg], in_cap)).

@@ -317,6 +317,8 @@ int ntc_reset(ntc_engine* e)
 	e->apply_ms = 0.0;
 	e->applies = 0;
 	e->k1f_ms = 0.0;
+	e->long_cut_ms = e->long_gather_ms = 0.0;
+	e->long_pieces = e->long_seqs = 0;
 	return 0;
 }
 
@@ -421,6 +423,21 @@ int ntc_merge_allocations(ntc_engine* e, uint64_t* n)
 	std::lock_guard<std::mutex> lk(e->mu);
 	*n = e->merge_allocs;
 	return 0;
+}
+
+int ntc_long_stats(ntc_engine* e, uint64_t* pieces, uint64_t* sequences)
+{
+	if (!e || !pieces || !sequences) return fail(NTC_ERR_ARG, "ntc_long_stats: null argument");
+	std::lock_guard<std::mutex> lk(e->mu);
+	*pieces = e->long_pieces;
+	*sequences = e->long_seqs;
+	return 0;
+}
+
+int ntc_long_time(ntc_engine* e, double* cut_ms, double* gather_ms)
+{
+	if (int rc = timing(e, "ntc_long_time", &ntc_engine::long_cut_ms, cut_ms, &ntc_engine::applies, nullptr)) return rc;
+	return timing(e, "ntc_long_time", &ntc_engine::long_gather_ms, gather_ms, &ntc_engine::applies, nullptr);
 }
 
 int ntc_update_mode(ntc_engine* e, uint32_t* mode_out)

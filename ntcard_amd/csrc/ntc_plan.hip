@@ -201,3 +201,16 @@ bool plan_log(ntc_engine* e, uint64_t want_entries)
 }
 
 } // namespace ntc_eng
+
+extern "C" int ntc_long_plan(uint32_t k, uint32_t piece_len, uint64_t len, uint64_t* pieces, uint64_t* rem_start)
+{
+	using ntc_eng::fail;
+	if (!pieces || !rem_start) return fail(NTC_ERR_ARG, "ntc_long_plan: null argument");
+	if (k < 1 || k > 65520u - 15u || (piece_len & 15u) || piece_len > 65520u || piece_len < k + 15u)
+		return fail(NTC_ERR_ARG, "ntc_long_plan: piece_len %u: need a multiple of 16 with k + 15 = %u <= piece_len <= 65520", piece_len, k + 15u);
+	const uint64_t step = piece_len - (k - 1u); // window starts per piece: every window of k bases lies in exactly one piece or in the remainder
+	const uint64_t m = len >= piece_len ? (len - piece_len) / step + 1u : 0u;
+	*pieces = m;
+	*rem_start = m * step;
+	return 0;
+}

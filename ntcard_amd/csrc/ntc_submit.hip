@@ -1,5 +1,6 @@
 // ntc_submit.hip — the ntc_submit* entry points: device-resident batches as they come; host reads packed into a staging pair (tiles for the
-// tiled kernels, length bins for ragged sets, row slots for the rest) and copied behind the engine's stream (ntc_engine.hpp)
+// tiled kernels, length bins for ragged sets, row slots for the rest) and copied behind the engine's stream; long sequences cut into pieces on the
+// device (ntc_submit_long_device; ntc_engine.hpp)
 #include "ntc_engine.hpp"
 
 using namespace ntc_eng;
@@ -124,89 +125,266 @@ template <class LenFn, class PtrFn> int submit_tiled_host(ntc_engine* e, const H
 	return end_stage_use(e, sl, run_tiled_segs(e, segs.data(), n_bins, 1, true)); // (the staging pair is recycled: its K1f may not be deferred)
 }
 
-// reads -> row slots (one slot per read, long sequences in overlapping chunks) -> K1
-template <class LenFn, class PtrFn> int submit_rows(ntc_engine* e, uint64_t n_reads, const LenFn& len_of, const PtrFn& ptr_of)
+// ---- row slots: the plan that ntc_submit's host packing and ntc_submit_long_device's gather both follow ----
+// one slot per read, or — once a read is longer than cap_chunk — chunks of cap_chunk bytes that overlap by kmax - 1
+struct RowPlan {
+	uint32_t kmin = 0, kmax = 0, cap_chunk = 0, stride = 0;
+	uint32_t ch = 0; // window starts per chunk
+	uint64_t maxlen = 0, len0 = 0, n_slots = 0;
+	bool uniform = true, chunked = false;
+	std::vector<uint32_t> order; // not empty: the reads longest first
+};
+
+// false: no read can produce a k-mer (ntHashIterator.hpp:61-64)
+template <class LenFn> bool plan_rows(const ntc_engine* e, uint64_t n_reads, const LenFn& len_of, RowPlan& p)
 {
-	const uint32_t kmax = *std::max_element(e->klist.begin(), e->klist.end());
-	const uint32_t kmin = *std::min_element(e->klist.begin(), e->klist.end());
-	// ---- plan: one slot per read, or chunks with kmax-1 overlap for long sequences ----
-	uint64_t maxlen = 0;
-	bool uniform = true;
-	const uint64_t len0 = len_of(0);
+	p.kmax = *std::max_element(e->klist.begin(), e->klist.end());
+	p.kmin = *std::min_element(e->klist.begin(), e->klist.end());
+	p.len0 = len_of(0);
 	for (uint64_t i = 0; i < n_reads; ++i) {
 		const uint64_t l = len_of(i);
-		maxlen = std::max(maxlen, l);
-		uniform &= (l == len0);
+		p.maxlen = std::max(p.maxlen, l);
+		p.uniform &= (l == p.len0);
 	}
-	if (maxlen < kmin) return 0; // nothing can produce a k-mer (ntHashIterator.hpp:61-64)
-	const uint32_t cap_chunk = std::max<uint32_t>(kSlotCapMin, ((2 * kmax + 64) + 3) & ~3u);
-	const bool chunked = maxlen > cap_chunk;
-	const uint32_t stride = pick_stride(chunked ? cap_chunk : maxlen, e->klist, e->max_seed_lds);
-	const uint32_t ch = cap_chunk - (kmax - 1); // window starts per chunk
-	uint64_t n_slots = 0;
-	if (!chunked) {
-		n_slots = n_reads;
+	if (p.maxlen < p.kmin) return false;
+	p.cap_chunk = std::max<uint32_t>(kSlotCapMin, ((2 * p.kmax + 64) + 3) & ~3u);
+	p.chunked = p.maxlen > p.cap_chunk;
+	p.stride = pick_stride(p.chunked ? p.cap_chunk : p.maxlen, e->klist, e->max_seed_lds);
+	p.ch = p.cap_chunk - (p.kmax - 1);
+	if (!p.chunked) {
+		p.n_slots = n_reads;
 	} else {
 		for (uint64_t i = 0; i < n_reads; ++i) {
 			const uint64_t l = len_of(i);
-			if (l < kmin) continue;
-			n_slots += l <= cap_chunk ? 1 : (l - (kmax - 1) + ch - 1) / ch;
+			if (l < p.kmin) continue;
+			p.n_slots += l <= p.cap_chunk ? 1 : (l - (p.kmax - 1) + p.ch - 1) / p.ch;
 		}
 	}
+	// Reads of different lengths are packed longest first (counting sort: counting is order-independent, ntcard.cpp:142-143).
+	// 64 consecutive slots form a wave, and a wave whose reads are equally long takes the kernel's fast path: with 5 % of
+	// trimmed reads scattered through a batch almost every wave would be ragged (0.95 vs 0.76 ms per 8 M reads).
+	if (!p.chunked && !p.uniform && n_reads < 0xffffffffull) {
+		std::vector<uint64_t> first(p.maxlen + 2, 0);
+		for (uint64_t i = 0; i < n_reads; ++i)
+			++first[p.maxlen - len_of(i) + 1];
+		for (uint64_t l = 1; l <= p.maxlen + 1; ++l)
+			first[l] += first[l - 1];
+		p.order.resize(n_reads);
+		for (uint64_t i = 0; i < n_reads; ++i)
+			p.order[first[p.maxlen - len_of(i)]++] = (uint32_t)i;
+	}
+	return true;
+}
+
+// the slots of a plan, in slot order: emit(read, first byte, bytes, window-start limit) -> 0 or an error, which ends the walk
+template <class LenFn, class Emit> int emit_rows(const RowPlan& p, uint64_t n_reads, const LenFn& len_of, const Emit& emit)
+{
+	for (uint64_t j = 0; j < n_reads; ++j) {
+		const uint64_t i = p.order.empty() ? j : p.order[j];
+		const uint64_t l = len_of(i);
+		if (p.chunked && l < p.kmin) continue;
+		if (!p.chunked || l <= p.cap_chunk) {
+			if (int rc = emit(i, (uint64_t)0, l, l)) return rc;
+			continue;
+		}
+		for (uint64_t start = 0; start + (p.kmax - 1) < l || start == 0; start += p.ch) {
+			const uint64_t nbytes = std::min<uint64_t>(p.cap_chunk, l - start);
+			const bool last = start + p.cap_chunk >= l;
+			if (int rc = emit(i, start, nbytes, last ? nbytes : (uint64_t)p.ch)) return rc;
+			if (last) break;
+		}
+	}
+	return 0;
+}
+
+// reads -> row slots (one slot per read, long sequences in overlapping chunks) -> K1
+template <class LenFn, class PtrFn> int submit_rows(ntc_engine* e, uint64_t n_reads, const LenFn& len_of, const PtrFn& ptr_of)
+{
+	RowPlan p;
+	if (!plan_rows(e, n_reads, len_of, p)) return 0;
+	const uint64_t n_slots = p.n_slots;
+	const uint32_t stride = p.stride;
 	StageLease lease;
 	if (int rc = lease_stage(e, (size_t)n_slots * stride + 16, lease)) return rc;
 	auto& sl = *lease.sl;
-	const bool need_meta = chunked || !uniform;
+	const bool need_meta = p.chunked || !p.uniform;
 	if (need_meta && !(sl.h_meta.reserve(n_slots * 4, sl.h_meta.cap * 2) && sl.d_meta.reserve(n_slots * 4, sl.d_meta.cap * 2)))
 		return fail(NTC_ERR_MEMORY, "ntc_submit: cannot allocate slot metadata");
 	// ---- pack (the copy the ABI promises: caller's buffers are free on return) ----
 	unsigned char* hs = sl.h_stage;
 	uint64_t slot = 0;
-	// Reads of different lengths are packed longest first (counting sort: counting is order-independent, ntcard.cpp:142-143).
-	// 64 consecutive slots form a wave, and a wave whose reads are equally long takes the kernel's fast path: with 5 % of
-	// trimmed reads scattered through a batch almost every wave would be ragged (0.95 vs 0.76 ms per 8 M reads).
-	std::vector<uint32_t> order;
-	if (!chunked && !uniform && n_reads < 0xffffffffull) {
-		std::vector<uint64_t> first(maxlen + 2, 0);
-		for (uint64_t i = 0; i < n_reads; ++i)
-			++first[maxlen - len_of(i) + 1];
-		for (uint64_t l = 1; l <= maxlen + 1; ++l)
-			first[l] += first[l - 1];
-		order.resize(n_reads);
-		for (uint64_t i = 0; i < n_reads; ++i)
-			order[first[maxlen - len_of(i)]++] = (uint32_t)i;
-	}
-	// one slot: nbytes of src, padded; its meta word = bytes | window-start limit << 16
-	auto put = [&](const char* src, uint64_t nbytes, uint64_t limit) {
+	// one slot: nbytes of the read from `start`, padded; its meta word = bytes | window-start limit << 16
+	(void)emit_rows(p, n_reads, len_of, [&](uint64_t i, uint64_t start, uint64_t nbytes, uint64_t limit) {
 		unsigned char* dst = hs + slot * stride;
-		std::memcpy(dst, src, nbytes);
+		std::memcpy(dst, ptr_of(i) + start, nbytes);
 		std::memset(dst + nbytes, 'A', stride - nbytes);
 		if (need_meta) sl.h_meta[slot] = (uint32_t)nbytes | ((uint32_t)limit << 16);
 		++slot;
-	};
-	for (uint64_t j = 0; j < n_reads; ++j) {
-		const uint64_t i = order.empty() ? j : order[j];
-		const uint64_t l = len_of(i);
-		const char* src = ptr_of(i);
-		if (chunked && l < kmin) continue;
-		if (!chunked || l <= cap_chunk) {
-			put(src, l, l);
-			continue;
-		}
-		for (uint64_t start = 0; start + (kmax - 1) < l || start == 0; start += ch) {
-			const uint64_t nbytes = std::min<uint64_t>(cap_chunk, l - start);
-			const bool last = start + cap_chunk >= l;
-			put(src + start, nbytes, last ? nbytes : ch);
-			if (last) break;
-		}
-	}
+		return 0;
+	});
 	if (slot != n_slots) return fail(NTC_ERR_STATE, "ntc_submit: internal slot plan mismatch (%llu != %llu)", (unsigned long long)slot, (unsigned long long)n_slots);
 	// ---- enqueue: copy + kernels, in order on the engine's stream (asynchronous; ntc_sync / ntc_finish wait) ----
 	std::lock_guard<std::mutex> lk(e->mu);
 	if (hipMemcpyAsync(sl.d_stage, hs, (size_t)n_slots * stride, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
 	    (need_meta && hipMemcpyAsync(sl.d_meta, sl.h_meta, n_slots * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess))
 		return stage_copy_failed(e);
-	return end_stage_use(e, sl, run_batch(e, sl.d_stage, need_meta ? sl.d_meta.get() : nullptr, n_slots, (uint32_t)len0, stride));
+	return end_stage_use(e, sl, run_batch(e, sl.d_stage, need_meta ? sl.d_meta.get() : nullptr, n_slots, (uint32_t)p.len0, stride));
+}
+
+// ---- long sequences as pieces (include/ntcard_hip.h: ntc_submit_long_device) ----
+// A sequence of n >= L bytes is cut, ON THE DEVICE, into m = ntc_long_plan() full pieces [j S, j S + L), S = L - (k - 1): an equal-length tiled batch of
+// "reads" for K1h + K1f, which count every window of k bases of a piece — and every window of the sequence lies in exactly one piece or in the remainder
+// [m S, n).  Remainders and sequences shorter than L are gathered into row slots (the plan above) for K1.  An engine whose one plane is not K1h's
+// gathers every sequence whole: ntc_submit's results from device-resident bytes.
+constexpr uint32_t kLongPieceDefault = 1008;   // profiles/long_seq.txt
+constexpr uint64_t kLongMinNever = ~0ull;
+constexpr uint64_t kLongMinDefault = 32768;   // host batches: full pieces from which the sequences of >= 2 pieces take this path (profiles/long_seq.txt: slower
+                                               // than row slots at 8 Ki pieces, level at 16 Ki, 19 % faster at 32 Ki); NTC_LONG_MIN=0: never
+constexpr uint64_t kLongRoundBytes = 1ull << 30; // scratch of one round: a 30 GB sequence set is cut and counted 1 GiB of tiles at a time
+
+bool long_fast(const ntc_engine* e) { return e->ts_all && e->klist.size() == 1; }
+
+int grow_long(ntc_engine* e, size_t need)
+{
+	if (need <= e->d_long.cap) return 0;
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	if (!e->d_long.reserve(need)) return fail(NTC_ERR_MEMORY, "cannot allocate %zu B of scratch for long sequences on device", need);
+	return 0;
+}
+
+// under e->mu: the rounds of one call — cut + K1h + K1f over the pieces, gather + K1 over the row slots; d_off / d_spans: the call's tables on the device
+int run_long_rounds(ntc_engine* e, const unsigned char* d_src, const uint64_t* d_off, uint64_t n_pieces, uint64_t n_cut_seqs, const ntc::LongSpan* d_spans,
+                    uint64_t n_slots, const RowPlan& rp, uint32_t L)
+{
+	uint64_t round = kLongRoundBytes;
+	if (const char* ev = std::getenv("NTC_LONG_ROUND_BYTES")) round = std::max(1ll, std::strtoll(ev, nullptr, 10)); // tests: several rounds of a small input
+	if (n_pieces) {
+		const uint64_t per_round = std::max<uint64_t>(1, round / ((uint64_t)L * ntc::kTileReads)) * ntc::kTileReads; // whole tiles
+		for (uint64_t first = 0; first < n_pieces; first += per_round) {
+			const uint64_t np = std::min(per_round, n_pieces - first);
+			if (int rc = grow_long(e, (size_t)ntc_tiled_bytes(np, L))) return rc;
+			if (int rc = close_run(e)) return rc;
+			Span sp;
+			if (int rc = open_span(e, sp)) return rc;
+			HIP_TRY(ntc::launch_cut_tiles(d_src, d_off + first, np, L, e->d_long, e->stream));
+			if (int rc = close_span(sp, e->stream, e->long_cut_events)) return rc;
+			const TiledSeg sg{e->d_long, np, L, nullptr};
+			if (int rc = run_tiled_segs(e, &sg, 1, 1, true)) return rc; // (the tiles are recycled by the next round: their K1f may not be deferred)
+			e->long_pieces += np;
+		}
+		e->long_seqs += n_cut_seqs;
+	}
+	if (n_slots) {
+		const uint64_t per_round = std::max<uint64_t>(64, (round / (rp.stride + 4u)) & ~63ull);
+		for (uint64_t first = 0; first < n_slots; first += per_round) {
+			const uint64_t ns = std::min(per_round, n_slots - first);
+			const size_t rows_bytes = ((size_t)ns * rp.stride + 16 + 15) & ~(size_t)15; // the slots, then their meta words
+			if (int rc = grow_long(e, rows_bytes + (size_t)ns * 4)) return rc;
+			if (int rc = close_run(e)) return rc;
+			uint32_t* d_meta = reinterpret_cast<uint32_t*>(e->d_long + rows_bytes);
+			Span sp;
+			if (int rc = open_span(e, sp)) return rc;
+			HIP_TRY(ntc::launch_gather_slots(d_src, d_spans + first, ns, rp.stride, e->d_long, d_meta, e->stream));
+			if (int rc = close_span(sp, e->stream, e->long_gather_events)) return rc;
+			if (int rc = run_batch(e, e->d_long, d_meta, ns, (uint32_t)rp.len0, rp.stride)) return rc;
+		}
+	}
+	return 0;
+}
+
+// sequence i = the len_of(i) bytes from d_src + off_of(i).  The tables (8 B per piece, 16 B per row slot) are built in the leased pair's meta buffers;
+// h2d_bytes != 0: d_src is the pair's device side, whose first h2d_bytes the host has filled (ntc_submit's long sequences)
+template <class LenFn, class OffFn>
+int submit_long_leased(ntc_engine* e, ntc_engine::StageSlot& sl, const unsigned char* d_src, size_t h2d_bytes, uint64_t n_seqs, const LenFn& len_of,
+                       const OffFn& off_of, uint32_t L)
+{
+	const bool fast = long_fast(e);
+	const uint32_t k = e->klist[0];
+	const uint64_t S = fast ? L - (k - 1u) : 1u;
+	struct Item {
+		uint64_t src, len;
+	};
+	std::vector<Item> items; // what goes to row slots: remainders that hold a window, sequences without a full piece
+	uint64_t n_pieces = 0, n_cut_seqs = 0;
+	for (uint64_t i = 0; i < n_seqs; ++i) {
+		const uint64_t n = len_of(i);
+		const uint64_t m = fast && n >= L ? (n - L) / S + 1u : 0u; // (ntc_long_plan)
+		n_pieces += m;
+		n_cut_seqs += m != 0;
+		if (m == 0 || n - m * S >= k) items.push_back(Item{off_of(i) + m * S, n - m * S});
+	}
+	const auto item_len = [&](uint64_t i) { return items[i].len; };
+	RowPlan rp;
+	const uint64_t n_slots = !items.empty() && plan_rows(e, items.size(), item_len, rp) ? rp.n_slots : 0;
+	if (n_pieces == 0 && n_slots == 0) return 0;
+	const size_t tab_bytes = (size_t)n_pieces * 8 + (size_t)n_slots * sizeof(ntc::LongSpan);
+	if (!(sl.h_meta.reserve(tab_bytes, sl.h_meta.cap * 2) && sl.d_meta.reserve(tab_bytes, sl.d_meta.cap * 2)))
+		return fail(NTC_ERR_MEMORY, "ntc_submit_long_device: cannot allocate %zu B of piece and slot tables", tab_bytes);
+	uint64_t* h_off = reinterpret_cast<uint64_t*>(sl.h_meta.get());
+	ntc::LongSpan* h_spans = reinterpret_cast<ntc::LongSpan*>(h_off + n_pieces);
+	uint64_t q = 0;
+	for (uint64_t i = 0; i < n_seqs && n_pieces; ++i) {
+		const uint64_t n = len_of(i), o = off_of(i);
+		if (n < L) continue;
+		for (uint64_t j = 0, m = (n - L) / S + 1u; j < m; ++j)
+			h_off[q++] = o + j * S;
+	}
+	uint64_t slot = 0;
+	if (n_slots)
+		(void)emit_rows(rp, items.size(), item_len, [&](uint64_t i, uint64_t start, uint64_t nbytes, uint64_t limit) {
+			h_spans[slot++] = ntc::LongSpan{items[i].src + start, (uint32_t)nbytes, (uint32_t)limit};
+			return 0;
+		});
+	if (q != n_pieces || slot != n_slots) return fail(NTC_ERR_STATE, "ntc_submit_long_device: internal plan mismatch");
+	std::lock_guard<std::mutex> lk(e->mu);
+	if ((h2d_bytes && hipMemcpyAsync(sl.d_stage, sl.h_stage, h2d_bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess) ||
+	    hipMemcpyAsync(sl.d_meta, sl.h_meta, tab_bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess)
+		return stage_copy_failed(e);
+	const uint64_t* d_off = reinterpret_cast<const uint64_t*>(sl.d_meta.get());
+	return end_stage_use(e, sl, run_long_rounds(e, d_src, d_off, n_pieces, n_cut_seqs, reinterpret_cast<const ntc::LongSpan*>(d_off + n_pieces), n_slots, rp, L));
+}
+
+// what submit_impl leaves to row slots.  On an engine whose one plane is K1h's the sequences of at least two full pieces are copied raw and contiguous
+// into the staging pair — one memcpy each, their bytes cross PCIe once — and cut on the device, once together they hold long_min full pieces
+// (NTC_LONG_MIN: tuning runs, tools/long_time.py); everything else takes row slots as before
+template <class LenFn, class PtrFn> int submit_rows_or_long(ntc_engine* e, uint64_t n_reads, const LenFn& len_of, const PtrFn& ptr_of)
+{
+	uint64_t long_min = kLongMinDefault;
+	if (const char* ev = std::getenv("NTC_LONG_MIN")) {
+		const long long v = std::strtoll(ev, nullptr, 10);
+		long_min = v >= 1 ? (uint64_t)v : kLongMinNever;
+	}
+	if (long_min == kLongMinNever || !long_fast(e)) return submit_rows(e, n_reads, len_of, ptr_of);
+	const uint32_t L = kLongPieceDefault;
+	const uint64_t S = L - (e->klist[0] - 1u);
+	std::vector<uint64_t> sel, rest;
+	uint64_t pieces = 0;
+	size_t bytes = 0;
+	for (uint64_t i = 0; i < n_reads; ++i) {
+		const uint64_t n = len_of(i);
+		if (n >= L + S) {
+			pieces += (n - L) / S + 1u;
+			bytes += n;
+			sel.push_back(i);
+		} else {
+			rest.push_back(i);
+		}
+	}
+	if (sel.empty() || pieces < long_min) return submit_rows(e, n_reads, len_of, ptr_of);
+	{
+		StageLease lease;
+		if (int rc = lease_stage(e, bytes + 16, lease)) return rc;
+		auto& sl = *lease.sl;
+		std::vector<uint64_t> off(sel.size() + 1, 0);
+		for (size_t j = 0; j < sel.size(); ++j) {
+			std::memcpy(sl.h_stage + off[j], ptr_of(sel[j]), len_of(sel[j]));
+			off[j + 1] = off[j] + len_of(sel[j]);
+		}
+		if (int rc = submit_long_leased(e, sl, sl.d_stage, bytes, sel.size(), [&](uint64_t j) { return off[j + 1] - off[j]; }, [&](uint64_t j) { return off[j]; }, L))
+			return rc;
+	}
+	if (rest.empty()) return 0;
+	return submit_rows(e, rest.size(), [&](uint64_t i) { return len_of(rest[i]); }, [&](uint64_t i) { return ptr_of(rest[i]); });
 }
 
 template <class LenFn, class PtrFn> int submit_impl(ntc_engine* e, uint64_t n_reads, const LenFn& len_of, const PtrFn& ptr_of)
@@ -277,11 +455,11 @@ template <class LenFn, class PtrFn> int submit_impl(ntc_engine* e, uint64_t n_re
 				// all the bins in one staging buffer and one launch per k (up to 8 bins: run_tiled_segs groups the rest)
 				if (int rc = submit_tiled_host(e, hbins.data(), (uint32_t)hbins.size(), len_of, ptr_of)) return rc;
 				if (rest.empty()) return 0;
-				return submit_rows(e, rest.size(), [&](uint64_t i) { return len_of(rest[i]); }, [&](uint64_t i) { return ptr_of(rest[i]); });
+				return submit_rows_or_long(e, rest.size(), [&](uint64_t i) { return len_of(rest[i]); }, [&](uint64_t i) { return ptr_of(rest[i]); });
 			}
 		}
 	}
-	return submit_rows(e, n_reads, len_of, ptr_of);
+	return submit_rows_or_long(e, n_reads, len_of, ptr_of);
 }
 
 } // namespace
@@ -316,6 +494,28 @@ int ntc_submit_device(ntc_engine* e, const void* d_slots, uint64_t n_reads, uint
 	std::lock_guard<std::mutex> lk(e->mu);
 	HIP_TRY(hipSetDevice(e->device));
 	return run_batch(e, (const unsigned char*)d_slots, nullptr, n_reads, read_len, stride);
+}
+
+int ntc_submit_long_device(ntc_engine* e, const void* d_bases, const uint64_t* offsets, uint64_t n_seqs, uint32_t piece_len)
+{
+	// (what needs no engine first, so that a bad call is told apart before a device is looked for)
+	if (n_seqs && !offsets) return fail(NTC_ERR_ARG, "ntc_submit_long_device: null offsets");
+	if ((piece_len & 15u) || piece_len > 65520u) return fail(NTC_ERR_ARG, "ntc_submit_long_device: piece_len %u is not 0 or a multiple of 16 up to 65520", piece_len);
+	for (uint64_t i = 0; i < n_seqs; ++i)
+		if (offsets[i + 1] < offsets[i]) return fail(NTC_ERR_ARG, "ntc_submit_long_device: offsets not monotone at sequence %llu", (unsigned long long)i);
+	if (n_seqs && offsets[n_seqs] > offsets[0] && !d_bases) return fail(NTC_ERR_ARG, "ntc_submit_long_device: null buffer");
+	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_long_device: null engine");
+	if (n_seqs == 0) return 0;
+	const bool fast = long_fast(e);
+	if (!fast && e->ts_required)
+		return fail(NTC_ERR_ARG, "ntc_submit_long_device: the tiled kernels do not serve this configuration (NTC_FLAG_REQUIRE_TILED); nothing was counted");
+	const uint32_t L = piece_len ? piece_len : kLongPieceDefault;
+	if (fast && L < e->klist[0] + 15u)
+		return fail(NTC_ERR_ARG, "ntc_submit_long_device: piece_len %u below k + 15 = %u", L, e->klist[0] + 15u);
+	StageLease lease;
+	if (int rc = lease_stage(e, 0, lease)) return rc; // (its meta buffers hold the call's tables)
+	return submit_long_leased(e, *lease.sl, (const unsigned char*)d_bases, 0, n_seqs, [&](uint64_t i) { return offsets[i + 1] - offsets[i]; },
+	                          [&](uint64_t i) { return offsets[i]; }, L);
 }
 
 int ntc_submit_tiled_device(ntc_engine* e, const void* d_tiles, uint64_t n_reads, uint32_t read_len)

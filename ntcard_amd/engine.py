@@ -164,6 +164,24 @@ class Engine:
         tails = (C.c_void_p * n)(*[(b[3] or None) for b in bins])
         check(self._lib.ntc_submit_tiled_bins_device(self._h, n, tiles, nr, rl, tails))
 
+    def submit_long_device(self, d_ptr, offsets, piece_len=0):
+        """device-resident long sequences: sequence i = the bytes [offsets[i], offsets[i + 1]) from d_ptr (device memory, raw bytes of any alignment);
+        offsets: host uint64[n + 1]; piece_len: 0 or a multiple of 16 (include/ntcard_hip.h: ntc_submit_long_device)"""
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        check(self._lib.ntc_submit_long_device(self._h, C.c_void_p(d_ptr) if d_ptr else None, _np_ptr(o), max(len(o) - 1, 0), int(piece_len)))
+
+    def long_stats(self):
+        """-> (full pieces cut for the tiled kernels, sequences that contributed one) since create / reset (ntc_long_stats)"""
+        pieces, seqs = C.c_uint64(), C.c_uint64()
+        check(self._lib.ntc_long_stats(self._h, C.byref(pieces), C.byref(seqs)))
+        return pieces.value, seqs.value
+
+    def long_time(self):
+        """-> (cut ms, gather ms) of submit_long_device's re-layout kernels while profiling (ntc_long_time)"""
+        cut, gather = C.c_double(), C.c_double()
+        check(self._lib.ntc_long_time(self._h, C.byref(cut), C.byref(gather)))
+        return cut.value, gather.value
+
     def sync(self):
         check(self._lib.ntc_sync(self._h))
 
@@ -287,6 +305,13 @@ def write_hist(path, f1, F0, f, cov_max=1000):
 def gen_reads_device(d_ptr, seed, first, n, read_len, stride, dist, genome_len=100_000_000, device=0, stream=None):
     check(_abi.lib().ntc_gen_reads_device(device, C.c_void_p(stream) if stream else None, C.c_void_p(d_ptr), seed, first, n,
                                           read_len, stride, dist, genome_len))
+
+
+def long_plan(k, piece_len, n):
+    """the cut of one sequence of n bytes into pieces of piece_len -> (full pieces m, start of the remainder [m S, n)); ntc_long_plan, host only"""
+    m, rem = C.c_uint64(), C.c_uint64()
+    check(_abi.lib().ntc_long_plan(int(k), int(piece_len), int(n), C.byref(m), C.byref(rem)))
+    return m.value, rem.value
 
 
 def tiled_bytes(n_reads, read_len):
