@@ -101,7 +101,7 @@ typedef struct {
  * is the general kernel's (K1, in its one-strand form: one rolling update and one table half per base instead of two) and the simple validation kernel's:
  * the tiled kernel pair K1h + K1f is canonical only, so no k of a strand engine is theirs — tiled batches, ragged ones and bins included, are re-laid out
  * on the device and counted by K1, NTC_FLAG_REQUIRE_TILED makes the tiled submit fail with nothing counted, host batches take row slots.  It counts at K1's
- * rate, not at K1h's (DESIGN.md §4 "One strand").  ntc_merge_devices refuses engines whose strands differ.  ntc_hll_create has no flags: nthll is canonical. */
+ * rate, not at K1h's (DESIGN.md §4 "One strand").  ntc_merge_devices refuses engines whose strands differ.  nthll engines take the same two flags through ntc_hll_create_ex (ntc_hll_create: canonical). */
 #define NTC_FLAG_STRAND_FORWARD 512u
 #define NTC_FLAG_STRAND_REVERSE 1024u
 #define NTC_FLAG_DIRECT_ATOMICS 2u /* no hit log: every sampled k-mer is one device atomic on the sketch
@@ -347,16 +347,42 @@ int ntc_estimate(const uint32_t *p_hist /* [2][65536] */, uint32_t r_bits, uint3
  * given verbatim.  Returns 0 or NTC_ERR_ARG if the file cannot be written.                      */
 int ntc_write_hist(const char *path, uint64_t f1, double F0, const double *f, uint32_t cov_max);
 
-/* ---- nthll: HyperLogLog-style F0 of the same canonical ntHash stream --------------
+/* ---- nthll: HyperLogLog-style F0 of the same ntHash stream ---------------------------
  * Replaces nthll.cpp's per-thread `uint8_t mVec[nBuck]`, its ntRead/ntComp (nthll.cpp:92-105: bucket = low
  * n_bits of the hash, value = leading zeros of the remaining bits, keep the max), the max-merge under
  * `omp critical` (nthll.cpp:238-243) and the estimate (nthll.cpp:247-254).  Reads are fed with
- * ntc_submit / ntc_submit_device exactly as for an ntcard engine.                                          */
+ * ntc_submit / ntc_submit_device exactly as for an ntcard engine.
+ * ntc_hll_create: one plain k, canonical — what nthll counts; the one-k, flag-less case of ntc_hll_create_ex. */
 int ntc_hll_create(uint32_t k, uint32_t n_bits /* nthll -b, default 16 */, int32_t device, void *stream,
                    ntc_engine **out);
-/* regs_out: HOST uint8_t [1<<n_bits] (== tVec of nthll.cpp:212-243); f1_out: number of k-mers hashed, or NULL */
+/* An nthll engine with several planes, spaced seeds and a strand (additive to ABI 6).  Plane i — the i-th k or the i-th mask, in list order — is a
+ * register file M_i[1 << n_bits] of its own.  The value of a window is the one an ntcard plane of that mask and strand counts (NTC_FLAG_STRAND_* and
+ * ntc_create_seeded above): canonical rs < fs ? rs : fs, forward fs, reverse rs; a window counts (F1, registers) only when all k bytes are bases, those
+ * under a '0' included.  Behind the value nthll.cpp:92-97 applies unchanged: bucket = the low n_bits bits, value = the leading zeros of the remaining
+ * bits, skipped when those are all zero, keep the max.
+ * Every argument is checked before a device is looked for; NTC_ERR_ARG with a message for: both strand flags, any other flag, both lists or neither, a
+ * bad mask (the rules of ntc_create_seeded), more than NTC_MAX_K_LIST planes, a k outside 1 .. ntc_max_k(), n_bits outside 4 .. 24.
+ * Every submit call works on such an engine: ntc_submit*, ntc_submit_device, the tiled submits (re-laid out on the device as row slots) and
+ * ntc_submit_long_device (every sequence gathered whole); the general kernel K1 hashes a batch once per plane.  A mask whose tables leave no room in LDS
+ * for a batch's slots makes the submit fail with a message, nothing counted, as for an ntcard engine.  ntc_reset zeroes every plane; ntc_merge_devices
+ * folds every plane's registers by max and F1 by sum and refuses engines whose planes, masks, strand or n_bits differ. */
+typedef struct {
+    uint32_t n_k; const uint32_t *k;              /* a k list (plain k-mers), 1 .. NTC_MAX_K_LIST entries, each 1 .. ntc_max_k() — or */
+    uint32_t n_seeds; const char *const *seeds;   /* masks with the syntax and rules of ntc_create_seeded; exactly one of the two is non-empty */
+    uint32_t n_bits;                              /* nthll -b, 4 .. 24 */
+    int32_t device; void *stream;
+    uint32_t flags;                               /* 0, NTC_FLAG_STRAND_FORWARD or NTC_FLAG_STRAND_REVERSE; anything else: NTC_ERR_ARG */
+} ntc_hll_config;
+int ntc_hll_create_ex(const ntc_hll_config *cfg, ntc_engine **out);
+/* regs_out: HOST uint8_t [n_planes][1<<n_bits] (a plane == tVec of nthll.cpp:212-243), or NULL; f1_out: uint64_t [n_planes], the k-mers hashed per
+ * plane, or NULL.  One plane (ntc_hll_create): uint8_t [1<<n_bits] and one uint64_t. */
 int ntc_hll_finish(ntc_engine *e, uint8_t *regs_out, uint64_t *f1_out);
+/* nthll.cpp:247-254 on one plane's registers, alpha halved as the reference does for canonical hashes (nthll.cpp:248-249) */
 int ntc_hll_estimate(const uint8_t *regs, uint32_t n_bits, double *est_out);
+/* the same for an engine's strand: 0 canonical — bit for bit ntc_hll_estimate; 1 forward, 2 reverse — the alpha is NOT halved (the halving answers for the
+ * canonical value being the minimum of two; a one-strand value is uniform), every other operation and its order as in nthll.cpp:247-254, no FMA
+ * contraction; any other strand: NTC_ERR_ARG */
+int ntc_hll_estimate_strand(const uint8_t *regs, uint32_t n_bits, uint32_t strand, double *est_out);
 
 /* Timing of the hot kernel as measured with HIP events on the engine's stream (for bench.py's
  * roofline leg): accumulated milliseconds and launch count since create/reset.                  */

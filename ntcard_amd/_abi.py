@@ -14,13 +14,27 @@ ABI_SYMBOLS = [
     "ntc_abi_version", "ntc_max_k", "ntc_last_error", "ntc_create", "ntc_destroy", "ntc_reset",
     "ntc_submit", "ntc_submit_spans", "ntc_submit_device", "ntc_sync", "ntc_finish", "ntc_device_state",
     "ntc_hash_dump_device", "ntc_hash_dump_k1_device", "ntc_gen_reads_device", "ntc_estimate", "ntc_write_hist",
-    "ntc_kernel_time", "ntc_apply_time", "ntc_fixup_time", "ntc_merge_allocations", "ntc_update_mode", "ntc_flush", "ntc_set_profiling", "ntc_merge_counters", "ntc_merge_devices", "ntc_value_hist_device", "ntc_hll_create", "ntc_hll_finish", "ntc_hll_estimate",
+    "ntc_kernel_time", "ntc_apply_time", "ntc_fixup_time", "ntc_merge_allocations", "ntc_update_mode", "ntc_flush", "ntc_set_profiling", "ntc_merge_counters", "ntc_merge_devices", "ntc_value_hist_device", "ntc_hll_create", "ntc_hll_finish", "ntc_hll_estimate", "ntc_hll_create_ex", "ntc_hll_estimate_strand",
     "ntc_submit_tiled_device", "ntc_submit_tiled_ragged_device", "ntc_submit_tiled_bins_device", "ntc_tiled_bytes", "ntc_gen_reads_tiled_device",
     "ntc_narrow_u16_device", "ntc_sum_slices_u16_device", "ntc_value_hist_u16_device",
     "ntc_log_export_device", "ntc_log_replace_device",
     "ntc_create_seeded", "ntc_hash_dump_seed_device", "ntc_hash_dump_strand_device",
     "ntc_submit_long_device", "ntc_long_plan", "ntc_long_stats", "ntc_long_time",
 ]
+
+
+class NtcHllConfig(C.Structure):
+    """ntc_hll_config"""
+    _fields_ = [
+        ("n_k", C.c_uint32),
+        ("k", C.POINTER(C.c_uint32)),
+        ("n_seeds", C.c_uint32),
+        ("seeds", C.POINTER(C.c_char_p)),
+        ("n_bits", C.c_uint32),
+        ("device", C.c_int32),
+        ("stream", C.c_void_p),
+        ("flags", C.c_uint32),
+    ]
 
 
 class NtcConfig(C.Structure):
@@ -113,6 +127,8 @@ def lib():
     L.ntc_hll_create.argtypes = [u32, u32, i32, p, C.POINTER(p)]
     L.ntc_hll_finish.argtypes = [p, p, p]
     L.ntc_hll_estimate.argtypes = [p, u32, C.POINTER(C.c_double)]
+    L.ntc_hll_create_ex.argtypes = [C.POINTER(NtcHllConfig), C.POINTER(p)]
+    L.ntc_hll_estimate_strand.argtypes = [p, u32, u32, C.POINTER(C.c_double)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("ntc_abi_version", "ntc_max_k", "ntc_last_error", "ntc_destroy", "ntc_tiled_bytes"):

@@ -52,13 +52,15 @@ int ntc_estimate(const uint32_t* p_hist, uint32_t r_bits, uint32_t s_bits, uint3
 	return 0;
 }
 
-// nthll.cpp:247-254: alpha * m^2 / sum_j 2^-M[j], alpha halved because the hashes are canonical
-int ntc_hll_estimate(const uint8_t* regs, uint32_t n_bits, double* est_out)
+// nthll.cpp:247-254: alpha * m^2 / sum_j 2^-M[j]; alpha is halved when the hashes are canonical (nthll.cpp:248-249: the minimum of two values),
+// not for one strand, whose value is uniform
+int ntc_hll_estimate_strand(const uint8_t* regs, uint32_t n_bits, uint32_t strand, double* est_out)
 {
 	if (!regs || !est_out || n_bits > 31) return ntc_internal_fail(NTC_ERR_ARG, "ntc_hll_estimate: null argument or n_bits %u > 31", n_bits);
+	if (strand > 2) return ntc_internal_fail(NTC_ERR_ARG, "ntc_hll_estimate_strand: strand %u is none of 0 (canonical), 1 (forward), 2 (reverse)", strand);
 	const unsigned n_buck = 1u << n_bits;
 	double alpha = 1.4426 / (1 + 1.079 / n_buck);
-	alpha /= 2;
+	if (strand == 0) alpha /= 2;
 	double p_est = 0.0;
 	for (unsigned j = 0; j < n_buck; ++j)
 		p_est += 1.0 / ((uint64_t)1 << regs[j]);
@@ -66,6 +68,8 @@ int ntc_hll_estimate(const uint8_t* regs, uint32_t n_bits, double* est_out)
 	*est_out = alpha * n_buck * n_buck * z_est;
 	return 0;
 }
+
+int ntc_hll_estimate(const uint8_t* regs, uint32_t n_bits, double* est_out) { return ntc_hll_estimate_strand(regs, n_bits, 0, est_out); }
 
 int ntc_write_hist(const char* path, uint64_t f1, double F0, const double* f, uint32_t cov_max)
 {

@@ -306,29 +306,38 @@ struct SlotBatch {
 };
 
 // nthll: refresh the "can still matter" threshold between sub-batches that double in size, so the
-// expensive resolve stage only sees a vanishing fraction of the k-mers once the registers warm up
+// expensive resolve stage only sees a vanishing fraction of the k-mers once the registers warm up.
+// Planes: one launch per plane per sub-batch, each against its own threshold word, refreshed from that plane's registers (DESIGN.md §4 "nthll forms").
 int run_hll(ntc_engine* e, const SlotBatch& b)
 {
+	const size_t nk = e->klist.size();
+	std::vector<HfPlan> plans(nk); // every plane's launch shape first (waves per CU do not depend on the slot count): a mask whose tables do not fit fails HERE, nothing counted
+	for (size_t ki = 0; ki < nk; ++ki)
+		if (int rc = hf_plan(e->device, std::min<uint64_t>(b.n, 16384), b.stride, &e->klist[ki], 1, seed_lds(e->seeds[ki]), plans[ki])) return rc;
 	for (uint64_t done = 0; done < b.n;) {
 		uint64_t n = std::max<uint64_t>(16384, e->hll_reads_seen);
 		n = std::min<uint64_t>((n + 63) & ~63ull, b.n - done); // whole waves: a sub-batch starts on a 16-byte aligned slot
-		HIP_TRY(ntc::launch_hll_threshold(e->d_sketch, 1u << e->hll_bits, e->d_hll_thr, e->stream));
-		ntc::HfArgs a;
-		std::memset(&a, 0, sizeof a);
-		a.slots = b.slots + done * b.stride;
-		a.meta = b.meta ? b.meta + done : nullptr;
-		a.n_slots = n;
-		a.stride = b.stride;
-		a.read_len = b.read_len;
-		a.r_bits = 27;
-		a.s_bits = 7;
-		a.n_k = 1;
-		a.hll_bits = e->hll_bits;
-		a.hll_thr = e->d_hll_thr;
-		a.ks[0] = e->hfk[0];
-		HfPlan hp;
-		if (int rc = hf_plan(e->device, n, b.stride, &e->klist[0], 1, 0, hp)) return rc;
-		HIP_TRY(ntc::launch_sketch_hf(a, hp.grid, hp.wpb, hp.smem, e->stream));
+		for (size_t ki = 0; ki < nk; ++ki) {
+			uint32_t* const regs = e->d_sketch + (ki << e->hll_bits);
+			HIP_TRY(ntc::launch_hll_threshold(regs, 1u << e->hll_bits, e->d_hll_thr + ki, e->stream));
+			ntc::HfArgs a;
+			std::memset(&a, 0, sizeof a);
+			a.slots = b.slots + done * b.stride;
+			a.meta = b.meta ? b.meta + done : nullptr;
+			a.n_slots = n;
+			a.stride = b.stride;
+			a.read_len = b.read_len;
+			a.r_bits = 27;
+			a.s_bits = 7;
+			a.n_k = 1;
+			a.hll_bits = e->hll_bits;
+			a.hll_thr = e->d_hll_thr + ki;
+			if (!e->plain(ki)) set_seed_args(a, e->seeds[ki], e->d_seedt[ki]);
+			a.ks[0] = e->hfk[ki];
+			HfPlan hp;
+			if (int rc = hf_plan(e->device, n, b.stride, &e->klist[ki], 1, seed_lds(e->seeds[ki]), hp)) return rc;
+			HIP_TRY(ntc::launch_sketch_hf(a, hp.grid, hp.wpb, hp.smem, e->stream));
+		}
 		done += n;
 		e->hll_reads_seen += n;
 	}

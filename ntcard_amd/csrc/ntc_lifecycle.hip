@@ -66,6 +66,26 @@ int check_config(const ntc_config* cfg)
 	return 0;
 }
 
+// the masks of ntc_create_seeded / ntc_hll_create_ex: 1 .. NTC_MAX_K_LIST strings of '0' / '1' with at least one '1', 1 .. kMaxK long
+int parse_masks(const char* who, uint32_t n_seeds, const char* const* seeds, std::vector<std::string>& masks, std::vector<uint32_t>& ks)
+{
+	if (n_seeds == 0 || n_seeds > NTC_MAX_K_LIST) return fail(NTC_ERR_ARG, "%s: need 1..%d seeds", who, NTC_MAX_K_LIST);
+	masks.assign(n_seeds, std::string());
+	ks.assign(n_seeds, 0u);
+	for (uint32_t i = 0; i < n_seeds; ++i) {
+		if (!seeds[i]) return fail(NTC_ERR_ARG, "%s: seed %u is null", who, i + 1);
+		const size_t len = strnlen(seeds[i], (size_t)kMaxK + 1);
+		if (len < 1 || len > kMaxK) return fail(NTC_ERR_ARG, "%s: seed %u: length outside 1..%u", who, i + 1, kMaxK);
+		for (size_t j = 0; j < len; ++j)
+			if (seeds[i][j] != '0' && seeds[i][j] != '1')
+				return fail(NTC_ERR_ARG, "%s: seed %u: character %zu is neither '0' nor '1'", who, i + 1, j + 1);
+		masks[i].assign(seeds[i], len);
+		if (masks[i].find('1') == std::string::npos) return fail(NTC_ERR_ARG, "%s: seed %u has no '1'", who, i + 1);
+		ks[i] = (uint32_t)len;
+	}
+	return 0;
+}
+
 // an engine under construction: any return before release() destroys it, with everything it owns so far
 struct EngineDeleter {
 	void operator()(ntc_engine* e) const { ntc_destroy(e); }
@@ -227,22 +247,12 @@ int ntc_create_seeded(const ntc_config* cfg, uint32_t n_seeds, const char* const
 	*out = nullptr;
 	if (cfg->n_k != 0 || cfg->k != nullptr || cfg->gap != 0)
 		return fail(NTC_ERR_ARG, "ntc_create_seeded: n_k, k and gap of the config must be 0 (the k list is the seeds' lengths)");
-	if (n_seeds == 0 || n_seeds > NTC_MAX_K_LIST) return fail(NTC_ERR_ARG, "ntc_create_seeded: need 1..%d seeds", NTC_MAX_K_LIST);
-	std::vector<std::string> masks(n_seeds);
-	std::vector<uint32_t> ks(n_seeds);
+	std::vector<std::string> masks;
+	std::vector<uint32_t> ks;
+	if (int rc = parse_masks("ntc_create_seeded", n_seeds, seeds, masks, ks)) return rc;
 	bool spaced = false;
-	for (uint32_t i = 0; i < n_seeds; ++i) {
-		if (!seeds[i]) return fail(NTC_ERR_ARG, "ntc_create_seeded: seed %u is null", i + 1);
-		const size_t len = strnlen(seeds[i], (size_t)kMaxK + 1);
-		if (len < 1 || len > kMaxK) return fail(NTC_ERR_ARG, "ntc_create_seeded: seed %u: length outside 1..%u", i + 1, kMaxK);
-		for (size_t j = 0; j < len; ++j)
-			if (seeds[i][j] != '0' && seeds[i][j] != '1')
-				return fail(NTC_ERR_ARG, "ntc_create_seeded: seed %u: character %zu is neither '0' nor '1'", i + 1, j + 1);
-		masks[i].assign(seeds[i], len);
-		if (masks[i].find('1') == std::string::npos) return fail(NTC_ERR_ARG, "ntc_create_seeded: seed %u has no '1'", i + 1);
-		spaced |= masks[i].find('0') != std::string::npos;
-		ks[i] = (uint32_t)len;
-	}
+	for (const std::string& m : masks)
+		spaced |= m.find('0') != std::string::npos;
 	ntc_config c = *cfg;
 	c.n_k = n_seeds;
 	c.k = ks.data();
@@ -251,34 +261,86 @@ int ntc_create_seeded(const ntc_config* cfg, uint32_t n_seeds, const char* const
 	return create_engine(&c, masks, true, out);
 }
 
-int ntc_hll_create(uint32_t k, uint32_t n_bits, int32_t device, void* stream, ntc_engine** out)
+int ntc_hll_create_ex(const ntc_hll_config* cfg, ntc_engine** out)
 {
-	if (!out) return fail(NTC_ERR_ARG, "ntc_hll_create: null argument");
+	if (!cfg || !out) return fail(NTC_ERR_ARG, "ntc_hll_create_ex: null argument");
 	*out = nullptr;
-	if (k < 1 || k > kMaxK) return fail(NTC_ERR_ARG, "ntc_hll_create: k=%u outside 1..%u", k, kMaxK);
-	if (n_bits < 4 || n_bits > 24) return fail(NTC_ERR_ARG, "ntc_hll_create: n_bits %u outside 4..24", n_bits);
+	// every argument first, the device afterwards
+	if (cfg->flags & ~(NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE))
+		return fail(NTC_ERR_ARG, "ntc_hll_create_ex: unknown flag bits 0x%x (an nthll engine takes the strand flags only)", cfg->flags & ~(NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE));
+	if ((cfg->flags & NTC_FLAG_STRAND_FORWARD) && (cfg->flags & NTC_FLAG_STRAND_REVERSE))
+		return fail(NTC_ERR_ARG, "ntc_hll_create_ex: NTC_FLAG_STRAND_FORWARD and NTC_FLAG_STRAND_REVERSE exclude each other");
+	const bool has_k = cfg->n_k != 0 || cfg->k != nullptr, has_seeds = cfg->n_seeds != 0 || cfg->seeds != nullptr;
+	if (has_k == has_seeds) return fail(NTC_ERR_ARG, "ntc_hll_create_ex: need either a k list or a list of seeds, not %s", has_k ? "both" : "neither");
+	std::vector<std::string> masks;
+	std::vector<uint32_t> ks;
+	if (has_k) {
+		if (cfg->n_k == 0 || cfg->n_k > NTC_MAX_K_LIST || !cfg->k) return fail(NTC_ERR_ARG, "ntc_hll_create_ex: need 1..%d k values", NTC_MAX_K_LIST);
+		for (uint32_t i = 0; i < cfg->n_k; ++i)
+			if (cfg->k[i] < 1 || cfg->k[i] > kMaxK) return fail(NTC_ERR_ARG, "ntc_hll_create_ex: k=%u outside 1..%u", cfg->k[i], kMaxK);
+		ks.assign(cfg->k, cfg->k + cfg->n_k);
+		masks.assign(cfg->n_k, std::string());
+	} else {
+		if (!cfg->seeds) return fail(NTC_ERR_ARG, "ntc_hll_create_ex: n_seeds = %u without seeds", cfg->n_seeds);
+		if (int rc = parse_masks("ntc_hll_create_ex", cfg->n_seeds, cfg->seeds, masks, ks)) return rc;
+	}
+	if (cfg->n_bits < 4 || cfg->n_bits > 24) return fail(NTC_ERR_ARG, "ntc_hll_create_ex: n_bits %u outside 4..24", cfg->n_bits);
 	EnginePtr e;
-	if (int rc = new_engine("ntc_hll_create", device, stream, e)) return rc;
-	e->klist.assign(1, k);
-	e->masks.assign(1, std::string());
-	e->kgap.assign(1, 0u);
-	e->seeds.assign(1, ntc::SeedPlan());
+	if (int rc = new_engine("ntc_hll_create_ex", cfg->device, cfg->stream, e)) return rc;
+	const size_t nk = ks.size();
+	const uint32_t n_bits = cfg->n_bits;
+	e->klist = ks;
+	e->seeded = has_seeds;
+	e->strand = (cfg->flags & NTC_FLAG_STRAND_FORWARD) ? 1u : (cfg->flags & NTC_FLAG_STRAND_REVERSE) ? 2u : 0u;
+	e->masks.assign(nk, std::string());
+	e->kgap.assign(nk, 0u);
+	e->seeds.assign(nk, ntc::SeedPlan());
+	e->k_tiled.assign(nk, 0); // (no plane of an nthll engine is the tiled kernels')
 	e->r_bits = 27;
 	e->s_bits = 7;
 	e->hll_bits = n_bits;
 	e->kernel_kind = KIND_HF;
-	std::vector<uint32_t> t1((size_t)ntc::t2_pairs(k) * 64);
-	ntc::build_t2(k, t1.data());
-	e->d_t1.resize(1);
-	if (!e->own_sketch.reserve(sizeof(uint32_t) << n_bits) || !e->own_f1.reserve(8) || !e->d_hll_thr.reserve(4) || !e->d_t1[0].upload(t1))
-		return fail(NTC_ERR_MEMORY, "ntc_hll_create: device allocation failed");
+	for (size_t ki = 0; ki < nk; ++ki) {
+		if (masks[ki].find('0') == std::string::npos) continue; // every position cared for: plain k-mers
+		e->masks[ki] = masks[ki];
+		e->kgap[ki] = symmetric_gap(masks[ki]);
+		ntc::build_seed_plan(masks[ki], e->seeds[ki]);
+		ntc::strand_seed_plan(e->seeds[ki], e->strand);
+		e->max_seed_lds = std::max(e->max_seed_lds, seed_lds(e->seeds[ki]));
+	}
+	// plane ki: its own register file M[1 << n_bits] (uint32 on the device), its own F1 and its own threshold word
+	if (!e->own_sketch.reserve((nk * sizeof(uint32_t)) << n_bits) || !e->own_f1.reserve(nk * 8) || !e->d_hll_thr.reserve(nk * 4))
+		return fail(NTC_ERR_MEMORY, "ntc_hll_create_ex: device allocation failed");
 	e->d_sketch = e->own_sketch;
 	e->d_f1 = e->own_f1;
-	e->hfk.resize(1);
-	fill_hfk(e->hfk[0], k, e->d_sketch, e->d_f1, e->d_t1[0]);
+	e->d_t1.resize(nk);
+	e->d_seedt.resize(nk);
+	e->hfk.resize(nk);
+	for (size_t ki = 0; ki < nk; ++ki) {
+		std::vector<uint32_t> t1((size_t)ntc::t2_pairs(ks[ki]) * 64);
+		ntc::build_t2(ks[ki], t1.data(), e->plain(ki) ? nullptr : e->masks[ki].c_str());
+		ntc::strand_t2(ks[ki], t1.data(), e->strand);
+		if (!e->d_t1[ki].upload(t1) || (!e->plain(ki) && !e->d_seedt[ki].upload(e->seeds[ki].blob)))
+			return fail(NTC_ERR_MEMORY, "ntc_hll_create_ex: cannot allocate the seed tables on device");
+		fill_hfk(e->hfk[ki], ks[ki], e->d_sketch + (ki << n_bits), e->d_f1 + ki, e->d_t1[ki], 0, e->strand);
+	}
 	if (int rc = ntc_reset(e.get())) return rc;
 	*out = e.release();
 	return 0;
+}
+
+// the one-k, canonical case of ntc_hll_create_ex
+int ntc_hll_create(uint32_t k, uint32_t n_bits, int32_t device, void* stream, ntc_engine** out)
+{
+	if (!out) return fail(NTC_ERR_ARG, "ntc_hll_create: null argument");
+	ntc_hll_config cfg;
+	std::memset(&cfg, 0, sizeof cfg);
+	cfg.n_k = 1;
+	cfg.k = &k;
+	cfg.n_bits = n_bits;
+	cfg.device = device;
+	cfg.stream = stream;
+	return ntc_hll_create_ex(&cfg, out);
 }
 
 // everything the engine owns is freed by its members' destructors, once nothing of it is in flight any more
@@ -297,7 +359,7 @@ int ntc_reset(ntc_engine* e)
 	std::lock_guard<std::mutex> lk(e->mu);
 	HIP_TRY(hipSetDevice(e->device));
 	if (int rc = join_k1f(e)) return rc;
-	HIP_TRY(hipMemsetAsync(e->d_sketch, 0, e->hll_bits ? (sizeof(uint32_t) << e->hll_bits) : e->klist.size() * e->plane_elems() * sizeof(uint32_t), e->stream));
+	HIP_TRY(hipMemsetAsync(e->d_sketch, 0, e->hll_bits ? (e->klist.size() * sizeof(uint32_t)) << e->hll_bits : e->klist.size() * e->plane_elems() * sizeof(uint32_t), e->stream));
 	e->hll_reads_seen = 0;
 	if (e->d_logfill) HIP_TRY(hipMemsetAsync(e->d_logfill, 0, (size_t)e->all_log_regions() * 4, e->stream));
 	if (e->d_skdirty) HIP_TRY(hipMemsetAsync(e->d_skdirty, 0, 4, e->stream));
@@ -372,9 +434,9 @@ int ntc_hll_finish(ntc_engine* e, uint8_t* regs_out, uint64_t* f1_out)
 	if (!e || !e->hll_bits) return fail(NTC_ERR_STATE, "ntc_hll_finish: not an nthll engine");
 	std::lock_guard<std::mutex> lk(e->mu);
 	HIP_TRY(hipSetDevice(e->device));
-	std::vector<uint32_t> regs((size_t)1 << e->hll_bits);
+	std::vector<uint32_t> regs(e->klist.size() << e->hll_bits); // every plane, in list order
 	HIP_TRY(hipMemcpyAsync(regs.data(), e->d_sketch, regs.size() * 4, hipMemcpyDeviceToHost, e->stream));
-	if (f1_out) HIP_TRY(hipMemcpyAsync(f1_out, e->d_f1, 8, hipMemcpyDeviceToHost, e->stream));
+	if (f1_out) HIP_TRY(hipMemcpyAsync(f1_out, e->d_f1, e->klist.size() * 8, hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	if (regs_out)
 		for (size_t i = 0; i < regs.size(); ++i)

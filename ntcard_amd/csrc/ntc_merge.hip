@@ -84,7 +84,7 @@ void release_peers(std::vector<MergePeer>& peers) // (buffers, streams and event
 int fold_small(ntc_engine* const* engines, int32_t n, bool regs)
 {
 	ntc_engine* root = engines[0];
-	const size_t bytes = regs ? (size_t)4 << root->hll_bits : root->klist.size() * 8;
+	const size_t bytes = regs ? (root->klist.size() * 4) << root->hll_bits : root->klist.size() * 8; // (nthll: every plane's register file)
 	void* tmp = nullptr;
 	HIP_TRY(hipSetDevice(root->device));
 	HIP_TRY(hipMalloc(&tmp, bytes));

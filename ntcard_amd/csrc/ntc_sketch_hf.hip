@@ -120,8 +120,9 @@ __device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_bal
 } // namespace
 
 // kMulti = false: exactly one k (the loop over the k list folds away and every per-k value is a launch constant)
-// kMode: 0 plain k-mers, 1 spaced seed (any mask; ntcard's -g seed is the one-run case), 2 nthll — separate instantiations keep each one's register budget
-// free of the other modes' state (the spaced-seed walks cost the plain kernel 5 spilled VGPRs otherwise)
+// kMode: 0 plain k-mers, 1 spaced seed (any mask; ntcard's -g seed is the one-run case), 2 nthll, 3 nthll under a spaced seed — separate instantiations keep
+// each one's register budget free of the other modes' state (the spaced-seed walks cost the plain kernel 5 spilled VGPRs otherwise).  The nthll modes drop the
+// sample bounds, the flipped bit and the hit log; they add the threshold word and the register update of the resolve stage, and combine with kOne
 // kPref: 1 KiB chunks of the NEXT batch a wave keeps in flight in registers (10 covers slots of up to 160 B at 16 waves
 // per CU; 16 covers 256 B slots, whose LDS footprint allows 12 waves at most, hence the smaller launch bound)
 // kDump: validation build (ntc_hash_dump_k1_device): the filter lets EVERY window through, so the resolve stage
@@ -138,6 +139,9 @@ __device__ unsigned long long g_hf_clocks[2 * 8192];
 extern "C" int ntc_dbg_hf_clocks(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ntc::g_hf_clocks), sizeof(unsigned long long) * 2 * 8192); }
 namespace ntc {
 #endif
+
+constexpr bool mode_spaced(int mode) { return (mode & 1) != 0; }
+constexpr bool mode_hll(int mode) { return mode >= 2; }
 
 template <bool kMulti, int kMode, int kPref, bool kDump = false, bool kTiled = false, bool kOne = false>
 __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(const HfArgs a)
@@ -168,7 +172,7 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 	// dynamic LDS: [closed-form tables of every fused k][gap table][16 B pad][waves x 64 slots].  The tables come first:
 	// with 1280 B of static LDS in front they start 256-byte aligned, so `index | base` addresses them.  The gap table of a
 	// spaced seed is SeedPlan::blob: XOR-out pair tables, the toggle tables beyond pair 0, the XOR-out position words.
-	const uint32_t seed_extra = kMode == 1 ? a.seed_extra : 0u;
+	const uint32_t seed_extra = mode_spaced(kMode) ? a.seed_extra : 0u;
 	const uint32_t tables_bytes = t1_off[kMaxFusedK] + ((a.gap + 1u) >> 1) * 256u + seed_extra;
 	unsigned char* const wdata = smem + tables_bytes + 16 + (size_t)wave * 64u * stride;
 	const unsigned char* const mine = wdata + (size_t)lane * stride;
@@ -178,15 +182,18 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 	// spaced seed (stRead, ntcard.cpp:160-171): per pair of don't-care positions, the H halves of the terms to XOR out
 	const uint32_t ngp = (a.gap + 1u) >> 1;
 	unsigned char* const gapT = t1_base + t1_off[kMaxFusedK];
-	const uint32_t nroll = kMode == 1 ? a.seed_nroll : 0u;
+	const uint32_t nroll = mode_spaced(kMode) ? a.seed_nroll : 0u;
 	const unsigned char* const rollT = gapT + ngp * 256u; // toggle tables of pairs 1 .. nroll-1 (pair 0: tabG)
 	const uint32_t* const dcw = reinterpret_cast<const uint32_t*>(rollT + (nroll > 1u ? nroll - 1u : 0u) * 256u); // [ngp] d | d' << 16
 	// Sample 0 of ntComp wants the top sBits+1 bits of min(fh,rh) to be 0..01.  Both strands are carried with
 	// that one bit flipped (folded into the step table: x' = x ^ c rolls with the term t ^ c ^ rotl(c)), so the
 	// test becomes min(f',r') < c: a superset (extra: one strand 0..01 while the other is 0..00, p = 2^-2(sBits+1)),
 	// made exact by the resolve stage, which re-derives everything from the bases.  Sample 1 looks at the bits
-	// above c only and is unaffected.  nthll compares against a moving threshold and runs unflipped.
-	const uint32_t flipc = kMode == 2 ? 0u : 1u << (31 - a.s_bits);
+	// above c only and is unaffected.  nthll compares against a moving threshold and runs unflipped: the threshold is a power of two >= 2
+	// (hll_threshold_kernel), so `value < thr` reads bits 31 .. 1 of the walk's word — H itself, the hash's bits 63 .. 33 — and never bit 0, the copy of H[30].
+	// One strand: both rotates keep the (H << 1) | H[30] layout (rotl31 and rotr31 of H with the copy refreshed, see kOne above), so the same compare holds for
+	// the forward and the reverse walk; canonical: min(f, r) < thr is "either strand below", a superset of "the smaller 64-bit value below".
+	const uint32_t flipc = mode_hll(kMode) ? 0u : 1u << (31 - a.s_bits);
 	// (one strand: x' = rot(x) ^ T for both, so the flipped bit rolls with T ^ c ^ rot(c); sBits 2 .. 24 keeps c and rot(c) inside bits 30 .. 6)
 	const uint32_t flipx = flipc ^ (kOne && a.ks[0].strand == 2u ? flipc >> 1 : flipc << 1);
 	uint32_t rot_sh = kOne && a.ks[0].strand == 2u ? 2u : 31u;
@@ -231,7 +238,7 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 	// index of every sampled k-mer to its private log regions gwave, gwave + W, ... (W = waves of this launch) with one
 	// coalesced store per resolve round; ntc_apply.hip adds them to the sketch later (counting commutes).  A wave
 	// that runs out of regions falls back to the direct atomic, which is exact as well.
-	const bool use_log = kMode != 2 && a.log_regions != 0 && (a.log_mode == nullptr || __builtin_amdgcn_readfirstlane(*a.log_mode) == 0u);
+	const bool use_log = !mode_hll(kMode) && a.log_regions != 0 && (a.log_mode == nullptr || __builtin_amdgcn_readfirstlane(*a.log_mode) == 0u);
 	const uint32_t log_w = gridDim.x * wpb;
 	uint32_t lreg = gwave, lfill = 0;
 	if (use_log && lreg < a.log_regions) lfill = __builtin_amdgcn_readfirstlane(a.log_fill[lreg]);
@@ -253,7 +260,7 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 			if (a.sk_dirty) *a.sk_dirty = 1u; // (out of log regions: the sketch is no longer what the last reset / apply left, ntc_apply.hip count_kernel)
 		}
 	};
-	if (kMode != 2 && !use_log && a.sk_dirty != nullptr && lane == 0) *a.sk_dirty = 1u; // direct atomics from here on (the device mode word, or no regions)
+	if (!mode_hll(kMode) && !use_log && a.sk_dirty != nullptr && lane == 0) *a.sk_dirty = 1u; // direct atomics from here on (the device mode word, or no regions)
 	uint64_t f1_acc[kMaxFusedK] = {0, 0, 0, 0};
 	uint32_t shb = (0u - k) & 3u; // byte phase of the outgoing-base stream
 
@@ -389,7 +396,7 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 		// RAGGED (lanes end at different steps, e.g. the last partial batch or a ragged host batch)
 		constexpr int CLEAN = 0, DIRTY = 1, RAGGED = 2;
 		// (a mask with more toggle pairs than the rolling form takes walks every wave as RAGGED: the closed-form XOR-out)
-		const int wclass = minq != maxq || (kMode == 1 && nroll == 0u) ? RAGGED : (wave_dirty ? DIRTY : CLEAN);
+		const int wclass = minq != maxq || (mode_spaced(kMode) && nroll == 0u) ? RAGGED : (wave_dirty ? DIRTY : CLEAN);
 
 		// The walk starts from the H halves of the hash of k virtual 'A's and feeds 'A' as the outgoing
 		// base of the first k steps, so ONE step body serves window filling and steady state.
@@ -491,7 +498,7 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 						a.dump[row * a.dump_win + win] = ((uint64_t)hi << 32) | lo;
 						atomicOr(a.dump_valid + row * ((a.dump_win + 31u) >> 5) + (win >> 5), 1u << (win & 31u));
 					}
-				} else if constexpr (kMode == 2) {
+				} else if constexpr (mode_hll(kMode)) {
 					// nthll's ntComp (nthll.cpp:92-97): bucket = low bits, value = leading zeros of the rest
 					const uint32_t bmask = (1u << a.hll_bits) - 1u;
 					const uint32_t lo_rest = lo & ~bmask;
@@ -508,7 +515,7 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 					key = key_base + rel;
 				}
 			}
-			if constexpr (kMode != 2 && !kDump) {
+			if constexpr (!mode_hll(kMode) && !kDump) {
 				if (use_log)
 					log_emit(hit, key); // the increment itself happens later (ntc_apply.hip)
 				else if (hit)
@@ -858,7 +865,14 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 				f1_wave += __builtin_amdgcn_readfirstlane(v);
 			}
 		};
-		if constexpr (kMode == 2) {
+		if constexpr (kMode == 3) {
+			if (wclass == CLEAN)
+				walk(std::integral_constant<int, CLEAN>{}, std::true_type{}, std::true_type{});
+			else if (wclass == DIRTY)
+				walk(std::integral_constant<int, DIRTY>{}, std::true_type{}, std::true_type{});
+			else
+				walk(std::integral_constant<int, RAGGED>{}, std::true_type{}, std::true_type{});
+		} else if constexpr (kMode == 2) {
 			if (wclass == CLEAN)
 				walk(std::integral_constant<int, CLEAN>{}, std::false_type{}, std::true_type{});
 			else if (wclass == DIRTY)
@@ -902,9 +916,14 @@ hipError_t launch_sketch_hf(const HfArgs& a, unsigned grid, unsigned waves_per_b
 	const dim3 g(grid), b(64u * waves_per_block);
 	const bool deep = sketch_hf_deep_prefetch(a.stride) && waves_per_block <= 12; // plain k-mer mode only
 	if (a.tiled != 0u && (a.dump != nullptr || a.gap != 0 || a.hll_bits != 0)) return hipErrorInvalidValue; // (tiled staging: plain k-mer mode only)
-	if (a.ks[0].strand > 2u || (a.ks[0].strand != 0u && (a.tiled != 0u || a.hll_bits != 0))) return hipErrorInvalidValue; // (one strand: row slots; nthll is canonical)
-	if (a.ks[0].strand != 0u) { // the one-strand copies of the seven instantiations a strand engine can reach (its tiled batches are re-laid out as row slots)
-		if (a.dump != nullptr && a.gap != 0)
+	if (a.ks[0].strand > 2u || (a.ks[0].strand != 0u && a.tiled != 0u)) return hipErrorInvalidValue; // (one strand: row slots)
+	if (a.hll_bits != 0 && (a.n_k != 1 || a.dump != nullptr || a.hll_thr == nullptr)) return hipErrorInvalidValue; // (nthll: one plane per launch)
+	if (a.ks[0].strand != 0u) { // the one-strand copies of the instantiations a strand engine can reach (its tiled batches are re-laid out as row slots)
+		if (a.hll_bits != 0 && a.gap != 0)
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 3, 10, false, false, true>), g, b, smem, st, a);
+		else if (a.hll_bits != 0)
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 2, 10, false, false, true>), g, b, smem, st, a);
+		else if (a.dump != nullptr && a.gap != 0)
 			hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, true, false, true>), g, b, smem, st, a);
 		else if (a.dump != nullptr)
 			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, true, false, true>), g, b, smem, st, a);
@@ -924,6 +943,8 @@ hipError_t launch_sketch_hf(const HfArgs& a, unsigned grid, unsigned waves_per_b
 		hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, true>), g, b, smem, st, a);
 	else if (a.dump != nullptr)
 		hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, true>), g, b, smem, st, a);
+	else if (a.hll_bits != 0 && a.gap != 0)
+		hipLaunchKernelGGL((sketch_hf_kernel<false, 3, 10>), g, b, smem, st, a);
 	else if (a.hll_bits != 0)
 		hipLaunchKernelGGL((sketch_hf_kernel<false, 2, 10>), g, b, smem, st, a);
 	else if (a.gap != 0)
@@ -984,7 +1005,10 @@ hipError_t set_sketch_hf_smem_limit(size_t smem)
 		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, false, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 10, false, false, true>),
 		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 16, false, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 16, false, false, true>),
 		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, false, false, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, true, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, true, false, true>) };
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, true, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, true, false, true>),
+		              // nthll under a spaced seed, nthll of one strand
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 3, 10>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 2, 10, false, false, true>),
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 3, 10, false, false, true>) };
 	for (const void* f : fns) {
 		const hipError_t rc = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 		if (rc != hipSuccess) return rc;

@@ -254,27 +254,63 @@ class Engine:
         return ms.value, n.value
 
 
-class HllEngine(Engine):
-    """nthll: uint8 M[1<<n_bits] of max leading-zero runs (nthll.cpp:92-105,212-243)"""
+_STRAND_INDEX = {"canonical": 0, "forward": 1, "reverse": 2}
 
-    def __init__(self, k, n_bits=16, device=0, stream=None):
+
+class HllEngine(Engine):
+    """nthll: per plane a uint8 M[1<<n_bits] of max leading-zero runs (nthll.cpp:92-105,212-243).  k: an int (one plane; finish() -> (regs 1-D, f1 int))
+    or a list of k (finish() -> (regs [n_planes, 1<<n_bits], f1 uint64[n_planes])); from_seeds: spaced seeds given as masks; strand as for Engine()
+    (include/ntcard_hip.h: ntc_hll_create_ex)"""
+
+    def __init__(self, k, n_bits=16, device=0, stream=None, strand="canonical"):
+        single = not isinstance(k, (list, tuple, np.ndarray))
+        self._setup([int(k)] if single else [int(x) for x in k], None, n_bits, device, stream, strand, single)
+
+    @classmethod
+    def from_seeds(cls, masks, n_bits=16, device=0, stream=None, strand="canonical"):
+        self = cls.__new__(cls)
+        self._h = None
+        seeds = [s.decode() if isinstance(s, bytes) else str(s) for s in masks]
+        self._setup([len(s) for s in seeds], seeds, n_bits, device, stream, strand, False)
+        return self
+
+    def _setup(self, klist, seeds, n_bits, device, stream, strand, single):
+        self._h = None
+        flags = _strand_flags(0, strand)  # (checked before the library is asked for a device)
         self._lib = _abi.lib()
-        self.klist, self.gap, self.n_bits, self.device = [int(k)], 0, int(n_bits), int(device)
+        self.klist, self.seeds, self.gap, self.n_bits, self.device = klist, seeds, 0, int(n_bits), int(device)
+        self.strand = "canonical" if strand is None else strand
+        self._single = single
+        cfg = _abi.NtcHllConfig()
+        if seeds is None:
+            self._karr = (C.c_uint32 * len(klist))(*klist)
+            cfg.n_k, cfg.k = len(klist), C.cast(self._karr, C.POINTER(C.c_uint32))
+        else:
+            self._sarr = (C.c_char_p * len(seeds))(*[s.encode() for s in seeds])
+            cfg.n_seeds, cfg.seeds = len(seeds), C.cast(self._sarr, C.POINTER(C.c_char_p))
+        cfg.n_bits, cfg.device, cfg.flags = self.n_bits, self.device, flags
+        cfg.stream = C.c_void_p(stream) if stream else None
         h = C.c_void_p()
-        check(self._lib.ntc_hll_create(int(k), int(n_bits), int(device), C.c_void_p(stream) if stream else None, C.byref(h)))
+        check(self._lib.ntc_hll_create_ex(C.byref(cfg), C.byref(h)))
         self._h = h
 
     def finish(self):
-        regs = np.zeros(1 << self.n_bits, dtype=np.uint8)
-        f1 = np.zeros(1, dtype=np.uint64)
+        n = len(self.klist)
+        regs = np.zeros((n, 1 << self.n_bits), dtype=np.uint8)
+        f1 = np.zeros(n, dtype=np.uint64)
         check(self._lib.ntc_hll_finish(self._h, _np_ptr(regs), _np_ptr(f1)))
-        return regs, int(f1[0])
+        if self._single:
+            return regs[0], int(f1[0])
+        return regs, f1
 
 
-def hll_estimate(regs, n_bits=16):
+def hll_estimate(regs, n_bits=16, strand="canonical"):
+    """nthll's estimate of one plane's registers; strand: the engine's (a one-strand value is uniform, so its alpha is not halved)"""
+    if not isinstance(strand, str) or strand not in _STRAND_INDEX:
+        raise ValueError(f"strand must be 'canonical', 'forward' or 'reverse', not {strand!r}")
     est = C.c_double()
     r = np.ascontiguousarray(regs, dtype=np.uint8)
-    check(_abi.lib().ntc_hll_estimate(_np_ptr(r), int(n_bits), C.byref(est)))
+    check(_abi.lib().ntc_hll_estimate_strand(_np_ptr(r), int(n_bits), _STRAND_INDEX[strand], C.byref(est)))
     return est.value
 
 
