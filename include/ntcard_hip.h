@@ -210,13 +210,19 @@ int ntc_submit_tiled_bins_device(ntc_engine *e, uint32_t n_bins, const void *con
  * n_seqs + 1 non-decreasing entries.  Stream-ordered: d_bases may be reused as soon as the stream has passed the call, under NTC_FLAG_DEFER_REDO too (the
  * engine counts from scratch of its own, so this call never defers); offsets is free on return.  The kernels read d_bases in aligned 4-byte words, and only
  * words that hold at least one byte of a sequence.
- * On an engine with ONE plane that is the tiled kernels' (plain k = 12 .. 32 or the two tiled -g seeds, canonical, sBits >= 7) every sequence of n >= piece_len
- * bytes is cut on the device into ntc_long_plan()'s full pieces [j S, j S + piece_len), S = piece_len - (k - 1) — an equal-length tiled batch, counted by
- * K1h + K1f at their rate, each window of k bases in exactly one piece — and its remainder, like every shorter sequence, is gathered into row slots for the
- * general kernel.  piece_len: 0 = the engine's choice (1008), or a multiple of 16 with k + 15 <= piece_len <= 65520.  The work goes in rounds of at most
- * 1 GiB of engine scratch, whatever the input's size; the tables cost 8 B per piece.
- * On every other engine (k lists, k > 32, other seeds, a strand, nthll, sBits < 7, NTC_FLAG_LANE_KERNEL, NTC_FLAG_SIMPLE_KERNEL) every sequence is gathered
- * whole: exactly ntc_submit's results — with NTC_FLAG_REQUIRE_TILED the call fails with NTC_ERR_ARG instead and counts nothing.
+ * An engine QUALIFIES when every plane is the tiled kernels' (plain k = 12 .. 32 or the two tiled -g seeds, canonical, sBits >= 7) and it has either one
+ * plane or a list of plain k with kmax - kmin <= 15.  Every sequence of n >= piece_len bytes is then cut on the device into the full pieces
+ * [j S, j S + piece_len) of ntc_long_plan(kmax, ..), S = piece_len - (kmax - 1): ONE cut, with the overlap of the largest k, for the whole list — an
+ * equal-length tiled batch counted by K1h + K1f at their rate, once per k.  A k of the list owns the windows that start in a piece's first S bytes: the
+ * windows of a read of piece_len - (kmax - k) bases, which is how the tiled kernels are launched for it over the same tiles (the limit of 15 keeps that
+ * length inside the piece's last 16-byte chunk).  So each window of each k lies in exactly one piece or in the remainder [m S, n).  The remainder is gathered
+ * into row slots for the general kernel iff it holds a window of kmin (n - m S >= kmin), like every sequence shorter than piece_len.  piece_len: 0 = the
+ * engine's choice (1008), or a multiple of 16 with kmax + 15 <= piece_len <= 65520.  The work goes in rounds of at most 1 GiB of engine scratch, whatever the
+ * input's size.  The host builds and sends 16 B per sequence that holds a full piece (its offset and the index of its first piece) and 16 B per row slot:
+ * the pieces' offsets are derived on the device.
+ * On every other engine (a list wider than 15 or with a k outside 12 .. 32, k > 32, other seeds, a strand, nthll, sBits < 7, NTC_FLAG_LANE_KERNEL,
+ * NTC_FLAG_SIMPLE_KERNEL) every sequence is gathered whole: exactly ntc_submit's results, ntc_long_stats stays (0, 0) — with NTC_FLAG_REQUIRE_TILED the call
+ * fails with NTC_ERR_ARG instead and counts nothing.
  * NTC_ERR_ARG for null pointers, a bad piece_len or offsets that decrease, checked before a device is looked for.
  * ntc_submit / ntc_submit_spans take the same path for the long sequences of a host batch on such an engine: the sequences of two or more full pieces
  * (piece_len 1008) are copied raw into staging and cut on the device once together they hold 32768 full pieces (about 32 MB; below that row slots are as fast
@@ -224,9 +230,11 @@ int ntc_submit_tiled_bins_device(ntc_engine *e, uint32_t n_bins, const void *con
 int ntc_submit_long_device(ntc_engine *e, const void *d_bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t piece_len);
 
 /* The cut ntc_submit_long_device makes of ONE sequence of len bytes (a pure host function; ntRead's window loop, ntcard.cpp:147-158,173-208, split
- * into ranges): *pieces = m full pieces [j S, j S + piece_len), j < m, S = piece_len - (k - 1); *rem_start = m S: the remainder [m S, len) — the whole
- * sequence when len < piece_len (m = 0), else k - 1 .. piece_len - 1 bytes — holds a window iff len - m S >= k.  The windows of the pieces and of the
- * remainder are the sequence's windows, each once.  NTC_ERR_ARG unless piece_len is a multiple of 16 with k + 15 <= piece_len <= 65520. */
+ * into ranges); k: the engine's k, for a list its LARGEST.  *pieces = m full pieces [j S, j S + piece_len), j < m, S = piece_len - (k - 1); *rem_start = m S:
+ * the remainder [m S, len) — the whole sequence when len < piece_len (m = 0), else k - 1 .. piece_len - 1 bytes — holds a window of a k' <= k iff
+ * len - m S >= k' (the engine counts it iff that holds for the smallest k of its list).  For every k' of a list within k - 15 .. k, the windows that start in
+ * the first S bytes of the pieces and the windows of the remainder are the sequence's windows of k' bases, each once.  NTC_ERR_ARG unless piece_len is a
+ * multiple of 16 with k + 15 <= piece_len <= 65520. */
 int ntc_long_plan(uint32_t k, uint32_t piece_len, uint64_t len, uint64_t *pieces, uint64_t *rem_start);
 
 /* cumulative since create / reset: the full pieces ntc_submit_long_device (and the host path behind NTC_LONG_MIN) has cut for the tiled kernels and the

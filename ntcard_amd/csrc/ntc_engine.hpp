@@ -114,6 +114,10 @@ struct TiledSeg {
 	uint64_t n_reads;
 	uint32_t read_len;
 	const uint32_t* d_tails;
+	// != 0: the reads are pieces of long sequences, cut with the overlap of this k — the largest of the list (ntc_submit.hip).  A smaller k owns the
+	// windows that start in the piece's first read_len - (cut_k - 1) bytes: those of a read of len_for(k) bases in the same chunks
+	uint32_t cut_k = 0;
+	uint32_t len_for(uint32_t k) const { return cut_k ? read_len - (cut_k - k) : read_len; }
 };
 
 // K1 (sketch_hf_kernel) launch shape.  Every wave parks its 64 slots in LDS and the block shares

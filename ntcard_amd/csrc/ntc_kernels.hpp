@@ -155,9 +155,15 @@ hipError_t launch_untile(const unsigned char* tiles, unsigned char* slots, uint6
 // a ragged tiled batch for K1 (round 6): meta[i] = len | len << 16 of read i from tails[tile][16] (the reads of a tile are sorted longest first)
 hipError_t launch_tails_to_meta(const uint32_t* tails, uint64_t n_reads, uint32_t n_chunks, uint32_t* meta, hipStream_t st);
 // ---- long sequences (ntc_long.hip; ntc_submit_long_device) ----
-// pieces -> tiles: piece p = the piece_len (= 16 x chunks) source bytes from src + piece_off[p], of any alignment, becomes "read p" of an equal-length tiled
-// batch (ntc_tiled_bytes(n_pieces, piece_len) bytes at `tiles`; the slots behind the last piece stay unwritten)
-hipError_t launch_cut_tiles(const unsigned char* src, const uint64_t* piece_off, uint64_t n_pieces, uint32_t piece_len, unsigned char* tiles, hipStream_t st);
+// pieces -> tiles: the call's sequences that hold a full piece are seqs[0 .. n_seqs), in piece order, and seqs[n_seqs] = {0, the call's pieces} closes the
+// table; piece p of the call = the piece_len (= 16 x chunks) source bytes from src + seqs[s].src + (p - seqs[s].first) * step, of any alignment, for the s
+// with seqs[s].first <= p < seqs[s + 1].first.  Pieces first_piece .. first_piece + n_pieces become "reads" 0 .. n_pieces of an equal-length tiled batch
+// (ntc_tiled_bytes(n_pieces, piece_len) bytes at `tiles`; the slots behind the last piece stay unwritten)
+struct LongSeq {
+	uint64_t src, first;
+};
+hipError_t launch_cut_tiles(const unsigned char* src, const LongSeq* seqs, uint32_t n_seqs, uint64_t first_piece, uint64_t n_pieces, uint32_t step,
+                            uint32_t piece_len, unsigned char* tiles, hipStream_t st);
 // spans -> row slots: slot i = `bytes` source bytes from src + spans[i].src, then 'A' up to the stride (a multiple of 4; slots 4-byte aligned);
 // meta[i] = bytes | limit << 16 (HashArgs::meta)
 struct LongSpan {

@@ -551,8 +551,8 @@ bool split_tiled(ntc_engine* e, const Segs& segs, uint32_t max_segs, bool k1f_no
 				continue;
 			}
 			const uint64_t head_tiles = n_tiles / 2, head_reads = head_tiles * ntc::kTileReads;
-			const TiledSeg head{sg.d_tiles, head_reads, sg.read_len, sg.d_tails};
-			const TiledSeg rest{sg.d_tiles + ntc_tiled_bytes(head_reads, sg.read_len), sg.n_reads - head_reads, sg.read_len, sg.d_tails ? sg.d_tails + head_tiles * 16 : nullptr};
+			const TiledSeg head{sg.d_tiles, head_reads, sg.read_len, sg.d_tails, sg.cut_k};
+			const TiledSeg rest{sg.d_tiles + ntc_tiled_bytes(head_reads, sg.read_len), sg.n_reads - head_reads, sg.read_len, sg.d_tails ? sg.d_tails + head_tiles * 16 : nullptr, sg.cut_k};
 			rc = run_tiled_segs(e, &head, 1, 1, k1f_now);
 			if (!rc) rc = run_tiled_segs(e, &rest, 1, 1, k1f_now);
 		}
@@ -570,19 +570,20 @@ bool probe_head_tiled(ntc_engine* e, const Segs& segs, bool k1f_now, int& rc)
 	const TiledSeg& sg = segs[0];
 	double per_read = 0.0;
 	for (uint32_t k : e->klist)
-		per_read += sampled_per_read(sg.read_len, k, e->s_bits);
+		per_read += sampled_per_read(sg.len_for(k), k, e->s_bits);
 	if (!(per_read > 0.0)) return false;
 	const uint64_t head = probe_head_reads(per_read);
 	if (sg.n_reads < 4 * head) return false;
-	const TiledSeg first{sg.d_tiles, head, sg.read_len, nullptr};
-	const TiledSeg rest{sg.d_tiles + ntc_tiled_bytes(head, sg.read_len), sg.n_reads - head, sg.read_len, nullptr};
+	const TiledSeg first{sg.d_tiles, head, sg.read_len, nullptr, sg.cut_k};
+	const TiledSeg rest{sg.d_tiles + ntc_tiled_bytes(head, sg.read_len), sg.n_reads - head, sg.read_len, nullptr, sg.cut_k};
 	rc = run_tiled_segs(e, &first, 1, 1, k1f_now);
 	if (!rc) rc = run_tiled_segs(e, &rest, 1, 1, k1f_now);
 	return true;
 }
 
 // One K1h k of a call: the batches with a window of this k (none in a shorter read, ntHashIterator.hpp:61-64) and their share of the launch, planned ONCE —
-// the hand-over sets are sized from it and the launch fills in the rest of hs
+// the hand-over sets are sized from it and the launch fills in the rest of hs.  hs[i].read_len is the batch's length FOR THIS k (TiledSeg::len_for: pieces of
+// long sequences under a list are trimmed, their chunks are not); blocks, nb_magic, the hand-over arrays and K1f's arguments all follow from it
 struct K1hPlan {
 	size_t ki;
 	uint32_t na;
@@ -608,16 +609,16 @@ void plan_k1h(const ntc_engine* e, const Segs& segs, unsigned cus, std::vector<K
 		p.na = 0;
 		std::memset(p.hs, 0, sizeof p.hs);
 		for (const auto& sg : segs)
-			if (sg.read_len >= k) {
+			if (sg.len_for(k) >= k) {
 				p.hs[p.na].n_tiles = (uint32_t)((sg.n_reads + ntc::kTileReads - 1) / ntc::kTileReads);
-				p.hs[p.na].read_len = sg.read_len;
+				p.hs[p.na].read_len = sg.len_for(k);
 				p.act[p.na++] = &sg;
 			}
 		if (p.na == 0) continue;
 		ntc::K1hArgs shares[ntc::kK1hSegs];
 		(void)ntc::plan_sketch_k1h(p.hs, p.na, k, cus, shares);
 		for (uint32_t i = 0; i < p.na; ++i) {
-			const uint32_t n_chunks = (p.hs[i].read_len + 15u) / 16u, nb = ntc::sketch_k1h_blocks(k, p.hs[i].read_len);
+			const uint32_t n_chunks = (p.act[i]->read_len + 15u) / 16u, nb = ntc::sketch_k1h_blocks(k, p.hs[i].read_len);
 			need.dirty = std::max(need.dirty, (size_t)p.hs[i].n_tiles * n_chunks * 256);
 			need.tie = std::max(need.tie, (size_t)p.hs[i].n_tiles * nb * 256);
 			need.sus_cap = std::max(need.sus_cap, k1h_suspects_per_wave(shares[i].blocks_per_wave, e->s_bits, need.max_waves));
@@ -760,11 +761,13 @@ int run_k1_share(ntc_engine* e, const Segs& segs)
 int run_tiled_segs(ntc_engine* e, const TiledSeg* segs_in, uint32_t n_in, uint64_t n_submits, bool k1f_now)
 {
 	Segs segs;
-	bool any_tails = false;
+	bool any_tails = false, any_trim = false; // any_trim: pieces that some k of the list takes shorter than they are — only K1h + K1f count those
 	for (uint32_t i = 0; i < n_in; ++i)
 		if (segs_in[i].n_reads) {
 			segs.push_back(segs_in[i]);
 			any_tails |= segs_in[i].d_tails != nullptr;
+			for (uint32_t k : e->klist)
+				any_trim |= segs_in[i].len_for(k) != segs_in[i].read_len;
 		}
 	if (segs.empty()) return 0;
 	int rc = 0;
@@ -782,7 +785,7 @@ int run_tiled_segs(ntc_engine* e, const TiledSeg* segs_in, uint32_t n_in, uint64
 		double est = 0;
 		for (const K1hPlan& p : plans) {
 			for (uint32_t i = 0; i < p.na; ++i)
-				est += (double)p.act[i]->n_reads * sampled_per_read(p.act[i]->read_len, e->klist[p.ki], e->s_bits);
+				est += (double)p.act[i]->n_reads * sampled_per_read(p.hs[i].read_len, e->klist[p.ki], e->s_bits);
 			est += 64.0 * 4096;
 		}
 		if ((rc = book_log(e, est))) return rc;
@@ -803,7 +806,7 @@ int run_tiled_segs(ntc_engine* e, const TiledSeg* segs_in, uint32_t n_in, uint64
 		if (int rc_sets = ensure_sets(e, p.na, need, defer, no_room)) {
 			// no memory for K1h's hand-over arrays (8 sets with NTC_FLAG_DEFER_REDO: up to ~0.5 GB each per 10 M reads): the
 			// batches are K1's, unless the caller insists on the tiled kernels or part of the k list has been launched already
-			if (!no_room || e->ts_required || &p != &plans.front() || any_tails) return rc_sets;
+			if (!no_room || e->ts_required || &p != &plans.front() || any_tails || any_trim) return rc_sets;
 			if ((rc = close_run(e))) return rc;
 			for (const auto& sg : segs)
 				if ((rc = run_tiled_as_rows(e, sg))) return rc;

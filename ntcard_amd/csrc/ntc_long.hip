@@ -24,20 +24,54 @@ __device__ __forceinline__ uint32_t load_unaligned_u32(uintptr_t addr, bool only
 }
 
 // Pieces -> tiles.  A workgroup takes 64 consecutive pieces (one lane group of a tile: 2048 % 64 == 0) x a run of up to kCutRun chunks.
+//   where: piece p of the call belongs to the sequence s with seqs[s].first <= p < seqs[s + 1].first and starts at seqs[s].src + (p - seqs[s].first) * step.
+//        Wave 0 finds the sequence of the workgroup's first piece — a 64-way search of the table, one probe per lane and step: three steps for 2^18
+//        sequences —, loads the 64 entries behind it (every entry holds a piece, so the workgroup's pieces lie in these) and every lane searches them, in
+//        LDS, for its own piece.  A round of a call passes the call's whole table and its first piece: it may begin and end in the middle of a sequence
 //   in:  wave w reads the run of pieces 16 w .. 16 w + 15, one piece per step: 64 lanes x 4 B = the run's 256 contiguous bytes
 //   out: per chunk one line group of the tile — 64 lanes x 16 B = 1 KiB contiguous — from LDS rows of kCutRow bytes
 // Slots behind the last piece (the rest of the last tile) stay unwritten: the tiled kernels ignore them.
-__global__ __launch_bounds__(256) void cut_tiles_kernel(const unsigned char* __restrict__ src, const uint64_t* __restrict__ piece_off, uint64_t n_pieces,
-                                                        uint32_t n_chunks, uint32_t n_runs, unsigned char* __restrict__ tiles)
+__global__ __launch_bounds__(256) void cut_tiles_kernel(const unsigned char* __restrict__ src, const LongSeq* __restrict__ seqs, uint32_t n_seqs, uint64_t first_piece,
+                                                        uint64_t n_pieces, uint32_t step, uint32_t n_chunks, uint32_t n_runs, unsigned char* __restrict__ tiles)
 {
 	__shared__ __attribute__((aligned(16))) unsigned char rows_lds[64 * kCutRow];
-	const uint64_t p0 = (uint64_t)(blockIdx.x / n_runs) * 64u;
+	__shared__ uint64_t win_src[65], win_first[65]; // the table from the first piece's sequence on
+	__shared__ uint64_t off_lds[64];  // source offset of the workgroup's pieces
+	const uint64_t p0 = (uint64_t)(blockIdx.x / n_runs) * 64u; // (within the round)
 	const uint32_t c0 = (blockIdx.x % n_runs) * kCutRun;
 	const uint32_t nc = n_chunks - c0 < kCutRun ? n_chunks - c0 : kCutRun; // chunks of this run
 	const uint32_t nb = nc * 16u;                                           // bytes per piece of this run
 	const uint32_t n_rows = n_pieces - p0 < 64u ? (uint32_t)(n_pieces - p0) : 64u;
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	if (wave == 0) {
+		const uint64_t g0 = first_piece + p0; // the first piece, in the call's numbering
+		uint32_t lo = 0, hi = n_seqs;          // seqs[lo].first <= g0 < seqs[hi].first (seqs[0].first == 0; the sentinel holds the call's pieces)
+		while (hi - lo > 1u) {
+			const uint32_t stride = (hi - lo + 63u) / 64u, i = lo + lane * stride;
+			const uint32_t n_le = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(i < hi && seqs[i].first <= g0)); // (monotone: a prefix of the lanes; lane 0 is in it)
+			hi = __builtin_amdgcn_readfirstlane(lo + n_le * stride < hi ? lo + n_le * stride : hi);
+			lo = __builtin_amdgcn_readfirstlane(lo + (n_le - 1u) * stride);
+		}
+		// (entries lo .. lo + 64; behind the sentinel: first = ~0)
+		uint64_t e_src = 0, e_first = ~0ull, l_src = 0, l_first = ~0ull;
+		if (lo + lane <= n_seqs) e_src = seqs[lo + lane].src, e_first = seqs[lo + lane].first;
+		if (lane == 0 && lo + 64u <= n_seqs) l_src = seqs[lo + 64u].src, l_first = seqs[lo + 64u].first;
+		win_src[lane] = e_src, win_first[lane] = e_first;
+		if (lane == 0) win_src[64] = l_src, win_first[64] = l_first;
+	}
+	__syncthreads();
+	if (wave == 0 && lane < n_rows) {
+		const uint64_t g = first_piece + p0 + lane;
+		uint32_t a = 0, b = lane + 1u; // win_first[a] <= g < win_first[b]: every sequence of the table holds a piece, so piece lane is not behind entry lane
+		while (b - a > 1u) {
+			const uint32_t mid = (a + b) / 2u;
+			if (win_first[mid] <= g) a = mid;
+			else b = mid;
+		}
+		off_lds[lane] = win_src[a] + (g - win_first[a]) * step;
+	}
+	__syncthreads();
 	const bool mine = 4u * lane < nb;
 	uint32_t v[16];
 #pragma unroll
@@ -46,7 +80,7 @@ __global__ __launch_bounds__(256) void cut_tiles_kernel(const unsigned char* __r
 		v[i] = 0;
 		if (row < n_rows && mine) {
 			// (the last dword of a piece that ends with the source: its second aligned word holds a source byte whenever the address is unaligned)
-			v[i] = load_unaligned_u32(reinterpret_cast<uintptr_t>(src) + piece_off[p0 + row] + 16u * (uint64_t)c0 + 4u * lane, false);
+			v[i] = load_unaligned_u32(reinterpret_cast<uintptr_t>(src) + off_lds[row] + 16u * (uint64_t)c0 + 4u * lane, false);
 		}
 	}
 #pragma unroll
@@ -90,13 +124,15 @@ __global__ __launch_bounds__(256) void gather_slots_kernel(const unsigned char* 
 
 } // namespace
 
-hipError_t launch_cut_tiles(const unsigned char* src, const uint64_t* piece_off, uint64_t n_pieces, uint32_t piece_len, unsigned char* tiles, hipStream_t st)
+hipError_t launch_cut_tiles(const unsigned char* src, const LongSeq* seqs, uint32_t n_seqs, uint64_t first_piece, uint64_t n_pieces, uint32_t step,
+                            uint32_t piece_len, unsigned char* tiles, hipStream_t st)
 {
 	if (n_pieces == 0) return hipSuccess;
+	if (n_seqs == 0) return hipErrorInvalidValue;
 	const uint32_t n_chunks = piece_len / 16u, n_runs = (n_chunks + kCutRun - 1u) / kCutRun;
 	const uint64_t blocks = ((n_pieces + 63u) / 64u) * n_runs;
 	if (blocks > 0x7fffffffull) return hipErrorInvalidValue; // (the engine cuts in rounds far below this)
-	hipLaunchKernelGGL(cut_tiles_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, piece_off, n_pieces, n_chunks, n_runs, tiles);
+	hipLaunchKernelGGL(cut_tiles_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, seqs, n_seqs, first_piece, n_pieces, step, n_chunks, n_runs, tiles);
 	return hipGetLastError();
 }
 

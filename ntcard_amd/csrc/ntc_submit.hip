@@ -231,18 +231,32 @@ template <class LenFn, class PtrFn> int submit_rows(ntc_engine* e, uint64_t n_re
 	return end_stage_use(e, sl, run_batch(e, sl.d_stage, need_meta ? sl.d_meta.get() : nullptr, n_slots, (uint32_t)p.len0, stride));
 }
 
-// ---- long sequences as pieces (include/ntcard_hip.h: ntc_submit_long_device) ----
-// A sequence of n >= L bytes is cut, ON THE DEVICE, into m = ntc_long_plan() full pieces [j S, j S + L), S = L - (k - 1): an equal-length tiled batch of
-// "reads" for K1h + K1f, which count every window of k bases of a piece — and every window of the sequence lies in exactly one piece or in the remainder
-// [m S, n).  Remainders and sequences shorter than L are gathered into row slots (the plan above) for K1.  An engine whose one plane is not K1h's
-// gathers every sequence whole: ntc_submit's results from device-resident bytes.
+// ---- long sequences as pieces (include/ntcard_hip.h: ntc_submit_long_device; DESIGN.md §4 "Long sequences") ----
+// A sequence of n >= L bytes is cut, ON THE DEVICE, into m = ntc_long_plan(kmax, ..) full pieces [j S, j S + L), S = L - (kmax - 1): an equal-length tiled
+// batch of "reads" for K1h + K1f.  Every k of the list counts the windows that START in a piece's first S bytes — those of a read of L - (kmax - k) bases
+// (TiledSeg::cut_k) — so every window of k bases lies in exactly one piece or in the remainder [m S, n).  Remainders that hold a window of kmin and sequences
+// shorter than L are gathered into row slots (the plan above) for K1.  An engine that does not qualify (long_fast) gathers every sequence whole:
+// ntc_submit's results from device-resident bytes.
 constexpr uint32_t kLongPieceDefault = 1008;   // profiles/long_seq.txt
 constexpr uint64_t kLongMinNever = ~0ull;
 constexpr uint64_t kLongMinDefault = 32768;   // host batches: full pieces from which the sequences of >= 2 pieces take this path (profiles/long_seq.txt: slower
                                                // than row slots at 8 Ki pieces, level at 16 Ki, 19 % faster at 32 Ki); NTC_LONG_MIN=0: never
 constexpr uint64_t kLongRoundBytes = 1ull << 30; // scratch of one round: a 30 GB sequence set is cut and counted 1 GiB of tiles at a time
+constexpr uint32_t kLongMaxSpread = 15;         // kmax - kmin of a list: the trimmed length of every k stays within the piece's last chunk, the ordinary
+                                                 // equal-length case of the tiled kernels (150 bp reads: 10 chunks, 10 bases in the last)
 
-bool long_fast(const ntc_engine* e) { return e->ts_all && e->klist.size() == 1; }
+uint32_t long_kmax(const ntc_engine* e) { return *std::max_element(e->klist.begin(), e->klist.end()); }
+uint32_t long_kmin(const ntc_engine* e) { return *std::min_element(e->klist.begin(), e->klist.end()); }
+
+// every plane K1h's, and one plane (the tiled -g seeds among them) or a list of plain k within kLongMaxSpread
+bool long_fast(const ntc_engine* e)
+{
+	if (!e->ts_all) return false;
+	if (e->klist.size() == 1) return true;
+	for (size_t ki = 0; ki < e->klist.size(); ++ki)
+		if (!e->plain(ki)) return false;
+	return long_kmax(e) - long_kmin(e) <= kLongMaxSpread;
+}
 
 int grow_long(ntc_engine* e, size_t need)
 {
@@ -252,10 +266,11 @@ int grow_long(ntc_engine* e, size_t need)
 	return 0;
 }
 
-// under e->mu: the rounds of one call — cut + K1h + K1f over the pieces, gather + K1 over the row slots; d_off / d_spans: the call's tables on the device
-int run_long_rounds(ntc_engine* e, const unsigned char* d_src, const uint64_t* d_off, uint64_t n_pieces, uint64_t n_cut_seqs, const ntc::LongSpan* d_spans,
+// under e->mu: the rounds of one call — cut + K1h + K1f over the pieces, gather + K1 over the row slots; d_seqs / d_spans: the call's tables on the device
+int run_long_rounds(ntc_engine* e, const unsigned char* d_src, const ntc::LongSeq* d_seqs, uint64_t n_pieces, uint64_t n_cut_seqs, const ntc::LongSpan* d_spans,
                     uint64_t n_slots, const RowPlan& rp, uint32_t L)
 {
+	const uint32_t kmax = long_kmax(e), cut_k = e->klist.size() > 1 ? kmax : 0u; // (one plane: the pieces are ordinary reads)
 	uint64_t round = kLongRoundBytes;
 	if (const char* ev = std::getenv("NTC_LONG_ROUND_BYTES")) round = std::max(1ll, std::strtoll(ev, nullptr, 10)); // tests: several rounds of a small input
 	if (n_pieces) {
@@ -266,9 +281,9 @@ int run_long_rounds(ntc_engine* e, const unsigned char* d_src, const uint64_t* d
 			if (int rc = close_run(e)) return rc;
 			Span sp;
 			if (int rc = open_span(e, sp)) return rc;
-			HIP_TRY(ntc::launch_cut_tiles(d_src, d_off + first, np, L, e->d_long, e->stream));
+			HIP_TRY(ntc::launch_cut_tiles(d_src, d_seqs, (uint32_t)n_cut_seqs, first, np, L - (kmax - 1u), L, e->d_long, e->stream));
 			if (int rc = close_span(sp, e->stream, e->long_cut_events)) return rc;
-			const TiledSeg sg{e->d_long, np, L, nullptr};
+			const TiledSeg sg{e->d_long, np, L, nullptr, cut_k};
 			if (int rc = run_tiled_segs(e, &sg, 1, 1, true)) return rc; // (the tiles are recycled by the next round: their K1f may not be deferred)
 			e->long_pieces += np;
 		}
@@ -292,59 +307,59 @@ int run_long_rounds(ntc_engine* e, const unsigned char* d_src, const uint64_t* d
 	return 0;
 }
 
-// sequence i = the len_of(i) bytes from d_src + off_of(i).  The tables (8 B per piece, 16 B per row slot) are built in the leased pair's meta buffers;
+// sequence i = the len_of(i) bytes from d_src + off_of(i).  The tables (16 B per sequence with a full piece, 16 B per row slot) are built in the leased pair's
+// meta buffers: the pieces' offsets are derived from them on the device (cut_tiles_kernel), so the host's work and the bytes it sends do not grow with the pieces.
 // h2d_bytes != 0: d_src is the pair's device side, whose first h2d_bytes the host has filled (ntc_submit's long sequences)
 template <class LenFn, class OffFn>
 int submit_long_leased(ntc_engine* e, ntc_engine::StageSlot& sl, const unsigned char* d_src, size_t h2d_bytes, uint64_t n_seqs, const LenFn& len_of,
                        const OffFn& off_of, uint32_t L)
 {
 	const bool fast = long_fast(e);
-	const uint32_t k = e->klist[0];
-	const uint64_t S = fast ? L - (k - 1u) : 1u;
+	const uint32_t kmin = long_kmin(e);
+	const uint64_t S = fast ? L - (long_kmax(e) - 1u) : 1u;
 	struct Item {
 		uint64_t src, len;
 	};
-	std::vector<Item> items; // what goes to row slots: remainders that hold a window, sequences without a full piece
-	uint64_t n_pieces = 0, n_cut_seqs = 0;
+	std::vector<Item> items;        // what goes to row slots: remainders that hold a window of kmin, sequences without a full piece
+	std::vector<ntc::LongSeq> cuts; // the sequences with a full piece
+	uint64_t n_pieces = 0;
 	for (uint64_t i = 0; i < n_seqs; ++i) {
 		const uint64_t n = len_of(i);
 		const uint64_t m = fast && n >= L ? (n - L) / S + 1u : 0u; // (ntc_long_plan)
+		if (m != 0) cuts.push_back(ntc::LongSeq{off_of(i), n_pieces});
 		n_pieces += m;
-		n_cut_seqs += m != 0;
-		if (m == 0 || n - m * S >= k) items.push_back(Item{off_of(i) + m * S, n - m * S});
+		if (m == 0 || n - m * S >= kmin) items.push_back(Item{off_of(i) + m * S, n - m * S});
 	}
+	const uint64_t n_cut_seqs = cuts.size();
+	if (n_cut_seqs >= (1ull << 31)) return fail(NTC_ERR_ARG, "ntc_submit_long_device: %llu sequences with a full piece in one call (at most 2^31 - 1)", (unsigned long long)n_cut_seqs);
+	cuts.push_back(ntc::LongSeq{0, n_pieces}); // the sentinel
 	const auto item_len = [&](uint64_t i) { return items[i].len; };
 	RowPlan rp;
 	const uint64_t n_slots = !items.empty() && plan_rows(e, items.size(), item_len, rp) ? rp.n_slots : 0;
 	if (n_pieces == 0 && n_slots == 0) return 0;
-	const size_t tab_bytes = (size_t)n_pieces * 8 + (size_t)n_slots * sizeof(ntc::LongSpan);
+	const size_t seq_bytes = n_pieces ? cuts.size() * sizeof(ntc::LongSeq) : 0, tab_bytes = seq_bytes + (size_t)n_slots * sizeof(ntc::LongSpan);
 	if (!(sl.h_meta.reserve(tab_bytes, sl.h_meta.cap * 2) && sl.d_meta.reserve(tab_bytes, sl.d_meta.cap * 2)))
-		return fail(NTC_ERR_MEMORY, "ntc_submit_long_device: cannot allocate %zu B of piece and slot tables", tab_bytes);
-	uint64_t* h_off = reinterpret_cast<uint64_t*>(sl.h_meta.get());
-	ntc::LongSpan* h_spans = reinterpret_cast<ntc::LongSpan*>(h_off + n_pieces);
-	uint64_t q = 0;
-	for (uint64_t i = 0; i < n_seqs && n_pieces; ++i) {
-		const uint64_t n = len_of(i), o = off_of(i);
-		if (n < L) continue;
-		for (uint64_t j = 0, m = (n - L) / S + 1u; j < m; ++j)
-			h_off[q++] = o + j * S;
-	}
+		return fail(NTC_ERR_MEMORY, "ntc_submit_long_device: cannot allocate %zu B of sequence and slot tables", tab_bytes);
+	unsigned char* h_tab = reinterpret_cast<unsigned char*>(sl.h_meta.get());
+	if (seq_bytes) std::memcpy(h_tab, cuts.data(), seq_bytes);
+	ntc::LongSpan* h_spans = reinterpret_cast<ntc::LongSpan*>(h_tab + seq_bytes);
 	uint64_t slot = 0;
 	if (n_slots)
 		(void)emit_rows(rp, items.size(), item_len, [&](uint64_t i, uint64_t start, uint64_t nbytes, uint64_t limit) {
 			h_spans[slot++] = ntc::LongSpan{items[i].src + start, (uint32_t)nbytes, (uint32_t)limit};
 			return 0;
 		});
-	if (q != n_pieces || slot != n_slots) return fail(NTC_ERR_STATE, "ntc_submit_long_device: internal plan mismatch");
+	if (slot != n_slots) return fail(NTC_ERR_STATE, "ntc_submit_long_device: internal plan mismatch");
 	std::lock_guard<std::mutex> lk(e->mu);
 	if ((h2d_bytes && hipMemcpyAsync(sl.d_stage, sl.h_stage, h2d_bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess) ||
 	    hipMemcpyAsync(sl.d_meta, sl.h_meta, tab_bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess)
 		return stage_copy_failed(e);
-	const uint64_t* d_off = reinterpret_cast<const uint64_t*>(sl.d_meta.get());
-	return end_stage_use(e, sl, run_long_rounds(e, d_src, d_off, n_pieces, n_cut_seqs, reinterpret_cast<const ntc::LongSpan*>(d_off + n_pieces), n_slots, rp, L));
+	const unsigned char* d_tab = reinterpret_cast<const unsigned char*>(sl.d_meta.get());
+	return end_stage_use(e, sl, run_long_rounds(e, d_src, reinterpret_cast<const ntc::LongSeq*>(d_tab), n_pieces, n_cut_seqs,
+	                                            reinterpret_cast<const ntc::LongSpan*>(d_tab + seq_bytes), n_slots, rp, L));
 }
 
-// what submit_impl leaves to row slots.  On an engine whose one plane is K1h's the sequences of at least two full pieces are copied raw and contiguous
+// what submit_impl leaves to row slots.  On an engine that qualifies (long_fast) the sequences of at least two full pieces are copied raw and contiguous
 // into the staging pair — one memcpy each, their bytes cross PCIe once — and cut on the device, once together they hold long_min full pieces
 // (NTC_LONG_MIN: tuning runs, tools/long_time.py); everything else takes row slots as before
 template <class LenFn, class PtrFn> int submit_rows_or_long(ntc_engine* e, uint64_t n_reads, const LenFn& len_of, const PtrFn& ptr_of)
@@ -356,7 +371,7 @@ template <class LenFn, class PtrFn> int submit_rows_or_long(ntc_engine* e, uint6
 	}
 	if (long_min == kLongMinNever || !long_fast(e)) return submit_rows(e, n_reads, len_of, ptr_of);
 	const uint32_t L = kLongPieceDefault;
-	const uint64_t S = L - (e->klist[0] - 1u);
+	const uint64_t S = L - (long_kmax(e) - 1u);
 	std::vector<uint64_t> sel, rest;
 	uint64_t pieces = 0;
 	size_t bytes = 0;
@@ -510,8 +525,8 @@ int ntc_submit_long_device(ntc_engine* e, const void* d_bases, const uint64_t* o
 	if (!fast && e->ts_required)
 		return fail(NTC_ERR_ARG, "ntc_submit_long_device: the tiled kernels do not serve this configuration (NTC_FLAG_REQUIRE_TILED); nothing was counted");
 	const uint32_t L = piece_len ? piece_len : kLongPieceDefault;
-	if (fast && L < e->klist[0] + 15u)
-		return fail(NTC_ERR_ARG, "ntc_submit_long_device: piece_len %u below k + 15 = %u", L, e->klist[0] + 15u);
+	if (fast && L < long_kmax(e) + 15u)
+		return fail(NTC_ERR_ARG, "ntc_submit_long_device: piece_len %u below k + 15 = %u (k: the largest of the list)", L, long_kmax(e) + 15u);
 	StageLease lease;
 	if (int rc = lease_stage(e, 0, lease)) return rc; // (its meta buffers hold the call's tables)
 	return submit_long_leased(e, *lease.sl, (const unsigned char*)d_bases, 0, n_seqs, [&](uint64_t i) { return offsets[i + 1] - offsets[i]; },

@@ -166,7 +166,10 @@ class Engine:
 
     def submit_long_device(self, d_ptr, offsets, piece_len=0):
         """device-resident long sequences: sequence i = the bytes [offsets[i], offsets[i + 1]) from d_ptr (device memory, raw bytes of any alignment);
-        offsets: host uint64[n + 1]; piece_len: 0 or a multiple of 16 (include/ntcard_hip.h: ntc_submit_long_device)"""
+        offsets: host uint64[n + 1]; piece_len: 0 or a multiple of 16 from kmax + 15 on.  An engine whose planes are all the tiled kernels' — one plane, or a
+        list of plain k with kmax - kmin <= 15 — cuts every sequence ONCE, as long_plan(kmax, piece_len, n) says, and counts every k from the same tiles; a
+        remainder is counted iff it holds a window of kmin; the host sends 16 B per sequence, not per piece.  Every other engine gathers the sequences
+        whole (long_stats stays (0, 0); FLAG_REQUIRE_TILED refuses).  include/ntcard_hip.h: ntc_submit_long_device"""
         o = np.ascontiguousarray(offsets, dtype=np.uint64)
         check(self._lib.ntc_submit_long_device(self._h, C.c_void_p(d_ptr) if d_ptr else None, _np_ptr(o), max(len(o) - 1, 0), int(piece_len)))
 
@@ -344,7 +347,8 @@ def gen_reads_device(d_ptr, seed, first, n, read_len, stride, dist, genome_len=1
 
 
 def long_plan(k, piece_len, n):
-    """the cut of one sequence of n bytes into pieces of piece_len -> (full pieces m, start of the remainder [m S, n)); ntc_long_plan, host only"""
+    """the cut of one sequence of n bytes into pieces of piece_len -> (full pieces m, start of the remainder [m S, n)), S = piece_len - (k - 1); k: the
+    engine's k, for a k list its largest (one cut serves the list).  ntc_long_plan, host only"""
     m, rem = C.c_uint64(), C.c_uint64()
     check(_abi.lib().ntc_long_plan(int(k), int(piece_len), int(n), C.byref(m), C.byref(rem)))
     return m.value, rem.value
