@@ -97,13 +97,28 @@ typedef struct {
  *     For a plane that is a spaced seed (ntc_create_seeded, ntc_create with gap) fs / rs as defined there — the don't-care terms XORed out of fh / rh —
  *     take the place of fh / rh.
  *   - Everything behind the value is unchanged: sampling, bucket, hit log, sketch update, estimator, output.
- * Valid with ntc_create (k lists, gap) and ntc_create_seeded; both flags together are NTC_ERR_ARG (checked before a device is looked for).  A strand engine
- * is the general kernel's (K1, in its one-strand form: one rolling update and one table half per base instead of two) and the simple validation kernel's:
- * the tiled kernel pair K1h + K1f is canonical only, so no k of a strand engine is theirs — tiled batches, ragged ones and bins included, are re-laid out
- * on the device and counted by K1, NTC_FLAG_REQUIRE_TILED makes the tiled submit fail with nothing counted, host batches take row slots.  It counts at K1's
- * rate, not at K1h's (DESIGN.md §4 "One strand").  ntc_merge_devices refuses engines whose strands differ.  nthll engines take the same two flags through ntc_hll_create_ex (ntc_hll_create: canonical). */
+ * Valid with ntc_create (k lists, gap) and ntc_create_seeded; both flags together are NTC_ERR_ARG (checked before a device is looked for).  WITHOUT
+ * NTC_FLAG_STRAND_TILED a strand engine is the general kernel's (K1, in its one-strand form: one rolling update and one table half per base instead of two)
+ * and the simple validation kernel's: no k of it is the tiled pair's — tiled batches, ragged ones and bins included, are re-laid out on the device and
+ * counted by K1, NTC_FLAG_REQUIRE_TILED makes the tiled submit fail with nothing counted, host batches take row slots.  It then counts at K1's rate, not at
+ * K1h's (DESIGN.md §4 "One strand").  ntc_merge_devices refuses engines whose strands differ.  nthll engines take the same two flags through
+ * ntc_hll_create_ex (ntc_hll_create: canonical). */
 #define NTC_FLAG_STRAND_FORWARD 512u
 #define NTC_FLAG_STRAND_REVERSE 1024u
+/* A ONE-STRAND engine on the TILED kernels (additive to ABI 6: one flag bit).  Valid only beside exactly one of NTC_FLAG_STRAND_FORWARD / _REVERSE: alone,
+ * or beside both, it is NTC_ERR_ARG, checked before a device is looked for; ntc_hll_create_ex refuses it.  The library holds a one-strand form of K1h for
+ * every (k, gap) of the canonical one — it walks, tests and queues that strand alone; K1f re-derives with fh or rh where it re-derives at all and has no
+ * ties to settle.  A strand engine's plane is the tiled kernels' when it is plain k = 12 .. 32 or one of the two tiled -g seeds, with sBits >= 7.
+ *   - EVERY plane of the engine is one of those: every tiled route works as for a canonical engine — ntc_submit_tiled_device, _ragged_device,
+ *     _bins_device, the tile packing of host batches, NTC_FLAG_DEFER_REDO's shared launches and deferred K1f — NTC_FLAG_REQUIRE_TILED is satisfied on
+ *     them, and the engine qualifies for the long-sequence cut under the rules given at ntc_submit_long_device.
+ *   - Only PART of the list qualifies (k = 32,64): the flag changes nothing, for any k of the list — re-layout, then K1, and NTC_FLAG_REQUIRE_TILED
+ *     refuses tiled batches as above.  (K1 has no one-strand form that stages tiles, so a strand list cannot be split between the kernels the way a
+ *     canonical one is.)
+ * Without the flag a strand engine behaves bit for bit as before it existed; results are identical either way, and ntc_merge_devices does not compare the
+ * flag (strand, k list, masks, rBits and sBits still have to match).  Rates: DESIGN.md §4 "One strand", profiles/strand_k1h.txt.
+ * (Bit 2048 stays refused as an unknown flag.) */
+#define NTC_FLAG_STRAND_TILED 4096u
 #define NTC_FLAG_DIRECT_ATOMICS 2u /* no hit log: every sampled k-mer is one device atomic on the sketch
                                       (the literal form of ntcard.cpp:142-143; cross-check and A/B runs) */
 
@@ -210,7 +225,8 @@ int ntc_submit_tiled_bins_device(ntc_engine *e, uint32_t n_bins, const void *con
  * n_seqs + 1 non-decreasing entries.  Stream-ordered: d_bases may be reused as soon as the stream has passed the call, under NTC_FLAG_DEFER_REDO too (the
  * engine counts from scratch of its own, so this call never defers); offsets is free on return.  The kernels read d_bases in aligned 4-byte words, and only
  * words that hold at least one byte of a sequence.
- * An engine QUALIFIES when every plane is the tiled kernels' (plain k = 12 .. 32 or the two tiled -g seeds, canonical, sBits >= 7) and it has either one
+ * An engine QUALIFIES when every plane is the tiled kernels' (plain k = 12 .. 32 or the two tiled -g seeds, sBits >= 7; canonical, or one strand with
+ * NTC_FLAG_STRAND_TILED) and it has either one
  * plane or a list of plain k with kmax - kmin <= 15.  Every sequence of n >= piece_len bytes is then cut on the device into the full pieces
  * [j S, j S + piece_len) of ntc_long_plan(kmax, ..), S = piece_len - (kmax - 1): ONE cut, with the overlap of the largest k, for the whole list — an
  * equal-length tiled batch counted by K1h + K1f at their rate, once per k.  A k of the list owns the windows that start in a piece's first S bytes: the
@@ -220,7 +236,7 @@ int ntc_submit_tiled_bins_device(ntc_engine *e, uint32_t n_bins, const void *con
  * engine's choice (1008), or a multiple of 16 with kmax + 15 <= piece_len <= 65520.  The work goes in rounds of at most 1 GiB of engine scratch, whatever the
  * input's size.  The host builds and sends 16 B per sequence that holds a full piece (its offset and the index of its first piece) and 16 B per row slot:
  * the pieces' offsets are derived on the device.
- * On every other engine (a list wider than 15 or with a k outside 12 .. 32, k > 32, other seeds, a strand, nthll, sBits < 7, NTC_FLAG_LANE_KERNEL,
+ * On every other engine (a list wider than 15 or with a k outside 12 .. 32, k > 32, other seeds, a strand without NTC_FLAG_STRAND_TILED, nthll, sBits < 7, NTC_FLAG_LANE_KERNEL,
  * NTC_FLAG_SIMPLE_KERNEL) every sequence is gathered whole: exactly ntc_submit's results, ntc_long_stats stays (0, 0) — with NTC_FLAG_REQUIRE_TILED the call
  * fails with NTC_ERR_ARG instead and counts nothing.
  * NTC_ERR_ARG for null pointers, a bad piece_len or offsets that decrease, checked before a device is looked for.
@@ -397,8 +413,8 @@ int ntc_hll_estimate_strand(const uint8_t *regs, uint32_t n_bits, uint32_t stran
 int ntc_kernel_time(ntc_engine *e, double *ms_total, uint64_t *launches);
 /* same for the deferred sketch update (partition + count passes): milliseconds and number of applies */
 int ntc_apply_time(ntc_engine *e, double *ms_total, uint64_t *applies);
-/* same for the fix-up kernels K1f of the one-wave-per-tile kernel when the engine defers them (NTC_FLAG_DEFER_REDO: one K1f launch over up to 8
- * batches, outside the hash kernels' events, so this time is NOT part of ntc_kernel_time; without the flag K1f follows every K1h launch and is) */
+/* same for the fix-up kernels K1f of the one-wave-per-tile kernel: a span of their own behind the hash kernels' — one per K1h launch, or with
+ * NTC_FLAG_DEFER_REDO one over up to 8 batches — so this time is NOT part of ntc_kernel_time, with or without the flag */
 int ntc_fixup_time(ntc_engine *e, double *ms_total);
 /* device buffers, copy streams and events ntc_merge_devices has created for this engine so far: they are kept between merges, so the count
  * stops growing after the first merge of a given group of engines (diagnostic) */

@@ -32,6 +32,11 @@ fixup_kernel) recomputes exactly those (read, block) pairs from the raw bytes wi
 
 Nothing is copied from the reference: the four seeds are its constants (nthash.hpp:25-28), everything else is derived (k1h_terms.py).
 
+One strand (NTC_FLAG_STRAND_TILED): Gen(k, sb_class, gap, strand) with strand 1 (forward) or 2 (reverse) emits the same kernel for that strand alone — its 31
+state planes in the walk, ONE candidate plane per window (flags_and_push_one), no tie plane or tie items, the tie words stored as zeros; forward candidates
+ride in the item's xf word, reverse ones in xr, so the resolve pass and its table are those of the canonical kernel.  strand 0 emits the canonical list
+unchanged.  STRAND_VARIANTS / `gen_k1h.py --strand` at the end of the file.
+
 The generator in three modules: k1h_regs.py (LDS geometry, the checked register map, the kernel arguments), k1h_exp.py (the K1H_EXP timing
 switches and their post-pass) and this one: class Gen, whose build() strings the kernel together from named stages.
 """
@@ -44,9 +49,10 @@ from k1h_regs import *  # noqa: F401,F403 (the register map is this module's voc
 
 
 class Gen:
-    def __init__(self, k, sb_class=7, gap=0):
-        assert 12 <= k <= 32 and 0 <= gap < k - 1
+    def __init__(self, k, sb_class=7, gap=0, strand=0):
+        assert 12 <= k <= 32 and 0 <= gap < k - 1 and strand in (0, 1, 2)
         self.k = k
+        self.strand = strand                # 0: both strands, the canonical value; 1 forward / 2 reverse: that strand alone is walked, tested and pushed
         self.sb = sb_class
         self.gap = gap                      # spaced seed "1" x (k-g)/2 "0" x g "1" x rest (ntcard.cpp:407-413): the g middle positions do not enter the hash
         self.g0 = (k - gap) // 2            # first don't-care position
@@ -303,7 +309,10 @@ class Gen:
             l0 = self.plane_back(a, self.k - self.g0)       # leaves the don't-care block (window index g0 -> g0 - 1)
             e0 = self.plane_back(a, self.k - 1 - self.g1)   # enters it (g1 + 1 -> g1)
         plan = {}
-        for strand, terms, gterms in (("F", self.f_terms, getattr(self, "fg_terms", None)), ("R", self.r_terms, getattr(self, "rg_terms", None))):
+        strands = (("F", self.f_terms, getattr(self, "fg_terms", None)), ("R", self.r_terms, getattr(self, "rg_terms", None)))
+        if self.strand:
+            strands = strands[self.strand - 1:self.strand]   # one strand: the other one's planes are neither planned nor updated (its registers are never read)
+        for strand, terms, gterms in strands:
             for jj in range(31):
                 tin, tout = terms[jj]
                 x, xi = self.fn_plane(cin, tin, i0, i1, tpool)
@@ -333,16 +342,18 @@ class Gen:
         # F's old bit 30, R's bit 30 R's old bit 0): that one alternates between its home register and a second one (V_WRAPF / V_WRAPR), written FIRST, while the
         # old value it needs is still there: no copy (round 5; two v_mov per step before).  Even steps find the bit at home and leave it in the second register,
         # odd steps the other way round; a block has 16 steps, so every block starts and ends at home.
-        f0_old, f0_new = (V_F + 0, V_WRAPF) if a % 2 == 0 else (V_WRAPF, V_F + 0)
-        update(f0_new, V_F + 30, *plan["F", 0])
-        for jj in range(30, 1, -1):
-            update(V_F + jj, V_F + jj - 1, *plan["F", jj])
-        update(V_F + 1, f0_old, *plan["F", 1])
-        r30_old, r30_new = (V_R + 30, V_WRAPR) if a % 2 == 0 else (V_WRAPR, V_R + 30)
-        update(r30_new, V_R + 0, *plan["R", 30])
-        for jj in range(0, 29):
-            update(V_R + jj, V_R + jj + 1, *plan["R", jj])
-        update(V_R + 29, r30_old, *plan["R", 29])
+        if self.strand != 2:
+            f0_old, f0_new = (V_F + 0, V_WRAPF) if a % 2 == 0 else (V_WRAPF, V_F + 0)
+            update(f0_new, V_F + 30, *plan["F", 0])
+            for jj in range(30, 1, -1):
+                update(V_F + jj, V_F + jj - 1, *plan["F", jj])
+            update(V_F + 1, f0_old, *plan["F", 1])
+        if self.strand != 1:
+            r30_old, r30_new = (V_R + 30, V_WRAPR) if a % 2 == 0 else (V_WRAPR, V_R + 30)
+            update(r30_new, V_R + 0, *plan["R", 30])
+            for jj in range(0, 29):
+                update(V_R + jj, V_R + jj + 1, *plan["R", jj])
+            update(V_R + 29, r30_old, *plan["R", 29])
 
     # ---- sample test of one strand: planes a (top bits == sample-1 pattern), g (>=), b (== sample-0 pattern), nz ----
     def strand_flags(self, base, out, top=None):
@@ -375,8 +386,56 @@ class Gen:
             self.bitop3(rb, t1, b0, b0, lambda x, y, z: 1 ^ (x | y))         # == 0x00
             # nz: any value is >= 0 — handled by the caller (cf = (a & g') | b)
 
+    def strand_candidates(self, base, out, top=None):
+        """one strand (self.strand): the candidate plane of the strand whose state starts at register `base` (top: as strand_flags) -> v(out) = a | b, the top bits
+        match sample 1's pattern or sample 0's (s_bits >= 8: their 8-bit prefixes).  No g / nz planes: there is no other strand to compare with.  Temps: T + 8, T + 9, T + 10 (flags_and_push_one puts `out` at T + 11): all inside the "test" range, whose g / nz / cf / cr / tie
+        planes a one-strand kernel does not have"""
+        t7, b6, b5, b4, b3, b2, b1, b0 = [v(base + 30 - i) for i in range(8)]
+        if top is not None:
+            t7 = v(top)
+        t1, t2, t3 = v(V_TEST + 8), v(V_TEST + 9), v(V_TEST + 10)
+        self.bitop3(t1, b6, b5, b4, lambda x, y, z: x & y & z)
+        self.bitop3(t1, t1, b3, b2, lambda x, y, z: x & y & z)                # bits 6 .. 2 all set
+        self.bitop3(t2, t7, b6, b5, lambda x, y, z: x | y | z)
+        self.bitop3(t3, b4, b3, b2, lambda x, y, z: x | y | z)
+        if self.sb == 7:
+            self.bitop3(t1, t7, t1, b1, lambda x, y, z: (1 ^ x) & y & z)       # a: top 7 bits == 0111111
+            self.bitop3(t2, t2, t3, b1, lambda x, y, z: 1 ^ (x | y | z))       # top 7 bits == 0
+            self.bitop3(v(out), t1, t2, b0, lambda x, y, z: x | (y & z))       # a | b, b: top 8 bits == 00000001
+        else:
+            self.bitop3(t1, t1, b1, b0, lambda x, y, z: x & y & z)            # low 7 of the 8 all set
+            self.bitop3(t2, t2, t3, b1, lambda x, y, z: x | y | z)
+            self.bitop3(t2, t2, b0, b0, lambda x, y, z: 1 ^ (x | y))           # b: == 0x00
+            self.bitop3(v(out), t7, t1, t2, lambda x, y, z: ((1 ^ x) & y) | z)  # a | b, a: == 0x7f
+
+    def flags_and_push_one(self, a):
+        """one strand: the candidate plane of step a, then the pushes — candidates of clean reads, suspects (the candidates under V_DMASK).  No tie plane, no
+        tie items, V_TACC stays 0 (end_of_block stores all-zero tie words).  Forward candidates ride in xf with xr = 0, reverse ones in xr with xf = 0: the
+        resolve pass picks the strand's half of the table from the item's zr word, as for a canonical item"""
+        p = self.p
+        cand = V_TEST + 11
+        if self.strand == 1:
+            self.strand_candidates(V_F, cand)
+        else:
+            self.strand_candidates(V_R, cand, top=V_WRAPR if a % 2 == 0 else V_R + 30)  # (behind an even step R's bit 30 sits in its second register)
+        hit, sx, zero = (V_PX, V_SXF, V_RX) if self.strand == 1 else (V_RX, V_SXR, V_PX)
+        p.i("v_and_b32", v(hit), v(cand), v(V_CMASK))
+        p.i("v_mov_b32", v(zero), 0)                           # (the other strand's word of both pushes)
+        sus = not self.on("timers")
+        if sus:
+            p.i("v_and_b32", v(sx), v(cand), v(V_DMASK))       # suspects: candidates of reads with a dirty piece near by (K1f knows the bytes)
+        self.push_items(a, *((hit, zero) if self.strand == 1 else (zero, hit)), 0)
+        if sus:
+            nosus = self.lbl("nosus")
+            p.i("v_cmp_ne_u32_e32", "vcc", 0, v(sx))
+            p.i("s_cbranch_vccz", "@" + nosus)                 # (the common case: no suspect in this step)
+            self.push_items(a, *((sx, zero) if self.strand == 1 else (zero, sx)), 1)
+            p.label(nosus)
+
     def flags_and_push(self, a):
         """candidate planes of step a (exact per strand), tie plane, then the two pushes"""
+        if self.strand:
+            return self.flags_and_push_one(a)
         p = self.p
         T = V_TEST
         fo = dict(a=T + 0, g=T + 1, b=T + 2, nz=T + 3, t1=T + 8, t2=T + 9)
@@ -1206,10 +1265,12 @@ class Gen:
         p.i("s_cmp_eq_u32", s(S_WF), s(S_S0))                    # (or the wave's first block, inside a tile)
         p.i("s_cbranch_scc0", "@" + notile)
         p.label(newtile)
-        hf, hr = self.poly_a("F"), self.poly_a("R")
+        hf, hr = self.poly_a("F") if self.strand != 2 else None, self.poly_a("R") if self.strand != 1 else None
         for jj in range(31):
-            p.i("v_mov_b32", v(V_F + jj), -1 if (hf >> jj) & 1 else 0)
-            p.i("v_mov_b32", v(V_R + jj), -1 if (hr >> jj) & 1 else 0)
+            if hf is not None:
+                p.i("v_mov_b32", v(V_F + jj), -1 if (hf >> jj) & 1 else 0)
+            if hr is not None:
+                p.i("v_mov_b32", v(V_R + jj), -1 if (hr >> jj) & 1 else 0)
         for i in range(32):
             p.i("v_mov_b32", v(V_H0 + i), 0)
             p.i("v_mov_b32", v(V_H1 + i), 0)
@@ -1303,12 +1364,13 @@ class Gen:
         p.i("s_branch", "@end")
 
 
-def render_inc(k, sb, gap=0):
-    g = Gen(k, sb, gap)
+def render_inc(k, sb, gap=0, strand=0):
+    g = Gen(k, sb, gap, strand)
     prog = g.build()
     lines = prog.render(label_fmt=".Lk1h_{}_%=")
     body = "\n".join('\t"' + ln.replace('"', '\\"') + '\\n"' for ln in lines)
-    return f"// GENERATED by gen_k1h.py (k = {k}, gap = {gap}, sBits class {sb}): {prog.n_insts()} instructions\n#define K1H_ASM_K{k}_G{gap}_S{sb} \\\n" + \
+    what, name = (f"sBits class {sb}", f"K1H_ASM_K{k}_G{gap}_S{sb}") if strand == 0 else (f"sBits class {sb}, strand {strand}", f"K1H_ASM_K{k}_G{gap}_S{sb}_T{strand}")
+    return f"// GENERATED by gen_k1h.py (k = {k}, gap = {gap}, {what}): {prog.n_insts()} instructions\n#define {name} \\\n" + \
         "\n".join(ln + " \\" for ln in body.split("\n")) + "\n\n"
 
 
@@ -1316,6 +1378,33 @@ def render_inc(k, sb, gap=0):
 # (k = 12 / gap 2: round 4; k = 32 / gap 8: round 5)
 VARIANTS = tuple((k, 0) for k in range(12, 33)) + ((12, 2), (32, 8))
 PARTS = 4                      # the kernels are spread over this many objects (k % PARTS) so that `make -j` compiles them side by side
+# the one-strand kernels (NTC_FLAG_STRAND_TILED): every (k, gap) above for strand 1 (forward) and 2 (reverse), in include files and objects of their own
+# (`gen_k1h.py --strand`: ntc_k1h_strand_gen.inc, compiled from the same ntc_sketch_k1h_body.hip with -DK1H_STRAND) beside the canonical parts
+STRAND_VARIANTS = tuple((k, g, st) for st in (1, 2) for k, g in VARIANTS)
+STRAND_PARTS = 8
+
+
+def strand_part(k, strand):
+    return (strand - 1) * (STRAND_PARTS // 2) + k % (STRAND_PARTS // 2)
+
+
+def write_strand(out):
+    defs = out.replace(".inc", "_defs.inc")
+    with open(defs, "w") as f:
+        f.write("// ntc_k1h_strand_gen_defs.inc — GENERATED by gen_k1h.py --strand (do not edit): the list of one-strand kernel variants\n")
+        f.write(f"#define K1H_STRAND_GEN_PARTS {STRAND_PARTS}\n")
+        f.write("#define K1H_STRAND_VARIANTS_ALL(X) " + " ".join(f"X({k}, {g}, {st})" for k, g, st in STRAND_VARIANTS) + "\n")
+        for part in range(STRAND_PARTS):
+            f.write(f"#define K1H_STRAND_VARIANTS_P{part}(X) " + " ".join(f"X({k}, {g}, {st})" for k, g, st in STRAND_VARIANTS if strand_part(k, st) == part) + "\n")
+    with open(out, "w") as f:
+        f.write("// ntc_k1h_strand_gen.inc — GENERATED by gen_k1h.py --strand (do not edit): one assembly string per (k, gap, sBits class, strand)\n")
+        for k, gap, st in STRAND_VARIANTS:
+            for sb in (7, 8):
+                f.write(f"#if K1H_PART == {strand_part(k, st)}\n")
+                f.write(render_inc(k, sb, gap, st))
+                f.write("#endif\n")
+    print("wrote", out, "and", defs)
+
 
 
 if __name__ == "__main__":
@@ -1323,6 +1412,9 @@ if __name__ == "__main__":
         parse_exp()
     except ValueError as e:
         sys.exit(str(e))
+    if len(sys.argv) > 1 and sys.argv[1] == "--strand":
+        write_strand(sys.argv[2] if len(sys.argv) > 2 else "ntc_k1h_strand_gen.inc")
+        sys.exit(0)
     out = sys.argv[1] if len(sys.argv) > 1 else "ntc_k1h_gen.inc"
     defs = out.replace(".inc", "_defs.inc")
     with open(defs, "w") as f:

@@ -234,7 +234,8 @@ struct ntc_engine {
 	bool ts_required = false;       // NTC_FLAG_REQUIRE_TILED
 	bool seeded = false;            // ntc_create_seeded (a ragged tiled batch of a list no plane of which is K1h's goes to row slots, instead of being refused)
 	bool defer_redo = false;        // NTC_FLAG_DEFER_REDO
-	uint32_t strand = 0;            // 0 canonical; 1 NTC_FLAG_STRAND_FORWARD, 2 NTC_FLAG_STRAND_REVERSE: every batch is K1's one-strand form (no k is K1h's)
+	uint32_t strand = 0;            // 0 canonical; 1 NTC_FLAG_STRAND_FORWARD, 2 NTC_FLAG_STRAND_REVERSE: every batch is K1's one-strand form (no k is K1h's) unless NTC_FLAG_STRAND_TILED
+	                                // was given and every plane is one of the one-strand K1h kernels' (then ts_all, and the tiled routes are those of a canonical engine)
 	DevBuf<unsigned char> d_untile; // row-major scratch for tiled batches of configurations K1h is not built for
 	// ntc_submit_long_device (ntc_submit.hip): the scratch of one round — the tiles its pieces are cut into, or its row slots and their slot table — grown like
 	// d_untile; what ntc_long_stats and ntc_long_time report
@@ -300,6 +301,7 @@ void set_seed_args(ntc::HfArgs& a, const ntc::SeedPlan& sp, const void* d_blob);
 // ---- ntc_launch.hip: what enters the engine's stream (the caller holds e->mu) ----
 int device_cus(int dev, unsigned& cus);
 int ensure_kernel_attrs(int dev);
+int ensure_strand_kernel_attrs(int dev);
 int hf_plan(int dev, uint64_t n_slots, uint32_t stride, const uint32_t* ks, uint32_t n_k, uint32_t seed_lds, HfPlan& p);
 int hash_grid(int dev, uint64_t n_slots, uint32_t stride, unsigned& grid, size_t& smem);
 int open_span(ntc_engine* e, Span& s, hipEvent_t borrow = nullptr);

@@ -118,20 +118,23 @@ struct K1hMulti {
 	K1hArgs seg[kK1hSegs];
 	uint32_t n_segs;
 };
-bool sketch_k1h_supports(uint32_t k, uint32_t gap, uint32_t s_bits, uint32_t r_bits);
+// strand: 0 the canonical kernels; 1 forward / 2 reverse: the one-strand kernels (gen_k1h.STRAND_VARIANTS: the same k, gaps and sBits classes)
+bool sketch_k1h_supports(uint32_t k, uint32_t gap, uint32_t s_bits, uint32_t r_bits, uint32_t strand = 0);
 uint32_t sketch_k1h_blocks(uint32_t k, uint32_t read_len);
 uint32_t sketch_k1h_waves();
 uint32_t sketch_k1h_min_blocks(); // blocks per wave below which launch_sketch_k1h uses fewer workgroups
 void build_k1h_table(uint32_t k, uint32_t gap, uint32_t r_bits, uint32_t s_bits, uint32_t* out /* 2 * ceil(k / 3) * 64 dwords */);
-hipError_t set_sketch_k1h_smem_limit();
-hipError_t launch_sketch_k1h(const K1hArgs& a, uint32_t k, uint32_t gap, unsigned cus, hipStream_t st, K1hArgs* args_out, uint32_t* n_waves);
+hipError_t set_sketch_k1h_smem_limit();        // the canonical kernels
+hipError_t set_sketch_k1h_strand_smem_limit(); // the one-strand kernels (before the first launch of one on a device)
+hipError_t launch_sketch_k1h(const K1hArgs& a, uint32_t k, uint32_t gap, unsigned cus, hipStream_t st, K1hArgs* args_out, uint32_t* n_waves, uint32_t strand = 0);
 // the workgroups and block shares launch_sketch_k1h_multi gives n batches (read_len / n_tiles of a[i] set): fills first_wg, n_wg, blocks_per_wave, nb_magic of
 // out[i]; -> the grid.  The engine sizes the suspect lists from it before the launch.
 unsigned plan_sketch_k1h(const K1hArgs* a, uint32_t n, uint32_t k, unsigned cus, K1hArgs* out);
 // ONE launch over n <= kK1hSegs batches (same k, gap, sBits, table); args_out[i] = the arguments of batch i as launched; *n_waves = the waves of the
 // whole launch.  Every batch's suspect list is indexed by the wave's number in the LAUNCH: batch i's suspects sit in the regions first_wg * 8 .. of ITS list,
 // the other regions of that list are not written (K1f visits n_wg * 8 regions from first_wg * 8: K1fItem::n_waves)
-hipError_t launch_sketch_k1h_multi(const K1hArgs* a, uint32_t n, uint32_t k, uint32_t gap, unsigned cus, hipStream_t st, K1hArgs* args_out, uint32_t* n_waves);
+hipError_t launch_sketch_k1h_multi(const K1hArgs* a, uint32_t n, uint32_t k, uint32_t gap, unsigned cus, hipStream_t st, K1hArgs* args_out, uint32_t* n_waves,
+                                   uint32_t strand = 0);
 // K1f takes up to kK1fBatch K1h launches at a time (blockIdx.y = the launch): its kernels wait on memory, not on issue slots, so the launches of
 // several batches cost little more than those of one (an engine whose caller keeps the batches unchanged until ntc_sync defers them)
 constexpr uint32_t kK1fBatch = 8;
@@ -144,6 +147,7 @@ struct K1fItem {
 	uint32_t* klog;               // [klog_n][klog_cap]
 	uint32_t* klog_fill;          // [klog_n]
 	uint32_t klog_n, klog_cap;
+	uint32_t strand;              // 0: a canonical K1h launch; 1 forward / 2 reverse: a one-strand launch — the slow path takes fh / rh, the tie rows are not visited
 };
 struct K1fBatch {
 	K1fItem item[kK1fBatch];

@@ -38,6 +38,19 @@ int ensure_kernel_attrs(int dev)
 	return 0;
 }
 
+// the one-strand K1h kernels' attribute, once per device, for the first engine that will launch them (NTC_FLAG_STRAND_TILED)
+int ensure_strand_kernel_attrs(int dev)
+{
+	static std::mutex mu;
+	static std::vector<char> done;
+	std::lock_guard<std::mutex> lk(mu);
+	if ((size_t)dev >= done.size()) done.resize(dev + 1, 0);
+	if (done[dev]) return 0;
+	HIP_TRY(ntc::set_sketch_k1h_strand_smem_limit());
+	done[dev] = 1;
+	return 0;
+}
+
 int hf_plan(int dev, uint64_t n_slots, uint32_t stride, const uint32_t* ks, uint32_t n_k, uint32_t seed_lds, HfPlan& p)
 {
 	unsigned cus = 0;
@@ -712,7 +725,7 @@ int launch_k1h(ntc_engine* e, K1hPlan& p, const K1hNeed& need, unsigned cus, boo
 	ntc::K1hArgs launched[ntc::kK1hSegs];
 	uint32_t n_waves = 0;
 	if (int rc = open_run(e)) return rc; // (a K1f in ensure_sets may have closed the bracket)
-	HIP_TRY(ntc::launch_sketch_k1h_multi(p.hs, na, k, e->kgap[ki], cus, e->stream, launched, &n_waves));
+	HIP_TRY(ntc::launch_sketch_k1h_multi(p.hs, na, k, e->kgap[ki], cus, e->stream, launched, &n_waves, e->strand));
 	for (uint32_t i = 0; i < na; ++i) {
 		auto& it = e->k1f_batch.item[e->k1f_n++];
 		it.a = launched[i];
@@ -723,6 +736,7 @@ int launch_k1h(ntc_engine* e, K1hPlan& p, const K1hNeed& need, unsigned cus, boo
 		it.klog_fill = e->d_log ? e->d_logfill + e->log_regions : nullptr;
 		it.klog_n = e->d_log ? e->klog_regions : 0u;
 		it.klog_cap = e->log_region_cap;
+		it.strand = e->strand;
 	}
 	return defer ? 0 : join_k1f(e); // the caller may change the batches once the stream has passed this call: K1f now
 }

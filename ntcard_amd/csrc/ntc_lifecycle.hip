@@ -45,11 +45,13 @@ namespace {
 int check_config(const ntc_config* cfg)
 {
 	constexpr uint32_t kKnownFlags = NTC_FLAG_SIMPLE_KERNEL | NTC_FLAG_DIRECT_ATOMICS | NTC_FLAG_ALWAYS_LOG | NTC_FLAG_PARTITION_ALWAYS | NTC_FLAG_LANE_KERNEL |
-	                                 NTC_FLAG_REQUIRE_TILED | NTC_FLAG_DEFER_REDO | NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE;
+	                                 NTC_FLAG_REQUIRE_TILED | NTC_FLAG_DEFER_REDO | NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE | NTC_FLAG_STRAND_TILED;
 	if (cfg->flags & ~kKnownFlags) // (ABI 4's NTC_FLAG_BITSLICE_KERNEL = 4 and NTC_FLAG_TILED_TEAMS = 256 selected kernels that no longer exist)
 		return fail(NTC_ERR_ARG, "ntc_create: unknown flag bits 0x%x", cfg->flags & ~kKnownFlags);
 	if ((cfg->flags & NTC_FLAG_STRAND_FORWARD) && (cfg->flags & NTC_FLAG_STRAND_REVERSE))
 		return fail(NTC_ERR_ARG, "ntc_create: NTC_FLAG_STRAND_FORWARD and NTC_FLAG_STRAND_REVERSE exclude each other");
+	if ((cfg->flags & NTC_FLAG_STRAND_TILED) && !(cfg->flags & (NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE)))
+		return fail(NTC_ERR_ARG, "ntc_create: NTC_FLAG_STRAND_TILED needs NTC_FLAG_STRAND_FORWARD or NTC_FLAG_STRAND_REVERSE (it picks the kernels of a one-strand engine)");
 	for (uint32_t i = 0; i < cfg->n_k; ++i)
 		if (cfg->k[i] < 1 || cfg->k[i] > kMaxK)
 			return fail(NTC_ERR_ARG, "ntc_create: k=%u outside 1..%u", cfg->k[i], kMaxK);
@@ -188,17 +190,26 @@ int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, 
 	// served by one launch per k over the same resident tiles.  Its hit-log keys and K1f's atomics are 32-bit counter indices.  Everything else —
 	// row slots, other k, other seeds, nthll — is K1's (NTC_FLAG_LANE_KERNEL: tiled batches too, re-laid out as row slots).
 	// A list may mix both kinds (`-k 16,24,32,48`, BASELINE config 4's `32,64,96,128`): K1h takes its k from the tiles, K1 stages the same tiles for the rest.
-	// One strand: K1h + K1f walk both strands bit-sliced and are not touched — no k of a strand engine is theirs (tiled batches: re-laid out, then K1).
-	const bool ts_pre = e->kernel_kind == KIND_HF && !(cfg->flags & NTC_FLAG_LANE_KERNEL) && e->hll_bits == 0 && e->strand == 0 &&
+	// One strand: the canonical K1h walks both strands bit-sliced — without NTC_FLAG_STRAND_TILED no k of a strand engine is the pair's (tiled batches:
+	// re-laid out, then K1).  With the flag the one-strand K1h kernels + K1f take the engine when EVERY plane is one of theirs; a list of which only a part
+	// qualifies stays K1's as a whole (K1 has no one-strand instantiation that stages tiles).
+	const bool strand_ok = e->strand == 0 || (cfg->flags & NTC_FLAG_STRAND_TILED);
+	const bool ts_pre = e->kernel_kind == KIND_HF && !(cfg->flags & NTC_FLAG_LANE_KERNEL) && e->hll_bits == 0 && strand_ok &&
 	                    nk * e->plane_elems() <= (1ull << 32);
 	e->k_tiled.assign(nk, 0);
 	e->ts_ok = false;
 	e->ts_all = ts_pre;
 	for (size_t ki = 0; ki < nk; ++ki) {
-		e->k_tiled[ki] = ts_pre && (e->plain(ki) || e->kgap[ki] != 0) && ntc::sketch_k1h_supports(e->klist[ki], e->kgap[ki], e->s_bits, e->r_bits) ? 1 : 0;
+		e->k_tiled[ki] = ts_pre && (e->plain(ki) || e->kgap[ki] != 0) && ntc::sketch_k1h_supports(e->klist[ki], e->kgap[ki], e->s_bits, e->r_bits, e->strand) ? 1 : 0;
 		e->ts_ok = e->ts_ok || e->k_tiled[ki];
 		e->ts_all = e->ts_all && e->k_tiled[ki];
 	}
+	if (e->strand != 0 && !e->ts_all) { // a partly qualifying strand list: today's route for every k
+		e->k_tiled.assign(nk, 0);
+		e->ts_ok = false;
+	}
+	if (e->strand != 0 && e->ts_all)
+		if (int rc = ensure_strand_kernel_attrs(e->device)) return rc;
 	e->d_k1h_tabs.resize(nk);
 	e->d_t4s.resize(nk);
 	for (size_t ki = 0; ki < nk; ++ki) {

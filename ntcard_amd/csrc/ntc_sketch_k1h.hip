@@ -31,6 +31,7 @@ namespace ntc {
 namespace {
 
 #include "ntc_k1h_gen_defs.inc"
+#include "ntc_k1h_strand_gen_defs.inc"
 
 constexpr uint32_t kK1hWaves = K1H_GEN_WAVES;
 constexpr uint32_t kK1hWArea = K1H_GEN_WAREA;
@@ -47,6 +48,14 @@ constexpr uint32_t k1h_lds_bytes(uint32_t k) { return kK1hTableOff + k1h_table_b
 	hipError_t k1h_set_smem_part##p();
 K1H_DECL_PART(0) K1H_DECL_PART(1) K1H_DECL_PART(2) K1H_DECL_PART(3)
 static_assert(K1H_GEN_PARTS == 4, "one declaration / call per part");
+// the one-strand kernels (NTC_FLAG_STRAND_TILED): the same file compiled with -DK1H_STRAND, parts of their own
+#define K1H_DECL_STRAND_PART(p)                                                                                                                                \
+	hipError_t k1h_strand_launch_parts##p(uint32_t k, uint32_t gap, uint32_t strand, bool sb7, unsigned grid, uint32_t lds, hipStream_t st, const K1hMulti& b, \
+	                                      bool* found);                                                                                                        \
+	hipError_t k1h_set_smem_parts##p();
+#define K1H_STRAND_PARTS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+K1H_STRAND_PARTS(K1H_DECL_STRAND_PART)
+static_assert(K1H_STRAND_GEN_PARTS == 8, "one declaration / call per part");
 
 // ---- K1f ------------------------------------------------------------------------------------------------------------------------
 // What K1h leaves behind: dirty[tile][chunk][lane] (bit m: the 16-byte piece of read 64 m + lane holds a byte that is no ACGTU letter),
@@ -61,6 +70,9 @@ static_assert(K1H_GEN_PARTS == 4, "one declaration / call per part");
 //                     slow path (a suspect region overflowed, or a table-slot byte turned up): every window of every dirty-affected
 //                     block is re-derived from the bytes with the rolling recurrence (nthash.hpp:242-257), suspects are ignored;
 //                     always: the windows of tie blocks that both strands flag, by the same walk.
+// One strand (K1fItem::strand 1 forward / 2 reverse, behind a one-strand K1h launch): the F1 role and the fast path are unchanged — a suspect is a candidate
+// of that strand and K1h's counter index is that strand's; the slow path takes fh or rh instead of the smaller one; there are no ties — K1h writes all-zero
+// tie words, no suspect carries mark 4, and the slow path does not visit the tie rows.
 // The slow path's walk: a wave compacts items into an LDS queue and takes 64 at a time, one per lane; the lane's <= 6 raw pieces are staged
 // in LDS, then one step per position: the byte's 2-bit code shifts into a 64-bit register (the last 32 bases), a counter tells how many
 // bases in a row were letters of the reference's table, and where a window ends its hash is the closed form over four bases per look-up
@@ -295,7 +307,7 @@ __device__ __forceinline__ void k1f_suspect_role(const K1fItem& item, const uint
 				r1 ^= x.w;
 			}
 			const uint64_t fh = ((uint64_t)f1 << 32) | f0, rh = ((uint64_t)r1 << 32) | r0;
-			const uint64_t h = rh < fh ? rh : fh;                                                          // nthash.hpp:275-279
+			const uint64_t h = rh < fh ? rh : fh;                                                          // nthash.hpp:275-279 (ties are a canonical launch's: a one-strand K1h marks none)
 			uint32_t smp = 2;                                                                             // ntcard.cpp:132-145
 			if ((h >> (63u - s_bits)) == 1ull) smp = 0;
 			if ((h >> (64u - s_bits)) == (1ull << (s_bits - 1u)) - 1ull) smp = 1;
@@ -347,13 +359,13 @@ __global__ __launch_bounds__(256) void k1h_slow_kernel(const K1fBatch batch)
 	const K1fItem& item = batch.item[blockIdx.y];
 	const K1hArgs& a = item.a;
 	const void* const t4 = item.t4;
-	const uint32_t k = item.k;
+	const uint32_t k = item.k, strand = item.strand;
 	__shared__ uint2 s_queue[4][kFixQCap];
 	__shared__ __align__(16) unsigned char s_stage[4][64 * kFixStage];
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
 	const uint32_t phi = (k - 1u) & 15u;
 	const uint32_t nb = ((a.read_len - 1u + 16u - phi) >> 4) + 1u, C = a.n_chunks;
-	const uint64_t n_dirty = (uint64_t)a.n_tiles * C * 64u, n_tie = (uint64_t)a.n_tiles * nb * 64u;
+	const uint64_t n_dirty = (uint64_t)a.n_tiles * C * 64u, n_tie = strand ? 0u : (uint64_t)a.n_tiles * nb * 64u; // (one strand: no ties)
 	const uint32_t s_bits = a.s_bits, r_bits = a.r_bits, L = a.read_len;
 	const uint32_t rmask = (1u << r_bits) - 1u;
 	const uint4* const t4v = reinterpret_cast<const uint4*>(t4);
@@ -446,7 +458,7 @@ __global__ __launch_bounds__(256) void k1h_slow_kernel(const K1fBatch batch)
 				}
 				if (!(cf && cr)) continue;
 			}
-			const uint64_t h = rh < fh ? rh : fh;                                                          // nthash.hpp:275-279
+			const uint64_t h = strand == 1u ? fh : strand == 2u ? rh : (rh < fh ? rh : fh);                  // nthash.hpp:275-279; one strand: its own value
 			uint32_t smp = 2;                                                                             // ntcard.cpp:132-145
 			if ((h >> (63u - s_bits)) == 1ull) smp = 0;
 			if ((h >> (64u - s_bits)) == (1ull << (s_bits - 1u)) - 1ull) smp = 1;
@@ -521,11 +533,14 @@ __global__ __launch_bounds__(256) void k1h_slow_kernel(const K1fBatch batch)
 
 // the resolve pass works on ONE 32-bit word per candidate: the low r_bits bits of the hash, the bit that tells the samples apart, and
 // (s_bits >= 8) the s_bits - 7 bits between the 8-bit prefix the walk tests and the end of ntComp's patterns
-bool sketch_k1h_supports(uint32_t k, uint32_t gap, uint32_t s_bits, uint32_t r_bits)
+bool sketch_k1h_supports(uint32_t k, uint32_t gap, uint32_t s_bits, uint32_t r_bits, uint32_t strand)
 {
 	bool built = false;
-#define K1H_IS(kk, gg) built |= k == kk && gap == gg;
+#define K1H_IS(kk, gg) built |= strand == 0u && k == kk && gap == gg;
 	K1H_VARIANTS_ALL(K1H_IS)
+#undef K1H_IS
+#define K1H_IS(kk, gg, tt) built |= strand == tt && k == kk && gap == gg;
+	K1H_STRAND_VARIANTS_ALL(K1H_IS)
 #undef K1H_IS
 	return built && s_bits >= 7 && s_bits <= 30 && r_bits + 1 + (s_bits - 7) <= 32;
 }
@@ -562,6 +577,16 @@ hipError_t set_sketch_k1h_smem_limit()
 	if (rc == hipSuccess) rc = k1h_set_smem_part1();
 	if (rc == hipSuccess) rc = k1h_set_smem_part2();
 	if (rc == hipSuccess) rc = k1h_set_smem_part3();
+	return rc;
+}
+
+// the same for the one-strand kernels: only a process that creates a strand engine on the tiled kernels pays for their 92 attributes
+hipError_t set_sketch_k1h_strand_smem_limit()
+{
+	hipError_t rc = hipSuccess;
+#define K1H_SET_STRAND_PART(p) if (rc == hipSuccess) rc = k1h_set_smem_parts##p();
+	K1H_STRAND_PARTS(K1H_SET_STRAND_PART)
+#undef K1H_SET_STRAND_PART
 	return rc;
 }
 
@@ -619,11 +644,12 @@ unsigned plan_sketch_k1h(const K1hArgs* a, uint32_t n, uint32_t k, unsigned cus,
 	return first;
 }
 
-hipError_t launch_sketch_k1h_multi(const K1hArgs* a, uint32_t n, uint32_t k, uint32_t gap, unsigned cus, hipStream_t st, K1hArgs* args_out, uint32_t* n_waves)
+hipError_t launch_sketch_k1h_multi(const K1hArgs* a, uint32_t n, uint32_t k, uint32_t gap, unsigned cus, hipStream_t st, K1hArgs* args_out, uint32_t* n_waves,
+                                   uint32_t strand)
 {
 	if (n == 0 || n > kK1hSegs) return hipErrorInvalidValue;
 	for (uint32_t i = 0; i < n; ++i)
-		if (!sketch_k1h_supports(k, gap, a[i].s_bits, a[i].r_bits) || a[i].s_bits != a[0].s_bits || a[i].table != a[0].table) return hipErrorInvalidValue;
+		if (!sketch_k1h_supports(k, gap, a[i].s_bits, a[i].r_bits, strand) || a[i].s_bits != a[0].s_bits || a[i].table != a[0].table) return hipErrorInvalidValue;
 	K1hMulti m;
 	std::memset(&m, 0, sizeof m);
 	m.n_segs = n;
@@ -631,10 +657,17 @@ hipError_t launch_sketch_k1h_multi(const K1hArgs* a, uint32_t n, uint32_t k, uin
 	const uint32_t lds = k1h_lds_bytes(k);
 	const bool sb7 = a[0].s_bits == 7;
 	bool found = false;
-	hipError_t rc = k1h_launch_part0(k, gap, sb7, grid, lds, st, m, &found);
-	if (!found) rc = k1h_launch_part1(k, gap, sb7, grid, lds, st, m, &found);
-	if (!found) rc = k1h_launch_part2(k, gap, sb7, grid, lds, st, m, &found);
-	if (!found) rc = k1h_launch_part3(k, gap, sb7, grid, lds, st, m, &found);
+	hipError_t rc = hipSuccess;
+	if (strand == 0u) {
+		rc = k1h_launch_part0(k, gap, sb7, grid, lds, st, m, &found);
+		if (!found) rc = k1h_launch_part1(k, gap, sb7, grid, lds, st, m, &found);
+		if (!found) rc = k1h_launch_part2(k, gap, sb7, grid, lds, st, m, &found);
+		if (!found) rc = k1h_launch_part3(k, gap, sb7, grid, lds, st, m, &found);
+	} else {
+#define K1H_TRY_STRAND_PART(p) if (!found) rc = k1h_strand_launch_parts##p(k, gap, strand, sb7, grid, lds, st, m, &found);
+		K1H_STRAND_PARTS(K1H_TRY_STRAND_PART)
+#undef K1H_TRY_STRAND_PART
+	}
 	if (!found) return hipErrorInvalidValue;
 	if (rc != hipSuccess) return rc;
 	for (uint32_t i = 0; i < n; ++i)
@@ -644,9 +677,9 @@ hipError_t launch_sketch_k1h_multi(const K1hArgs* a, uint32_t n, uint32_t k, uin
 }
 
 // K1h over one batch on stream st; *args_out = the arguments as launched (block shares filled in), *n_waves = its waves (suspect regions)
-hipError_t launch_sketch_k1h(const K1hArgs& a, uint32_t k, uint32_t gap, unsigned cus, hipStream_t st, K1hArgs* args_out, uint32_t* n_waves)
+hipError_t launch_sketch_k1h(const K1hArgs& a, uint32_t k, uint32_t gap, unsigned cus, hipStream_t st, K1hArgs* args_out, uint32_t* n_waves, uint32_t strand)
 {
-	return launch_sketch_k1h_multi(&a, 1, k, gap, cus, st, args_out, n_waves);
+	return launch_sketch_k1h_multi(&a, 1, k, gap, cus, st, args_out, n_waves, strand);
 }
 
 // K1f for the batches K1h has been launched over (arguments as launched), on any stream ordered behind those launches

@@ -1,6 +1,9 @@
 // ntc_sketch_k1h_body.hip — K1h's kernels: compiled K1H_GEN_PARTS times (-DK1H_PART=p: the variants with k % parts == p), see ntc_sketch_k1h.hip
 // for what the kernel pair computes.  C++ here only stages the closed-form table in LDS, shares the workgroup's blocks out among its eight waves
 // and hands seven scalars to the generated assembly (gen_k1h.py: explicit physical registers, exactly 255 VGPRs).
+// With -DK1H_STRAND the same file gives the ONE-STRAND kernels (NTC_FLAG_STRAND_TILED; gen_k1h.py --strand: ntc_k1h_strand_gen.inc, K1H_STRAND_GEN_PARTS
+// parts): one more template parameter — the strand, 1 forward / 2 reverse — and names of their own; without it the preprocessed text is what it was before
+// the switch existed.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -16,7 +19,20 @@ namespace ntc {
 namespace {
 
 #include "ntc_k1h_gen_defs.inc"
+#ifdef K1H_STRAND
+#include "ntc_k1h_strand_gen_defs.inc"
+#include "ntc_k1h_strand_gen.inc" // (only the strings of this part: #if K1H_PART == ...)
+#define K1H_TPARAMS int K, int SB, int GAP, int ST
+#define K1H_TARGS K, SB, GAP, ST
+#define K1H_KERNEL sketch_k1h_strand_kernel
+#define K1H_FN(name) K1H_CAT(K1H_CAT(name, s), K1H_PART)
+#else
 #include "ntc_k1h_gen.inc" // (only the strings of this part: #if K1H_PART == ...)
+#define K1H_TPARAMS int K, int SB, int GAP
+#define K1H_TARGS K, SB, GAP
+#define K1H_KERNEL sketch_k1h_kernel
+#define K1H_FN(name) K1H_CAT(name, K1H_PART)
+#endif
 
 // every offset the generated code reads its arguments at (k1h_regs.KARG, written into the defs file as K1H_GEN_KARGS) is the field's
 #define K1H_KARG_CHECK(name, off) static_assert(offsetof(K1hArgs, name) == off, "K1hArgs." #name " is not where k1h_regs.KARG has it");
@@ -52,7 +68,23 @@ constexpr uint32_t k1h_lds_bytes(uint32_t k) { return kK1hTableOff + k1h_table_b
 #define K1H_CLOBBERS_S "s26", "s27", "s28", "s29", "s30", "s31", "s34", "s35", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "vcc", "memory"
 
 // gen_k1h.py emits one body per (k, gap) and s_bits class (7, >= 8): an assembly string with explicit registers
-template <int K, int SB, int GAP> struct K1hBody;
+template <K1H_TPARAMS> struct K1hBody;
+#ifdef K1H_STRAND
+#define K1H_BODY_SPEC(k, g, sb, t)                                                                                                                           \
+	template <> struct K1hBody<k, sb, g, t> {                                                                                                               \
+		static __device__ __forceinline__ void run(uint32_t karg_lo, uint32_t karg_hi, uint32_t wave_gid, uint32_t n_waves, uint32_t lds_wbase,             \
+		                                           uint32_t first_block, uint32_t end_block)                                                                \
+		{                                                                                                                                                   \
+			asm volatile(K1H_ASM_K##k##_G##g##_S##sb##_T##t ::"s"(karg_lo), "s"(karg_hi), "s"(wave_gid), "s"(n_waves), "s"(lds_wbase), "s"(first_block),    \
+			             "s"(end_block)                                                                                                                     \
+			             : K1H_CLOBBERS_V, K1H_CLOBBERS_S);                                                                                                 \
+		}                                                                                                                                                   \
+	};
+#define K1H_BODY_SPECS(k, g, t) K1H_BODY_SPEC(k, g, 7, t) K1H_BODY_SPEC(k, g, 8, t)
+#define K1H_CAT2(a, b) a##b
+#define K1H_CAT(a, b) K1H_CAT2(a, b)
+#define K1H_MY_VARIANTS K1H_CAT(K1H_STRAND_VARIANTS_P, K1H_PART)
+#else
 #define K1H_BODY_SPEC(k, g, sb)                                                                                                                              \
 	template <> struct K1hBody<k, sb, g> {                                                                                                                  \
 		static __device__ __forceinline__ void run(uint32_t karg_lo, uint32_t karg_hi, uint32_t wave_gid, uint32_t n_waves, uint32_t lds_wbase,             \
@@ -67,16 +99,20 @@ template <int K, int SB, int GAP> struct K1hBody;
 #define K1H_CAT2(a, b) a##b
 #define K1H_CAT(a, b) K1H_CAT2(a, b)
 #define K1H_MY_VARIANTS K1H_CAT(K1H_VARIANTS_P, K1H_PART)
+#endif
 K1H_MY_VARIANTS(K1H_BODY_SPECS)
 
 } // namespace
 
+#if defined(K1H_WAVE_CLOCKS) && defined(K1H_STRAND)
+#error "the per-wave clocks are an experiment on the canonical kernels"
+#endif
 #ifdef K1H_WAVE_CLOCKS // timing experiment (tools/k1h_variant.sh, K1H_CXXFLAGS=-DK1H_WAVE_CLOCKS): every wave of the LAST launch leaves its first and last clock (100 MHz)
 static __device__ unsigned long long g_k1h_wave_clocks[2 * 4096];
 #endif
 
-template <int K, int SB, int GAP>
-__global__ __launch_bounds__(kK1hThreads) void sketch_k1h_kernel(const K1hMulti m)
+template <K1H_TPARAMS>
+__global__ __launch_bounds__(kK1hThreads) void K1H_KERNEL(const K1hMulti m)
 {
 #ifdef K1H_WAVE_CLOCKS
 	const unsigned long long wc_t0 = __builtin_amdgcn_s_memrealtime();
@@ -119,7 +155,7 @@ __global__ __launch_bounds__(kK1hThreads) void sketch_k1h_kernel(const K1hMulti 
 	const uint64_t karg = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(K1hMulti, seg) + (uint64_t)s * sizeof(K1hArgs);
 	const uint32_t karg_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)karg);
 	const uint32_t karg_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(karg >> 32));
-	K1hBody<K, SB, GAP>::run(karg_lo, karg_hi, wave_gid, n_waves, lds_wbase, first_block, end_block);
+	K1hBody<K1H_TARGS>::run(karg_lo, karg_hi, wave_gid, n_waves, lds_wbase, first_block, end_block);
 #ifdef K1H_WAVE_CLOCKS
 	if ((threadIdx.x & 63u) == 0u && blockIdx.x * kK1hWaves + (threadIdx.x >> 6) < 4096u) {
 		g_k1h_wave_clocks[2u * (blockIdx.x * kK1hWaves + (threadIdx.x >> 6))] = wc_t0;
@@ -129,6 +165,25 @@ __global__ __launch_bounds__(kK1hThreads) void sketch_k1h_kernel(const K1hMulti 
 }
 
 // ---- what ntc_sketch_k1h.hip calls: launch / shared-memory attribute of this part's kernels ----
+#ifdef K1H_STRAND
+#define K1H_LAUNCH_CASE(kk, gg, tt)                                                                                                                          \
+	if (k == kk && gap == gg && strand == tt) {                                                                                                             \
+		*found = true;                                                                                                                                      \
+		if (sb7) hipLaunchKernelGGL((sketch_k1h_strand_kernel<kk, 7, gg, tt>), dim3(grid), dim3(kK1hThreads), lds, st, b);                                      \
+		else hipLaunchKernelGGL((sketch_k1h_strand_kernel<kk, 8, gg, tt>), dim3(grid), dim3(kK1hThreads), lds, st, b);                                          \
+		return hipGetLastError();                                                                                                                           \
+	}
+#define K1H_SMEM_CASE(kk, gg, tt)                                                                                                                            \
+	if (rc == hipSuccess) rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&sketch_k1h_strand_kernel<kk, 7, gg, tt>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k1h_lds_bytes(kk)); \
+	if (rc == hipSuccess) rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&sketch_k1h_strand_kernel<kk, 8, gg, tt>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k1h_lds_bytes(kk));
+
+hipError_t K1H_FN(k1h_strand_launch_part)(uint32_t k, uint32_t gap, uint32_t strand, bool sb7, unsigned grid, uint32_t lds, hipStream_t st, const K1hMulti& b, bool* found)
+{
+	K1H_MY_VARIANTS(K1H_LAUNCH_CASE)
+	*found = false;
+	return hipSuccess;
+}
+#else
 #define K1H_LAUNCH_CASE(kk, gg)                                                                                                                              \
 	if (k == kk && gap == gg) {                                                                                                                             \
 		*found = true;                                                                                                                                      \
@@ -140,12 +195,13 @@ __global__ __launch_bounds__(kK1hThreads) void sketch_k1h_kernel(const K1hMulti 
 	if (rc == hipSuccess) rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&sketch_k1h_kernel<kk, 7, gg>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k1h_lds_bytes(kk)); \
 	if (rc == hipSuccess) rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&sketch_k1h_kernel<kk, 8, gg>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k1h_lds_bytes(kk));
 
-hipError_t K1H_CAT(k1h_launch_part, K1H_PART)(uint32_t k, uint32_t gap, bool sb7, unsigned grid, uint32_t lds, hipStream_t st, const K1hMulti& b, bool* found)
+hipError_t K1H_FN(k1h_launch_part)(uint32_t k, uint32_t gap, bool sb7, unsigned grid, uint32_t lds, hipStream_t st, const K1hMulti& b, bool* found)
 {
 	K1H_MY_VARIANTS(K1H_LAUNCH_CASE)
 	*found = false;
 	return hipSuccess;
 }
+#endif
 
 #ifdef K1H_WAVE_CLOCKS
 } // namespace ntc
@@ -156,7 +212,7 @@ extern "C" int K1H_CAT(ntc_dbg_k1h_wave_clocks_p, K1H_PART)(unsigned long long* 
 namespace ntc {
 #endif
 
-hipError_t K1H_CAT(k1h_set_smem_part, K1H_PART)()
+hipError_t K1H_FN(k1h_set_smem_part)()
 {
 	hipError_t rc = hipSuccess;
 	K1H_MY_VARIANTS(K1H_SMEM_CASE)

@@ -48,6 +48,9 @@ void usage(std::ostream& os)
 	   << "\t\toutput files <STRING>_seed<i>_k<length>.hist, or -o rows (seed, f, n) with i = 1, 2, ...\n"
 	   << "      --strand=canonical|forward|reverse\twhich value of a k-mer is counted [canonical]: the smaller of the k-mer and its reverse\n"
 	   << "\t\tcomplement (ntcard), the k-mer as read, or its reverse complement; with -k, -g and --seed; output files unchanged\n"
+	   << "      --strand-kernel=tiled|general\twhich kernels count a forward or reverse run [tiled]: the one-strand tiled kernels where every k-mer length\n"
+	   << "\t\tof the run is theirs (k = 12 .. 32, -g 2 at k = 12, -g 8 at k = 32), or the general kernel throughout (A/B runs); the output is the same;\n"
+	   << "\t\tno effect (and a warning) without --strand=forward|reverse\n"
 	   << "      --help\tdisplay this help and exit\n"
 	   << "      --version\toutput version information and exit\n";
 }
@@ -63,6 +66,7 @@ struct Options {
 	bool gap_given = false;
 	std::vector<std::string> seeds; // --seed: masks of '0' / '1' (include/ntcard_hip.h: ntc_create_seeded)
 	uint32_t strand_flag = 0;       // --strand: NTC_FLAG_STRAND_FORWARD / _REVERSE, 0 = canonical
+	bool strand_tiled = true;       // --strand-kernel: NTC_FLAG_STRAND_TILED beside a strand flag
 };
 
 void process_file(const std::string& path, ntc_engine* eng)
@@ -92,7 +96,8 @@ int main(int argc, char** argv)
 {
 	const auto t_start = std::chrono::steady_clock::now();
 	static const char shortopts[] = "t:s:r:k:c:l:p:f:o:g:";
-	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED, OPT_STRAND };
+	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED, OPT_STRAND, OPT_STRAND_KERNEL };
+	bool strand_kernel_given = false;
 	static const struct option longopts[] = { { "threads", required_argument, nullptr, 't' },
 		                                      { "kmer", required_argument, nullptr, 'k' },
 		                                      { "gap", required_argument, nullptr, 'g' },
@@ -105,6 +110,7 @@ int main(int argc, char** argv)
 		                                      { "version", no_argument, nullptr, OPT_VERSION },
 		                                      { "seed", required_argument, nullptr, OPT_SEED },
 		                                      { "strand", required_argument, nullptr, OPT_STRAND },
+		                                      { "strand-kernel", required_argument, nullptr, OPT_STRAND_KERNEL },
 		                                      { nullptr, 0, nullptr, 0 } };
 	Options opt;
 	bool die = false;
@@ -145,6 +151,17 @@ int main(int argc, char** argv)
 				opt.strand_flag = NTC_FLAG_STRAND_REVERSE;
 			else {
 				std::cerr << PROGRAM << ": --strand: `" << arg << "' is none of canonical, forward, reverse\n";
+				die = true;
+			}
+			break;
+		}
+		case OPT_STRAND_KERNEL: {
+			const std::string arg(optarg ? optarg : "");
+			if (arg == "tiled" || arg == "general") {
+				opt.strand_tiled = arg == "tiled";
+				strand_kernel_given = true;
+			} else {
+				std::cerr << PROGRAM << ": --strand-kernel: `" << arg << "' is neither tiled nor general\n";
 				die = true;
 			}
 			break;
@@ -260,7 +277,8 @@ int main(int argc, char** argv)
 	cfg.gap = opt.gap;
 	cfg.r_bits = opt.r_bits;
 	cfg.s_bits = opt.s_bits;
-	cfg.flags = opt.strand_flag;
+	if (strand_kernel_given && !opt.strand_flag) std::cerr << PROGRAM << ": warning: --strand-kernel has no effect on a canonical run (no --strand=forward|reverse)\n";
+	cfg.flags = opt.strand_flag | (opt.strand_flag && opt.strand_tiled ? NTC_FLAG_STRAND_TILED : 0u);
 	// Devices: NTCARD_DEVICES="0,1,2,..." spreads the input files over several GPUs (one private sketch each, merged
 	// at the end: counting is a commutative sum); NTCARD_DEVICE=<n> or nothing selects a single one.
 	std::vector<int> devices;

@@ -22,6 +22,7 @@ FLAG_REQUIRE_TILED = 64  # NTC_FLAG_REQUIRE_TILED: submit_tiled_device fails ins
 FLAG_DIRECT_ATOMICS = 2  # NTC_FLAG_DIRECT_ATOMICS: no hit log, one device atomic per sampled k-mer
 FLAG_STRAND_FORWARD = 512  # NTC_FLAG_STRAND_FORWARD: count the forward value fh of every window instead of the canonical min(fh, rh)
 FLAG_STRAND_REVERSE = 1024  # NTC_FLAG_STRAND_REVERSE: count the reverse value rh (the forward value of the window's reverse complement)
+FLAG_STRAND_TILED = 4096  # NTC_FLAG_STRAND_TILED: a one-strand engine whose planes are all the tiled kernels' counts on the one-strand K1h + K1f instead of K1
 _STRAND_FLAGS = {"canonical": 0, "forward": FLAG_STRAND_FORWARD, "reverse": FLAG_STRAND_REVERSE}
 SIZE_RULE_BYTES = 50_000_000_000  # ntcard.cpp:430: total input < 50 GB => sBits = 7
 
@@ -35,9 +36,14 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def _strand_flags(flags, strand):
-    """`flags` with the bit of the `strand` keyword ORed in (None: whatever `flags` says); checked before the library is asked for a device"""
+def _strand_flags(flags, strand, strand_tiled=False):
+    """`flags` with the bit of the `strand` keyword ORed in (None: whatever `flags` says), and FLAG_STRAND_TILED if `strand_tiled`; checked before the
+    library is asked for a device"""
     flags = int(flags)
+    if strand_tiled:
+        if not (strand in ("forward", "reverse") or (strand is None and flags & (FLAG_STRAND_FORWARD | FLAG_STRAND_REVERSE))):
+            raise ValueError("strand_tiled=True picks the kernels of a one-strand engine: it needs strand='forward' or 'reverse'")
+        flags |= FLAG_STRAND_TILED
     if strand is None:
         return flags
     if not isinstance(strand, str) or strand not in _STRAND_FLAGS:
@@ -49,10 +55,13 @@ def _strand_flags(flags, strand):
 
 
 class Engine:
-    def __init__(self, klist, gap=0, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0, strand=None):
+    def __init__(self, klist, gap=0, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0, strand=None,
+                 strand_tiled=False):
         """strand: "canonical" (the default, what ntcard counts), "forward" or "reverse" — which value of a window is counted
-        (include/ntcard_hip.h: NTC_FLAG_STRAND_FORWARD / _REVERSE)"""
-        flags = _strand_flags(flags, strand)
+        (include/ntcard_hip.h: NTC_FLAG_STRAND_FORWARD / _REVERSE).  strand_tiled: a one-strand engine whose planes are all the tiled kernels' (plain
+        k = 12 .. 32, the two tiled gap seeds, sBits >= 7) counts on the one-strand K1h + K1f instead of the general kernel (NTC_FLAG_STRAND_TILED;
+        the results are the same)"""
+        flags = _strand_flags(flags, strand, strand_tiled)
         self._lib = _abi.lib()
         self.klist = [int(k) for k in klist]
         self.gap, self.r_bits, self.s_bits, self.device = int(gap), int(r_bits), int(s_bits), int(device)
@@ -73,10 +82,11 @@ class Engine:
         self.seeds = None
 
     @classmethod
-    def from_seeds(cls, seeds, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0, strand=None):
+    def from_seeds(cls, seeds, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0, strand=None,
+                   strand_tiled=False):
         """an engine whose planes are spaced seeds given as masks of '0' / '1' (include/ntcard_hip.h: ntc_create_seeded); its klist is
-        the masks' lengths, so finish, merge_counters and the rest work as for a k list; strand as for Engine()"""
-        flags = _strand_flags(flags, strand)
+        the masks' lengths, so finish, merge_counters and the rest work as for a k list; strand and strand_tiled as for Engine()"""
+        flags = _strand_flags(flags, strand, strand_tiled)
         self = cls.__new__(cls)
         self._lib = _abi.lib()
         self.seeds = [s.decode() if isinstance(s, bytes) else str(s) for s in seeds]
@@ -246,7 +256,8 @@ class Engine:
         return n.value
 
     def fixup_time(self):
-        """milliseconds of the deferred K1f launches (FLAG_DEFER_REDO engines: one per up to 8 K1h launches, on the engine's stream; 0 otherwise)"""
+        """milliseconds of the K1f launches (a span of their own on the engine's stream, not part of kernel_time: one per K1h launch, or with FLAG_DEFER_REDO
+        one per up to 8)"""
         ms = C.c_double()
         check(self._lib.ntc_fixup_time(self._h, C.byref(ms)))
         return ms.value

@@ -12,6 +12,6 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$T -I$C -I$C/../../include $
 for p in 0 1 2 3; do /opt/rocm/bin/hipcc $FLAGS -DK1H_PART=$p -c $T/ntc_sketch_k1h_body.hip -o $T/ntc_sketch_k1h_p$p.o & done
 /opt/rocm/bin/hipcc $FLAGS -c $T/ntc_sketch_k1h.hip -o $T/ntc_sketch_k1h.o
 wait
-OBJS=$(ls $C/build/*.o | grep -v ntc_sketch_k1h)
+OBJS=$(ls $C/build/*.o | grep -v 'ntc_sketch_k1h\(_p[0-9]*\)\?\.o$')  # (the one-strand parts ntc_sketch_k1h_s*.o stay the product's)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $(dirname $0)/lib_k1h_$NAME.so $OBJS $T/ntc_sketch_k1h.o $T/ntc_sketch_k1h_p0.o $T/ntc_sketch_k1h_p1.o $T/ntc_sketch_k1h_p2.o $T/ntc_sketch_k1h_p3.o -ldl
 echo built tools/lib_k1h_$NAME.so
