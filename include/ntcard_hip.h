@@ -119,6 +119,26 @@ typedef struct {
  * flag (strand, k list, masks, rBits and sBits still have to match).  Rates: DESIGN.md §4 "One strand", profiles/strand_k1h.txt.
  * (Bit 2048 stays refused as an unknown flag.) */
 #define NTC_FLAG_STRAND_TILED 4096u
+/* HOMOPOLYMER-COMPRESSED counting (additive to ABI 6: one flag bit, ntc_hpc_compress, ntc_hpc_compress_device, ntc_hpc_stats, ntc_hpc_time; ntc_config and
+ * NTC_ABI_VERSION are unchanged).  Every run of one base is collapsed to its first byte before the windows are taken — the space HiFi / ONT assemblers and
+ * their QC count k-mers in, since long-read errors are mostly errors of a run's length.  class(b): A a -> 0, C c -> 1, G g -> 2, T t U u -> 3; every other
+ * byte has none (N, IUPAC letters, CR, the control bytes 1, 3, 4, 5, 7 the seed table takes for bases).  Within ONE sequence byte j is DROPPED iff j > 0 and
+ * class(b[j]) exists and equals class(b[j - 1]); kept bytes keep value and order (of `aAAa` the leading `a` survives).  So bytes without a class are never
+ * dropped (`NNN` stays three bytes), a run never continues across a sequence boundary, an empty sequence stays empty.  The compressed sequence is what
+ * ntRead (ntcard.cpp:147-158) then sees: which windows count, strands, masks, k lists, sampling, F1, the estimator and the outputs are unchanged.
+ *   - Valid in ntc_create and ntc_create_seeded beside every other flag, and in ntc_hll_config.flags alone or beside one strand flag.
+ *   - ntc_submit / ntc_submit_spans compress every read on the host (ntc_hpc_compress) into a temporary batch and go on as without the flag.
+ *   - ntc_submit_long_device compacts ON THE DEVICE into scratch of the engine's own, in rounds of whole sequences of at most NTC_HPC_ROUND_BYTES source
+ *     bytes (environment, read per call; default 1 GiB; a longer sequence is a round of its own, the scratch grows to it), and hands the scratch and the new
+ *     offsets to the path the call takes without the flag: piece_len, the cut, ntc_long_stats and NTC_FLAG_REQUIRE_TILED speak of the COMPRESSED sequences.
+ *     Every round WAITS for the stream once: the new offsets (8 B per sequence) come back to the host, whose planner cuts the sequences.  The source
+ *     may be reused as soon as the stream has passed the call, under NTC_FLAG_DEFER_REDO too.
+ *   - The fixed-layout device batches (ntc_submit_device, ntc_submit_tiled_device, _ragged_device, _bins_device) fix a read's length: on an engine with
+ *     the flag they fail with NTC_ERR_ARG and count nothing.
+ *   - ntc_merge_devices refuses engines that differ in the flag.  ntc_merge_counters CANNOT know how a dumped image was counted: merging an image
+ *     counted without the flag into an engine with it (or the other way round) is the caller's mistake to avoid.  The dump and generator tools ignore it.
+ * (Bits 4, 256, 2048 and 1 << 20 stay refused as unknown flags.) */
+#define NTC_FLAG_HPC 8192u
 #define NTC_FLAG_DIRECT_ATOMICS 2u /* no hit log: every sampled k-mer is one device atomic on the sketch
                                       (the literal form of ntcard.cpp:142-143; cross-check and A/B runs) */
 
@@ -259,6 +279,22 @@ int ntc_long_stats(ntc_engine *e, uint64_t *pieces, uint64_t *sequences);
 /* milliseconds of the cut and of the gather kernels while profiling (ntc_set_profiling), outside ntc_kernel_time's spans; either pointer may be NULL */
 int ntc_long_time(ntc_engine *e, double *cut_ms, double *gather_ms);
 
+/* Homopolymer compression of ONE sequence of n bytes (NTC_FLAG_HPC has the definition) — a pure host function, what ntc_submit / ntc_submit_spans run per
+ * read on an engine with the flag.  out has room for n bytes; out == in is allowed (any other overlap is not); *n_out = the bytes kept.  NTC_ERR_ARG for a
+ * null n_out, or a null in / out with n != 0. */
+int ntc_hpc_compress(const char *in, uint64_t n, char *out, uint64_t *n_out);
+/* The same for DEVICE-resident sequences, by the kernels an engine with NTC_FLAG_HPC runs in ntc_submit_long_device (a stand-alone tool, like
+ * ntc_hash_dump_device): d_in and offsets as for ntc_submit_long_device (any alignment; a HOST array of n_seqs + 1 non-decreasing entries), d_out device
+ * memory of any alignment with room for offsets[n_seqs] - offsets[0] bytes, not overlapping d_in; offsets_out a HOST array of n_seqs + 1 entries:
+ * offsets_out[0] = 0, sequence i of the result = d_out[offsets_out[i], offsets_out[i + 1]).  Synchronous.  NTC_ERR_ARG for null pointers and offsets that
+ * decrease, checked before the device is touched.  The call allocates its scratch (an eighth of the input and 12 B per 4 KiB) and frees it. */
+int ntc_hpc_compress_device(int32_t device, void *stream, const void *d_in, const uint64_t *offsets, uint64_t n_seqs, void *d_out, uint64_t *offsets_out);
+/* cumulative since create / reset: the sequence bytes an engine with NTC_FLAG_HPC was given and the bytes it kept, over the host and the device paths
+ * alike; (0, 0) for ever on an engine without the flag */
+int ntc_hpc_stats(ntc_engine *e, uint64_t *bytes_in, uint64_t *bytes_out);
+/* milliseconds of the compaction kernels of ntc_submit_long_device while profiling (ntc_set_profiling), outside ntc_kernel_time's spans, like ntc_long_time */
+int ntc_hpc_time(ntc_engine *e, double *ms);
+
 int ntc_sync(ntc_engine *e); /* wait for all submitted work */
 
 /* Apply the pending hit log to the device sketch (asynchronous on the engine's stream).  After it the
@@ -395,7 +431,7 @@ typedef struct {
     uint32_t n_seeds; const char *const *seeds;   /* masks with the syntax and rules of ntc_create_seeded; exactly one of the two is non-empty */
     uint32_t n_bits;                              /* nthll -b, 4 .. 24 */
     int32_t device; void *stream;
-    uint32_t flags;                               /* 0, NTC_FLAG_STRAND_FORWARD or NTC_FLAG_STRAND_REVERSE; anything else: NTC_ERR_ARG */
+    uint32_t flags;                               /* 0 or NTC_FLAG_STRAND_FORWARD or NTC_FLAG_STRAND_REVERSE, each with or without NTC_FLAG_HPC; anything else: NTC_ERR_ARG */
 } ntc_hll_config;
 int ntc_hll_create_ex(const ntc_hll_config *cfg, ntc_engine **out);
 /* regs_out: HOST uint8_t [n_planes][1<<n_bits] (a plane == tVec of nthll.cpp:212-243), or NULL; f1_out: uint64_t [n_planes], the k-mers hashed per

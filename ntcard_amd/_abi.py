@@ -20,6 +20,7 @@ ABI_SYMBOLS = [
     "ntc_log_export_device", "ntc_log_replace_device",
     "ntc_create_seeded", "ntc_hash_dump_seed_device", "ntc_hash_dump_strand_device",
     "ntc_submit_long_device", "ntc_long_plan", "ntc_long_stats", "ntc_long_time",
+    "ntc_hpc_compress", "ntc_hpc_compress_device", "ntc_hpc_stats", "ntc_hpc_time",
 ]
 
 
@@ -99,6 +100,10 @@ def lib():
     L.ntc_long_plan.argtypes = [u32, u32, u64, C.POINTER(u64), C.POINTER(u64)]
     L.ntc_long_stats.argtypes = [p, C.POINTER(u64), C.POINTER(u64)]
     L.ntc_long_time.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.ntc_hpc_compress.argtypes = [p, u64, p, C.POINTER(u64)]
+    L.ntc_hpc_compress_device.argtypes = [i32, p, p, p, u64, p, p]
+    L.ntc_hpc_stats.argtypes = [p, C.POINTER(u64), C.POINTER(u64)]
+    L.ntc_hpc_time.argtypes = [p, C.POINTER(C.c_double)]
     L.ntc_sync.argtypes = [p]
     L.ntc_finish.argtypes = [p, p, p, p]
     L.ntc_merge_counters.argtypes = [p, p, p]

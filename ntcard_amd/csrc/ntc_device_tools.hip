@@ -132,6 +132,51 @@ int ntc_value_hist_u16_device(int32_t device, void* stream, const void* d_counte
 	return 0;
 }
 
+// homopolymer compression of one sequence (include/ntcard_hip.h: NTC_FLAG_HPC); in place when out == in: byte j is read before byte m <= j is written
+int ntc_hpc_compress(const char* in, uint64_t n, char* out, uint64_t* n_out)
+{
+	if (!n_out || (n && (!in || !out))) return fail(NTC_ERR_ARG, "ntc_hpc_compress: null argument");
+	const auto cls = [](unsigned char b) -> uint32_t {
+		switch (b | 0x20u) {
+		case 'a': return 0u;
+		case 'c': return 1u;
+		case 'g': return 2u;
+		case 't':
+		case 'u': return 3u;
+		default: return 0xffu; // N, IUPAC, CR, control bytes: no class, never dropped
+		}
+	};
+	uint64_t m = 0;
+	uint32_t pc = 0xffu;
+	for (uint64_t j = 0; j < n; ++j) {
+		const char b = in[j];
+		const uint32_t c = cls((unsigned char)b);
+		if (!(c != 0xffu && c == pc)) out[m++] = b;
+		pc = c;
+	}
+	*n_out = m;
+	return 0;
+}
+
+int ntc_hpc_compress_device(int32_t device, void* stream, const void* d_in, const uint64_t* offsets, uint64_t n_seqs, void* d_out, uint64_t* offsets_out)
+{
+	if (!offsets || !offsets_out) return fail(NTC_ERR_ARG, "ntc_hpc_compress_device: null offsets");
+	for (uint64_t i = 0; i < n_seqs; ++i)
+		if (offsets[i + 1] < offsets[i]) return fail(NTC_ERR_ARG, "ntc_hpc_compress_device: offsets not monotone at sequence %llu", (unsigned long long)i);
+	const uint64_t n = offsets[n_seqs] - offsets[0];
+	if (n && (!d_in || !d_out)) return fail(NTC_ERR_ARG, "ntc_hpc_compress_device: null buffer");
+	std::fill(offsets_out, offsets_out + n_seqs + 1, (uint64_t)0);
+	if (n == 0) return 0;
+	HIP_TRY(hipSetDevice(device));
+	hipStream_t st = (hipStream_t)stream;
+	DevBuf<unsigned char> aux; // (scratch of this call: freed on every way out)
+	if (!aux.reserve(ntc::hpc_aux_bytes(n, n_seqs))) return fail(NTC_ERR_MEMORY, "ntc_hpc_compress_device: cannot allocate %zu B of scratch on device", ntc::hpc_aux_bytes(n, n_seqs));
+	HIP_TRY(ntc::launch_hpc_compact((const unsigned char*)d_in, offsets, n_seqs, (unsigned char*)d_out, aux.get(), st));
+	HIP_TRY(hipMemcpyAsync(offsets_out, ntc::hpc_aux_offsets(aux.get(), n_seqs), (n_seqs + 1) * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return 0;
+}
+
 int ntc_hash_dump_device(int32_t device, void* stream, const void* d_slots, uint64_t n_reads, uint32_t read_len,
                          uint32_t stride, uint32_t k, uint32_t gap, uint32_t max_win, void* d_hash_out,
                          void* d_count_out)

@@ -243,6 +243,15 @@ struct ntc_engine {
 	uint64_t long_pieces = 0, long_seqs = 0;
 	std::vector<ntc_eng::Span> long_cut_events, long_gather_events; // (filled while profiling, like `pending`)
 	double long_cut_ms = 0.0, long_gather_ms = 0.0;
+	// NTC_FLAG_HPC (ntc_submit.hip, ntc_hpc.hip): homopolymer-compressed counting.  ntc_submit_long_device compacts a round of whole sequences into d_hpc —
+	// an owner of its own: d_long is recycled by the rounds of the cut that then READ d_hpc — with d_hpc_aux as the kernels' scratch (offsets, keep bits,
+	// prefix table); hpc_mu serialises such calls (a round leaves e->mu between its compaction and its count); what ntc_hpc_stats / ntc_hpc_time report
+	bool hpc = false;
+	DevBuf<unsigned char> d_hpc, d_hpc_aux;
+	std::mutex hpc_mu;
+	uint64_t hpc_bytes_in = 0, hpc_bytes_out = 0;
+	std::vector<ntc_eng::Span> hpc_events;
+	double hpc_ms = 0.0;
 	DevBuf<uint32_t> d_tmeta;       // K1's slot table (len | len << 16 per read) of a RAGGED tiled batch under a list of which a part is K1's
 	uint32_t hll_bits = 0;          // != 0: nthll engine (d_sketch holds uint32 M[1<<hll_bits])
 	DevBuf<uint32_t> d_hll_thr;

@@ -175,6 +175,14 @@ struct LongSpan {
 	uint32_t bytes, limit;
 };
 hipError_t launch_gather_slots(const unsigned char* src, const LongSpan* spans, uint64_t n_slots, uint32_t stride, unsigned char* slots, uint32_t* meta, hipStream_t st);
+// ---- homopolymer compression (ntc_hpc.hip; NTC_FLAG_HPC, ntc_hpc_compress_device) ----
+// One compaction: the n_seqs sequences [h_off[i], h_off[i + 1]) of src (host offsets, non-decreasing; source bytes of any alignment) lose every byte that
+// repeats the base class of the byte in front of it inside its sequence; the kept bytes go to out (any alignment; room for h_off[n_seqs] - h_off[0] bytes)
+// behind one another, and the new offsets — from 0 — to hpc_aux_offsets(aux, n_seqs): n_seqs + 1 device uint64.  aux: hpc_aux_bytes() bytes of device
+// scratch, 8-byte aligned.  Everything is queued on st, the copy of h_off included: the caller waits for the stream before h_off goes away.
+size_t hpc_aux_bytes(uint64_t n_bytes, uint64_t n_seqs);
+const uint64_t* hpc_aux_offsets(const void* aux, uint64_t n_seqs);
+hipError_t launch_hpc_compact(const unsigned char* src, const uint64_t* h_off, uint64_t n_seqs, unsigned char* out, void* aux, hipStream_t st);
 
 // ---- deferred sketch update (ntc_apply.hip) ----
 // A1/A2: radix partition of key runs.  Input run `seg` = in[seg * in_cap, +min(in_cnt[seg], in_cap)).

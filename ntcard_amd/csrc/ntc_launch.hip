@@ -138,11 +138,13 @@ int drain_events(ntc_engine* e)
 	if (int rc = elapsed(e->k1f_events, e->k1f_ms, nullptr)) return rc;
 	if (int rc = elapsed(e->long_cut_events, e->long_cut_ms, nullptr)) return rc;
 	if (int rc = elapsed(e->long_gather_events, e->long_gather_ms, nullptr)) return rc;
+	if (int rc = elapsed(e->hpc_events, e->hpc_ms, nullptr)) return rc;
 	e->pending.clear();
 	e->apply_pending.clear();
 	e->k1f_events.clear();
 	e->long_cut_events.clear();
 	e->long_gather_events.clear();
+	e->hpc_events.clear();
 	return 0;
 }
 

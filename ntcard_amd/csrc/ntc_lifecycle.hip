@@ -45,7 +45,7 @@ namespace {
 int check_config(const ntc_config* cfg)
 {
 	constexpr uint32_t kKnownFlags = NTC_FLAG_SIMPLE_KERNEL | NTC_FLAG_DIRECT_ATOMICS | NTC_FLAG_ALWAYS_LOG | NTC_FLAG_PARTITION_ALWAYS | NTC_FLAG_LANE_KERNEL |
-	                                 NTC_FLAG_REQUIRE_TILED | NTC_FLAG_DEFER_REDO | NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE | NTC_FLAG_STRAND_TILED;
+	                                 NTC_FLAG_REQUIRE_TILED | NTC_FLAG_DEFER_REDO | NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE | NTC_FLAG_STRAND_TILED | NTC_FLAG_HPC;
 	if (cfg->flags & ~kKnownFlags) // (ABI 4's NTC_FLAG_BITSLICE_KERNEL = 4 and NTC_FLAG_TILED_TEAMS = 256 selected kernels that no longer exist)
 		return fail(NTC_ERR_ARG, "ntc_create: unknown flag bits 0x%x", cfg->flags & ~kKnownFlags);
 	if ((cfg->flags & NTC_FLAG_STRAND_FORWARD) && (cfg->flags & NTC_FLAG_STRAND_REVERSE))
@@ -128,6 +128,7 @@ int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, 
 	e->klist.assign(cfg->k, cfg->k + nk);
 	e->seeded = seeded;
 	e->strand = (cfg->flags & NTC_FLAG_STRAND_FORWARD) ? 1u : (cfg->flags & NTC_FLAG_STRAND_REVERSE) ? 2u : 0u;
+	e->hpc = (cfg->flags & NTC_FLAG_HPC) != 0;
 	e->masks.assign(nk, std::string());
 	e->kgap.assign(nk, 0u);
 	e->seeds.assign(nk, ntc::SeedPlan());
@@ -277,8 +278,9 @@ int ntc_hll_create_ex(const ntc_hll_config* cfg, ntc_engine** out)
 	if (!cfg || !out) return fail(NTC_ERR_ARG, "ntc_hll_create_ex: null argument");
 	*out = nullptr;
 	// every argument first, the device afterwards
-	if (cfg->flags & ~(NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE))
-		return fail(NTC_ERR_ARG, "ntc_hll_create_ex: unknown flag bits 0x%x (an nthll engine takes the strand flags only)", cfg->flags & ~(NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE));
+	constexpr uint32_t kHllFlags = NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE | NTC_FLAG_HPC;
+	if (cfg->flags & ~kHllFlags)
+		return fail(NTC_ERR_ARG, "ntc_hll_create_ex: unknown flag bits 0x%x (an nthll engine takes the strand flags and NTC_FLAG_HPC only)", cfg->flags & ~kHllFlags);
 	if ((cfg->flags & NTC_FLAG_STRAND_FORWARD) && (cfg->flags & NTC_FLAG_STRAND_REVERSE))
 		return fail(NTC_ERR_ARG, "ntc_hll_create_ex: NTC_FLAG_STRAND_FORWARD and NTC_FLAG_STRAND_REVERSE exclude each other");
 	const bool has_k = cfg->n_k != 0 || cfg->k != nullptr, has_seeds = cfg->n_seeds != 0 || cfg->seeds != nullptr;
@@ -303,6 +305,7 @@ int ntc_hll_create_ex(const ntc_hll_config* cfg, ntc_engine** out)
 	e->klist = ks;
 	e->seeded = has_seeds;
 	e->strand = (cfg->flags & NTC_FLAG_STRAND_FORWARD) ? 1u : (cfg->flags & NTC_FLAG_STRAND_REVERSE) ? 2u : 0u;
+	e->hpc = (cfg->flags & NTC_FLAG_HPC) != 0;
 	e->masks.assign(nk, std::string());
 	e->kgap.assign(nk, 0u);
 	e->seeds.assign(nk, ntc::SeedPlan());
@@ -392,6 +395,8 @@ int ntc_reset(ntc_engine* e)
 	e->k1f_ms = 0.0;
 	e->long_cut_ms = e->long_gather_ms = 0.0;
 	e->long_pieces = e->long_seqs = 0;
+	e->hpc_ms = 0.0;
+	e->hpc_bytes_in = e->hpc_bytes_out = 0;
 	return 0;
 }
 
@@ -512,6 +517,17 @@ int ntc_long_time(ntc_engine* e, double* cut_ms, double* gather_ms)
 	if (int rc = timing(e, "ntc_long_time", &ntc_engine::long_cut_ms, cut_ms, &ntc_engine::applies, nullptr)) return rc;
 	return timing(e, "ntc_long_time", &ntc_engine::long_gather_ms, gather_ms, &ntc_engine::applies, nullptr);
 }
+
+int ntc_hpc_stats(ntc_engine* e, uint64_t* bytes_in, uint64_t* bytes_out)
+{
+	if (!e || !bytes_in || !bytes_out) return fail(NTC_ERR_ARG, "ntc_hpc_stats: null argument");
+	std::lock_guard<std::mutex> lk(e->mu);
+	*bytes_in = e->hpc_bytes_in;
+	*bytes_out = e->hpc_bytes_out;
+	return 0;
+}
+
+int ntc_hpc_time(ntc_engine* e, double* ms) { return timing(e, "ntc_hpc_time", &ntc_engine::hpc_ms, ms, &ntc_engine::applies, nullptr); }
 
 int ntc_update_mode(ntc_engine* e, uint32_t* mode_out)
 {

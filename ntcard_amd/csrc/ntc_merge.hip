@@ -110,7 +110,7 @@ int ntc_merge_devices(ntc_engine* const* engines, int32_t n_engines)
 	if (!root) return fail(NTC_ERR_ARG, "ntc_merge_devices: null engine");
 	for (int32_t i = 0; i < n_engines; ++i) {
 		ntc_engine* e = engines[i];
-		if (!e || e->klist != root->klist || e->masks != root->masks || e->strand != root->strand || e->r_bits != root->r_bits || e->s_bits != root->s_bits || e->hll_bits != root->hll_bits)
+		if (!e || e->klist != root->klist || e->masks != root->masks || e->strand != root->strand || e->hpc != root->hpc || e->r_bits != root->r_bits || e->s_bits != root->s_bits || e->hll_bits != root->hll_bits)
 			return fail(NTC_ERR_ARG, "ntc_merge_devices: engine %d is not configured like engine 0", i);
 		for (int32_t j = 0; j < i; ++j)
 			if (engines[j] == e) return fail(NTC_ERR_ARG, "ntc_merge_devices: engine %d listed twice", i);

@@ -477,6 +477,75 @@ template <class LenFn, class PtrFn> int submit_impl(ntc_engine* e, uint64_t n_re
 	return submit_rows_or_long(e, n_reads, len_of, ptr_of);
 }
 
+// ---- homopolymer compression (include/ntcard_hip.h: NTC_FLAG_HPC; DESIGN.md §4 "Homopolymer compression") ----
+constexpr uint64_t kHpcRoundBytes = 1ull << 30; // source bytes of one round of ntc_submit_long_device's compaction (NTC_HPC_ROUND_BYTES)
+
+int hpc_fixed_layout(const ntc_engine*, const char* who)
+{
+	return fail(NTC_ERR_ARG, "%s: a fixed-layout batch fixes every read's length, which homopolymer compression changes (NTC_FLAG_HPC): use ntc_submit, ntc_submit_spans or ntc_submit_long_device; nothing was counted", who);
+}
+
+// host reads: every read compressed into a temporary batch, which then takes submit_impl's routes — tiles, bins, rows, the path behind NTC_LONG_MIN
+template <class LenFn, class PtrFn> int submit_hpc_host(ntc_engine* e, uint64_t n_reads, const LenFn& len_of, const PtrFn& ptr_of)
+{
+	uint64_t total = 0;
+	for (uint64_t i = 0; i < n_reads; ++i)
+		total += len_of(i);
+	std::vector<char> buf(total ? total : 1);
+	std::vector<uint64_t> off(n_reads + 1, 0);
+	for (uint64_t i = 0; i < n_reads; ++i) {
+		uint64_t m = 0;
+		if (int rc = ntc_hpc_compress(ptr_of(i), len_of(i), buf.data() + off[i], &m)) return rc;
+		off[i + 1] = off[i] + m;
+	}
+	if (int rc = submit_impl(e, n_reads, [&](uint64_t i) { return off[i + 1] - off[i]; }, [&](uint64_t i) { return buf.data() + off[i]; })) return rc;
+	std::lock_guard<std::mutex> lk(e->mu);
+	e->hpc_bytes_in += total;
+	e->hpc_bytes_out += off[n_reads];
+	return 0;
+}
+
+// ntc_submit_long_device on an engine with the flag: rounds of whole sequences — compact into d_hpc, bring the new offsets back (the ONE wait per round:
+// the planner of the cut is host code), count (d_hpc, new offsets) exactly as the caller's buffer is counted without the flag.  The caller's source is
+// only read by the compaction, which is in the stream when the call returns.
+int submit_long_hpc(ntc_engine* e, const unsigned char* d_bases, const uint64_t* offsets, uint64_t n_seqs, uint32_t L)
+{
+	uint64_t budget = kHpcRoundBytes;
+	if (const char* ev = std::getenv("NTC_HPC_ROUND_BYTES")) budget = (uint64_t)std::max(1ll, std::strtoll(ev, nullptr, 10)); // tests: several rounds of a small input
+	std::lock_guard<std::mutex> hk(e->hpc_mu);
+	std::vector<uint64_t> noff;
+	for (uint64_t s0 = 0, s1; s0 < n_seqs; s0 = s1) {
+		for (s1 = s0 + 1; s1 < n_seqs && offsets[s1 + 1] - offsets[s0] <= budget;) // (a sequence beyond the budget is a round of its own)
+			++s1;
+		const uint64_t ns = s1 - s0, n = offsets[s1] - offsets[s0];
+		noff.assign(ns + 1, 0);
+		if (n != 0) {
+			std::lock_guard<std::mutex> lk(e->mu);
+			HIP_TRY(hipSetDevice(e->device));
+			const size_t aux_bytes = ntc::hpc_aux_bytes(n, ns);
+			if (n > e->d_hpc.cap || aux_bytes > e->d_hpc_aux.cap) {
+				HIP_TRY(hipStreamSynchronize(e->stream)); // (the round before may still be counting from the scratch)
+				if (!e->d_hpc.reserve(n) || !e->d_hpc_aux.reserve(aux_bytes))
+					return fail(NTC_ERR_MEMORY, "ntc_submit_long_device: cannot allocate %zu B of scratch for homopolymer compression on device", (size_t)n + aux_bytes);
+			}
+			if (int rc = close_run(e)) return rc;
+			Span sp;
+			if (int rc = open_span(e, sp)) return rc;
+			HIP_TRY(ntc::launch_hpc_compact(d_bases, offsets + s0, ns, e->d_hpc, e->d_hpc_aux.get(), e->stream));
+			if (int rc = close_span(sp, e->stream, e->hpc_events)) return rc;
+			HIP_TRY(hipMemcpyAsync(noff.data(), ntc::hpc_aux_offsets(e->d_hpc_aux.get(), ns), (ns + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+			HIP_TRY(hipStreamSynchronize(e->stream));
+			e->hpc_bytes_in += n;
+			e->hpc_bytes_out += noff[ns];
+		}
+		StageLease lease;
+		if (int rc = lease_stage(e, 0, lease)) return rc; // (its meta buffers hold the round's tables)
+		if (int rc = submit_long_leased(e, *lease.sl, e->d_hpc.get(), 0, ns, [&](uint64_t i) { return noff[i + 1] - noff[i]; }, [&](uint64_t i) { return noff[i]; }, L))
+			return rc;
+	}
+	return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -488,6 +557,7 @@ int ntc_submit(ntc_engine* e, const char* bases, const uint64_t* offsets, uint64
 	if (!bases || !offsets) return fail(NTC_ERR_ARG, "ntc_submit: null buffer");
 	for (uint64_t i = 0; i < n_reads; ++i)
 		if (offsets[i + 1] < offsets[i]) return fail(NTC_ERR_ARG, "ntc_submit: offsets not monotone at read %llu", (unsigned long long)i);
+	if (e->hpc) return submit_hpc_host(e, n_reads, [&](uint64_t i) { return offsets[i + 1] - offsets[i]; }, [&](uint64_t i) { return bases + offsets[i]; });
 	return submit_impl(e, n_reads, [&](uint64_t i) { return offsets[i + 1] - offsets[i]; }, [&](uint64_t i) { return bases + offsets[i]; });
 }
 
@@ -496,12 +566,14 @@ int ntc_submit_spans(ntc_engine* e, const char* buf, const uint64_t* starts, con
 	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_spans: null engine");
 	if (n_reads == 0) return 0;
 	if (!buf || !starts || !lens) return fail(NTC_ERR_ARG, "ntc_submit_spans: null buffer");
+	if (e->hpc) return submit_hpc_host(e, n_reads, [&](uint64_t i) { return (uint64_t)lens[i]; }, [&](uint64_t i) { return buf + starts[i]; });
 	return submit_impl(e, n_reads, [&](uint64_t i) { return (uint64_t)lens[i]; }, [&](uint64_t i) { return buf + starts[i]; });
 }
 
 int ntc_submit_device(ntc_engine* e, const void* d_slots, uint64_t n_reads, uint32_t read_len, uint32_t stride)
 {
 	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_device: null engine");
+	if (e->hpc) return hpc_fixed_layout(e, "ntc_submit_device");
 	if (n_reads == 0) return 0;
 	if (!d_slots || (stride & 3u) || stride < read_len || ((uintptr_t)d_slots & 15u))
 		return fail(NTC_ERR_ARG, "ntc_submit_device: need 16-byte aligned slots, stride %% 4 == 0, stride >= read_len");
@@ -527,6 +599,7 @@ int ntc_submit_long_device(ntc_engine* e, const void* d_bases, const uint64_t* o
 	const uint32_t L = piece_len ? piece_len : kLongPieceDefault;
 	if (fast && L < long_kmax(e) + 15u)
 		return fail(NTC_ERR_ARG, "ntc_submit_long_device: piece_len %u below k + 15 = %u (k: the largest of the list)", L, long_kmax(e) + 15u);
+	if (e->hpc) return submit_long_hpc(e, (const unsigned char*)d_bases, offsets, n_seqs, L);
 	StageLease lease;
 	if (int rc = lease_stage(e, 0, lease)) return rc; // (its meta buffers hold the call's tables)
 	return submit_long_leased(e, *lease.sl, (const unsigned char*)d_bases, 0, n_seqs, [&](uint64_t i) { return offsets[i + 1] - offsets[i]; },
@@ -536,6 +609,7 @@ int ntc_submit_long_device(ntc_engine* e, const void* d_bases, const uint64_t* o
 int ntc_submit_tiled_device(ntc_engine* e, const void* d_tiles, uint64_t n_reads, uint32_t read_len)
 {
 	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_tiled_device: null engine");
+	if (e->hpc) return hpc_fixed_layout(e, "ntc_submit_tiled_device");
 	if (n_reads == 0) return 0;
 	if (!d_tiles || ((uintptr_t)d_tiles & 15u)) return fail(NTC_ERR_ARG, "ntc_submit_tiled_device: need a 16-byte aligned buffer");
 	if (read_len == 0 || read_len > 0xffffu) return fail(NTC_ERR_ARG, "ntc_submit_tiled_device: read_len %u outside 1..65535", read_len);
@@ -547,6 +621,7 @@ int ntc_submit_tiled_device(ntc_engine* e, const void* d_tiles, uint64_t n_reads
 int ntc_submit_tiled_ragged_device(ntc_engine* e, const void* d_tiles, uint64_t n_reads, uint32_t n_chunks, const uint32_t* d_tails)
 {
 	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: null engine");
+	if (e->hpc) return hpc_fixed_layout(e, "ntc_submit_tiled_ragged_device");
 	if (n_reads == 0) return 0;
 	if (!d_tiles || ((uintptr_t)d_tiles & 15u) || !d_tails || ((uintptr_t)d_tails & 3u)) return fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: need a 16-byte aligned tile buffer and a tails array");
 	if (n_chunks == 0 || n_chunks > 0xffffu / 16u) return fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: n_chunks %u outside 1..4095", n_chunks);
@@ -559,6 +634,7 @@ int ntc_submit_tiled_bins_device(ntc_engine* e, uint32_t n_bins, const void* con
                                  const uint32_t* const* d_tails)
 {
 	if (!e) return fail(NTC_ERR_ARG, "ntc_submit_tiled_bins_device: null engine");
+	if (e->hpc) return hpc_fixed_layout(e, "ntc_submit_tiled_bins_device");
 	if (n_bins == 0) return 0;
 	if (!d_tiles || !n_reads || !read_len) return fail(NTC_ERR_ARG, "ntc_submit_tiled_bins_device: null argument"); // (d_tails == NULL: every bin is equal-length)
 	std::vector<TiledSeg> segs;

@@ -51,6 +51,8 @@ void usage(std::ostream& os)
 	   << "      --strand-kernel=tiled|general\twhich kernels count a forward or reverse run [tiled]: the one-strand tiled kernels where every k-mer length\n"
 	   << "\t\tof the run is theirs (k = 12 .. 32, -g 2 at k = 12, -g 8 at k = 32), or the general kernel throughout (A/B runs); the output is the same;\n"
 	   << "\t\tno effect (and a warning) without --strand=forward|reverse\n"
+	   << "      --hpc\tcount homopolymer-compressed k-mers: every run of one base (A, C, G, T = U, either case) is collapsed to its first letter before the\n"
+	   << "\t\tk-mers are taken (N and other letters are kept and break runs); with -k, -g, --seed and --strand; output files unchanged\n"
 	   << "      --help\tdisplay this help and exit\n"
 	   << "      --version\toutput version information and exit\n";
 }
@@ -67,6 +69,7 @@ struct Options {
 	std::vector<std::string> seeds; // --seed: masks of '0' / '1' (include/ntcard_hip.h: ntc_create_seeded)
 	uint32_t strand_flag = 0;       // --strand: NTC_FLAG_STRAND_FORWARD / _REVERSE, 0 = canonical
 	bool strand_tiled = true;       // --strand-kernel: NTC_FLAG_STRAND_TILED beside a strand flag
+	bool hpc = false;               // --hpc: NTC_FLAG_HPC
 };
 
 void process_file(const std::string& path, ntc_engine* eng)
@@ -96,7 +99,7 @@ int main(int argc, char** argv)
 {
 	const auto t_start = std::chrono::steady_clock::now();
 	static const char shortopts[] = "t:s:r:k:c:l:p:f:o:g:";
-	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED, OPT_STRAND, OPT_STRAND_KERNEL };
+	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED, OPT_STRAND, OPT_STRAND_KERNEL, OPT_HPC };
 	bool strand_kernel_given = false;
 	static const struct option longopts[] = { { "threads", required_argument, nullptr, 't' },
 		                                      { "kmer", required_argument, nullptr, 'k' },
@@ -111,6 +114,7 @@ int main(int argc, char** argv)
 		                                      { "seed", required_argument, nullptr, OPT_SEED },
 		                                      { "strand", required_argument, nullptr, OPT_STRAND },
 		                                      { "strand-kernel", required_argument, nullptr, OPT_STRAND_KERNEL },
+		                                      { "hpc", no_argument, nullptr, OPT_HPC },
 		                                      { nullptr, 0, nullptr, 0 } };
 	Options opt;
 	bool die = false;
@@ -166,6 +170,7 @@ int main(int argc, char** argv)
 			}
 			break;
 		}
+		case OPT_HPC: opt.hpc = true; break;
 		case 'k': {
 			std::istringstream arg(optarg ? optarg : "");
 			std::string token;
@@ -278,7 +283,7 @@ int main(int argc, char** argv)
 	cfg.r_bits = opt.r_bits;
 	cfg.s_bits = opt.s_bits;
 	if (strand_kernel_given && !opt.strand_flag) std::cerr << PROGRAM << ": warning: --strand-kernel has no effect on a canonical run (no --strand=forward|reverse)\n";
-	cfg.flags = opt.strand_flag | (opt.strand_flag && opt.strand_tiled ? NTC_FLAG_STRAND_TILED : 0u);
+	cfg.flags = opt.strand_flag | (opt.strand_flag && opt.strand_tiled ? NTC_FLAG_STRAND_TILED : 0u) | (opt.hpc ? NTC_FLAG_HPC : 0u);
 	// Devices: NTCARD_DEVICES="0,1,2,..." spreads the input files over several GPUs (one private sketch each, merged
 	// at the end: counting is a commutative sum); NTCARD_DEVICE=<n> or nothing selects a single one.
 	std::vector<int> devices;

@@ -45,7 +45,7 @@ void process_file(const std::string& path, ntc_engine* eng)
 int main(int argc, char** argv)
 {
 	static const char shortopts[] = "t:k:b:s:hc";
-	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED, OPT_STRAND };
+	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED, OPT_STRAND, OPT_HPC };
 	static const struct option longopts[] = { { "threads", required_argument, nullptr, 't' },
 		                                      { "kmer", required_argument, nullptr, 'k' },
 		                                      { "bit", required_argument, nullptr, 'b' },
@@ -55,11 +55,13 @@ int main(int argc, char** argv)
 		                                      { "version", no_argument, nullptr, OPT_VERSION },
 		                                      { "seed", required_argument, nullptr, OPT_SEED },
 		                                      { "strand", required_argument, nullptr, OPT_STRAND },
+		                                      { "hpc", no_argument, nullptr, OPT_HPC },
 		                                      { nullptr, 0, nullptr, 0 } };
 	unsigned threads = 1, n_bits = 16, s_unused = 22;
 	std::vector<uint32_t> klist;    // -k K[,K...] (none given: 64)
 	std::vector<std::string> seeds; // --seed: masks of '0' / '1' (include/ntcard_hip.h: ntc_hll_create_ex)
 	uint32_t strand = 0;            // --strand: 0 canonical, 1 forward, 2 reverse
+	bool hpc = false;               // --hpc: NTC_FLAG_HPC
 	bool die = false;
 	for (int c; (c = getopt_long(argc, argv, shortopts, longopts, nullptr)) != -1;) {
 		bool clean = true;
@@ -105,6 +107,7 @@ int main(int argc, char** argv)
 			}
 			break;
 		}
+		case OPT_HPC: hpc = true; break;
 		case 'c': break; // canonical hashing is always on (nthll.cpp:51,167-169)
 		case OPT_HELP:
 			std::cerr << "Usage: nthll [OPTION]... FILE(S)...\n"
@@ -113,6 +116,7 @@ int main(int argc, char** argv)
 			          << "  -b, --bit=N\tlog2 of the number of registers [16]\n"
 			          << "      --seed=MASK[,MASK...]\tspaced seeds instead of -k: strings of 0 (don't care) and 1 (counted), one result line each\n"
 			          << "      --strand=canonical|forward|reverse\twhich value of a k-mer is hashed [canonical]\n"
+			          << "      --hpc\thash homopolymer-compressed k-mers: every run of one base is collapsed to its first letter before the k-mers are taken\n"
 			          << "      --help\tdisplay this help and exit\n      --version\toutput version information and exit\n";
 			return EXIT_SUCCESS;
 		case OPT_VERSION:
@@ -186,7 +190,7 @@ int main(int argc, char** argv)
 	}
 	cfg.n_bits = n_bits;
 	cfg.device = device;
-	cfg.flags = strand == 1 ? NTC_FLAG_STRAND_FORWARD : strand == 2 ? NTC_FLAG_STRAND_REVERSE : 0u;
+	cfg.flags = (strand == 1 ? NTC_FLAG_STRAND_FORWARD : strand == 2 ? NTC_FLAG_STRAND_REVERSE : 0u) | (hpc ? NTC_FLAG_HPC : 0u);
 	ntc_engine* eng = nullptr;
 	if (ntc_hll_create_ex(&cfg, &eng) != 0) die_engine();
 	std::atomic<size_t> next(0);

@@ -23,6 +23,7 @@ FLAG_DIRECT_ATOMICS = 2  # NTC_FLAG_DIRECT_ATOMICS: no hit log, one device atomi
 FLAG_STRAND_FORWARD = 512  # NTC_FLAG_STRAND_FORWARD: count the forward value fh of every window instead of the canonical min(fh, rh)
 FLAG_STRAND_REVERSE = 1024  # NTC_FLAG_STRAND_REVERSE: count the reverse value rh (the forward value of the window's reverse complement)
 FLAG_STRAND_TILED = 4096  # NTC_FLAG_STRAND_TILED: a one-strand engine whose planes are all the tiled kernels' counts on the one-strand K1h + K1f instead of K1
+FLAG_HPC = 8192  # NTC_FLAG_HPC: homopolymer-compressed counting — every run of one base is collapsed to its first byte before the windows are taken
 _STRAND_FLAGS = {"canonical": 0, "forward": FLAG_STRAND_FORWARD, "reverse": FLAG_STRAND_REVERSE}
 SIZE_RULE_BYTES = 50_000_000_000  # ntcard.cpp:430: total input < 50 GB => sBits = 7
 
@@ -56,12 +57,13 @@ def _strand_flags(flags, strand, strand_tiled=False):
 
 class Engine:
     def __init__(self, klist, gap=0, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0, strand=None,
-                 strand_tiled=False):
+                 strand_tiled=False, hpc=False):
         """strand: "canonical" (the default, what ntcard counts), "forward" or "reverse" — which value of a window is counted
         (include/ntcard_hip.h: NTC_FLAG_STRAND_FORWARD / _REVERSE).  strand_tiled: a one-strand engine whose planes are all the tiled kernels' (plain
         k = 12 .. 32, the two tiled gap seeds, sBits >= 7) counts on the one-strand K1h + K1f instead of the general kernel (NTC_FLAG_STRAND_TILED;
-        the results are the same)"""
-        flags = _strand_flags(flags, strand, strand_tiled)
+        the results are the same).  hpc: count homopolymer-compressed sequences (NTC_FLAG_HPC: submit / submit_spans compress on the host,
+        submit_long_device on the device; the fixed-layout device batches are refused)"""
+        flags = _strand_flags(flags, strand, strand_tiled) | (FLAG_HPC if hpc else 0)
         self._lib = _abi.lib()
         self.klist = [int(k) for k in klist]
         self.gap, self.r_bits, self.s_bits, self.device = int(gap), int(r_bits), int(s_bits), int(device)
@@ -83,10 +85,10 @@ class Engine:
 
     @classmethod
     def from_seeds(cls, seeds, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0, strand=None,
-                   strand_tiled=False):
+                   strand_tiled=False, hpc=False):
         """an engine whose planes are spaced seeds given as masks of '0' / '1' (include/ntcard_hip.h: ntc_create_seeded); its klist is
-        the masks' lengths, so finish, merge_counters and the rest work as for a k list; strand and strand_tiled as for Engine()"""
-        flags = _strand_flags(flags, strand, strand_tiled)
+        the masks' lengths, so finish, merge_counters and the rest work as for a k list; strand, strand_tiled and hpc as for Engine()"""
+        flags = _strand_flags(flags, strand, strand_tiled) | (FLAG_HPC if hpc else 0)
         self = cls.__new__(cls)
         self._lib = _abi.lib()
         self.seeds = [s.decode() if isinstance(s, bytes) else str(s) for s in seeds]
@@ -195,6 +197,18 @@ class Engine:
         check(self._lib.ntc_long_time(self._h, C.byref(cut), C.byref(gather)))
         return cut.value, gather.value
 
+    def hpc_stats(self):
+        """-> (sequence bytes given, bytes kept) by homopolymer compression since create / reset; (0, 0) on an engine without hpc=True (ntc_hpc_stats)"""
+        b_in, b_out = C.c_uint64(), C.c_uint64()
+        check(self._lib.ntc_hpc_stats(self._h, C.byref(b_in), C.byref(b_out)))
+        return b_in.value, b_out.value
+
+    def hpc_time(self):
+        """-> ms of submit_long_device's compaction kernels while profiling (ntc_hpc_time)"""
+        ms = C.c_double()
+        check(self._lib.ntc_hpc_time(self._h, C.byref(ms)))
+        return ms.value
+
     def sync(self):
         check(self._lib.ntc_sync(self._h))
 
@@ -276,21 +290,21 @@ class HllEngine(Engine):
     or a list of k (finish() -> (regs [n_planes, 1<<n_bits], f1 uint64[n_planes])); from_seeds: spaced seeds given as masks; strand as for Engine()
     (include/ntcard_hip.h: ntc_hll_create_ex)"""
 
-    def __init__(self, k, n_bits=16, device=0, stream=None, strand="canonical"):
+    def __init__(self, k, n_bits=16, device=0, stream=None, strand="canonical", hpc=False):
         single = not isinstance(k, (list, tuple, np.ndarray))
-        self._setup([int(k)] if single else [int(x) for x in k], None, n_bits, device, stream, strand, single)
+        self._setup([int(k)] if single else [int(x) for x in k], None, n_bits, device, stream, strand, single, hpc)
 
     @classmethod
-    def from_seeds(cls, masks, n_bits=16, device=0, stream=None, strand="canonical"):
+    def from_seeds(cls, masks, n_bits=16, device=0, stream=None, strand="canonical", hpc=False):
         self = cls.__new__(cls)
         self._h = None
         seeds = [s.decode() if isinstance(s, bytes) else str(s) for s in masks]
-        self._setup([len(s) for s in seeds], seeds, n_bits, device, stream, strand, False)
+        self._setup([len(s) for s in seeds], seeds, n_bits, device, stream, strand, False, hpc)
         return self
 
-    def _setup(self, klist, seeds, n_bits, device, stream, strand, single):
+    def _setup(self, klist, seeds, n_bits, device, stream, strand, single, hpc=False):
         self._h = None
-        flags = _strand_flags(0, strand)  # (checked before the library is asked for a device)
+        flags = _strand_flags(0, strand) | (FLAG_HPC if hpc else 0)  # (checked before the library is asked for a device)
         self._lib = _abi.lib()
         self.klist, self.seeds, self.gap, self.n_bits, self.device = klist, seeds, 0, int(n_bits), int(device)
         self.strand = "canonical" if strand is None else strand
@@ -363,6 +377,26 @@ def long_plan(k, piece_len, n):
     m, rem = C.c_uint64(), C.c_uint64()
     check(_abi.lib().ntc_long_plan(int(k), int(piece_len), int(n), C.byref(m), C.byref(rem)))
     return m.value, rem.value
+
+
+def hpc_compress(seq):
+    """homopolymer compression of one sequence (bytes) -> bytes: every byte that repeats the base class (A, C, G, T = U, either case) of the byte in front
+    of it is dropped (ntc_hpc_compress, host only)"""
+    a = np.frombuffer(bytes(seq), dtype=np.uint8)
+    out = np.empty(max(a.size, 1), dtype=np.uint8)
+    n = C.c_uint64()
+    check(_abi.lib().ntc_hpc_compress(_np_ptr(a) if a.size else None, a.size, _np_ptr(out), C.byref(n)))
+    return out[:n.value].tobytes()
+
+
+def hpc_compress_device(d_in_ptr, offsets, d_out_ptr, device=0, stream=None):
+    """the same for device-resident sequences [offsets[i], offsets[i + 1]) of d_in (host offsets, any alignment) into d_out (room for
+    offsets[-1] - offsets[0] bytes) -> the new offsets, uint64[n + 1] from 0; synchronous (ntc_hpc_compress_device)"""
+    o = np.ascontiguousarray(offsets, dtype=np.uint64)
+    out = np.zeros(len(o), dtype=np.uint64)
+    check(_abi.lib().ntc_hpc_compress_device(device, C.c_void_p(stream) if stream else None, C.c_void_p(d_in_ptr) if d_in_ptr else None, _np_ptr(o),
+                                             len(o) - 1, C.c_void_p(d_out_ptr) if d_out_ptr else None, _np_ptr(out)))
+    return out
 
 
 def tiled_bytes(n_reads, read_len):
