@@ -39,6 +39,22 @@ def model(seqs):
     return [compress(s) for s in seqs]
 
 
+def compress_many(buf, offsets):
+    """the sequences [offsets[i], offsets[i + 1]) of buf (uint8 array) in ONE vectorised pass -> (their compressed forms behind one another, the new
+    offsets from 0): the keep rule over the whole concatenation, with every sequence's first byte forced to "kept" (a run never continues across a
+    boundary).  For inputs of megabytes and of hundreds of thousands of sequences; tests/test_hpc_host.py pins it to compress() per sequence"""
+    offs = np.asarray(offsets, dtype=np.uint64).astype(np.int64)
+    a = np.asarray(buf, dtype=np.uint8)[offs[0]:offs[-1]]
+    c = CLASS[a]
+    keep = np.ones(a.size, dtype=bool)
+    keep[1:] = ~((c[1:] != NONE) & (c[1:] == c[:-1]))
+    starts = offs[:-1] - offs[0]
+    keep[starts[starts < a.size]] = True  # (empty sequences at the very end start nowhere)
+    pre = np.zeros(a.size + 1, dtype=np.uint64)
+    np.cumsum(keep, dtype=np.uint64, out=pre[1:])
+    return a[keep], pre[offs - offs[0]]
+
+
 def offsets_of(seqs, lead=0):
     offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
     offs[0] = lead
@@ -132,3 +148,83 @@ def slot_piece_set(k=32, piece_len=48):
         out.append(b"".join(bytes([b]) * (rng.randrange(1, 4) if CLASS[b] != NONE else 1) for b in s))
         assert compress(out[-1]) == bytes(s)
     return tuple(out)
+
+
+# ---- inputs beyond the compaction kernels' thresholds (tests/test_hpc_gpu.py; ntc_hpc.hip) ----
+CHUNK = 4096          # positions of a wave's chunk (kHpcChunk)
+SCAN_THREADS = 1024   # hpc_scan_kernel: one workgroup; thread t sums `per` = ceil(chunks / 1024) chunks
+SEQ_THREADS = 2048 * 256  # hpc_mark_kernel / hpc_offsets_kernel: at most 2048 workgroups of 256 threads, a thread per offset and turn
+
+
+def chunks_of(lead, n):
+    """chunks of a compaction of n bytes whose first byte sits `lead` bytes behind an aligned dword (launch_hpc_compact)"""
+    words = (lead + n + 3) // 4
+    return (words + CHUNK // 4 - 1) // (CHUNK // 4)
+
+
+def runs_array(gen, n, p_more=0.5, p_low=0.1, p_other=0.01):
+    """runs_seq in numpy, for megabytes: n bytes (uint8 array) of runs of one base with a geometric length, case flips inside, bytes without a class"""
+    base = np.frombuffer(b"ACGTU", dtype=np.uint8)[gen.integers(0, 5, size=n)]
+    a = np.repeat(base, gen.geometric(1.0 - p_more, size=n))[:n].copy()
+    a[gen.random(n) < p_low] |= 0x20
+    other = np.flatnonzero(gen.random(n) < p_other)
+    a[other] = np.frombuffer(b"NnR\r\x01\x03", dtype=np.uint8)[gen.integers(0, 6, size=other.size)]
+    assert a.size == n
+    return a
+
+
+def lens_offsets(lens):
+    offs = np.zeros(len(lens) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(lens, dtype=np.uint64)
+    return offs
+
+
+@functools.lru_cache(maxsize=None)
+def pair_seq():
+    """one sequence that holds every ordered pair of byte values: (a, b) for a, b = 0 .. 255 behind one another, 131072 bytes"""
+    a = np.repeat(np.arange(256, dtype=np.uint8), 256)
+    b = np.tile(np.arange(256, dtype=np.uint8), 256)
+    s = np.stack([a, b], axis=1).reshape(-1)
+    return s, np.array([0, s.size], dtype=np.uint64)
+
+
+@functools.lru_cache(maxsize=None)
+def pair_seqs():
+    """the same pairs as 65536 sequences of two bytes"""
+    return pair_seq()[0], np.arange(65537, dtype=np.uint64) * np.uint64(2)
+
+
+def pair_want():
+    """what the definition leaves of the pair (a, b) as a sequence of its own, for every pair: a alone iff b repeats a's class -> (bytes, offsets)"""
+    s = pair_seq()[0].reshape(-1, 2)
+    drop = (CLASS[s[:, 1]] != NONE) & (CLASS[s[:, 1]] == CLASS[s[:, 0]])
+    keep = np.ones(s.shape, dtype=bool)
+    keep[:, 1] = ~drop
+    return s[keep], lens_offsets(2 - drop.astype(np.int64))
+
+
+@functools.lru_cache(maxsize=None)
+def many_short():
+    """530 000 sequences of 0 .. 20 bytes over ACGTacgtUuNR, 5.3 MB: more sequences than the mark and offsets kernels have threads, more chunks than the scan
+    kernel has threads"""
+    gen = np.random.default_rng(530)
+    offs = lens_offsets(gen.integers(0, 21, size=530_000))
+    return np.frombuffer(b"ACGTacgtUuNR", dtype=np.uint8)[gen.integers(0, 12, size=int(offs[-1]))], offs
+
+
+@functools.lru_cache(maxsize=None)
+def three_seqs(total):
+    """three sequences of `total` bytes in all; a run of G / g covers the last 5000 bytes and the join of the second and the third sequence 2000 bytes
+    in front of the end (the byte behind the join is kept, the rest of the run is not)"""
+    gen = np.random.default_rng(total % 1000)
+    a = runs_array(gen, total)
+    a[total - 5000:] = np.frombuffer(b"GGGg", dtype=np.uint8)[gen.integers(0, 4, size=5000)]
+    return a, np.array([0, 1_500_000, total - 2000, total], dtype=np.uint64)
+
+
+@functools.lru_cache(maxsize=None)
+def few_large():
+    """about 8.5 MiB in four sequences"""
+    gen = np.random.default_rng(85)
+    lens = [3_000_001, 2_500_003, 7, 3_412_000]
+    return runs_array(gen, sum(lens)), lens_offsets(lens)

@@ -87,7 +87,7 @@ def same(got, want):
 
 # ---- the compaction itself ----
 @pytest.mark.parametrize("lead", [0, 1, 2, 3])
-@pytest.mark.parametrize("out_lead", [0, 1])
+@pytest.mark.parametrize("out_lead", [0, 1, 2, 3])
 def test_compress_device_matches_the_model(nt, lead, out_lead):
     d, offs = on_device(lead, raw=True)
     raw, want_seqs = hm.device_set(), hm.model(hm.device_set())
@@ -111,6 +111,79 @@ def test_compress_device_subrange_and_empty(nt):
     c = hm.model(hm.device_set())[5:19]
     assert np.array_equal(new, hm.offsets_of(c)) and out.cpu().numpy()[:int(new[-1])].tobytes() == b"".join(c)
     assert np.array_equal(nt.hpc_compress_device(d.data_ptr(), offs[1:3] * 0 + offs[1], out.data_ptr()), [0, 0])
+
+
+# ---- the compaction beyond its kernels' thresholds (hpc_model.compress_many is the model: tests/test_hpc_host.py pins it to compress() per sequence) ----
+def compress_on_device(nt, buf, offs, lead=3, out_lead=0):
+    """the sequences [offs[i], offs[i + 1]) of buf through ntc_hpc_compress_device, `lead` bytes behind an aligned address: offsets and bytes against
+    the model, nothing written outside the result -> the chunks of the compaction"""
+    host = np.concatenate([np.full(lead, 0x23, dtype=np.uint8), buf, np.full(1, 0x23, dtype=np.uint8)])
+    d = torch.from_numpy(host).cuda()
+    assert d.data_ptr() % 4 == 0 and int(offs[0]) == 0  # (the source's phase in its dword is `lead`)
+    out = torch.full((buf.size + 8,), 0x23, dtype=torch.uint8, device="cuda")
+    new = nt.hpc_compress_device(d.data_ptr(), offs + np.uint64(lead), out.data_ptr() + out_lead)
+    want, want_offs = hm.compress_many(buf, offs)
+    assert 0 < want.size < buf.size
+    assert np.array_equal(new, want_offs)
+    got = out.cpu().numpy()
+    assert np.array_equal(got[out_lead:out_lead + want.size], want)
+    assert np.all(got[:out_lead] == 0x23) and np.all(got[out_lead + want.size:] == 0x23)
+    return hm.chunks_of(lead, buf.size)
+
+
+@pytest.mark.parametrize("lead", [0, 3])
+def test_every_pair_of_byte_values_on_the_device(nt, lead):
+    """hpc_class on all 256 values, in front of and behind every other: as one sequence and as 65536 sequences of two bytes"""
+    compress_on_device(nt, *hm.pair_seq(), lead=lead)
+    compress_on_device(nt, *hm.pair_seqs(), lead=lead, out_lead=1)
+    want, want_offs = hm.pair_want()
+    got, got_offs = hm.compress_many(*hm.pair_seqs())
+    assert np.array_equal(got, want) and np.array_equal(got_offs, want_offs)  # (the model against the definition, pair by pair)
+
+
+def test_more_sequences_than_threads_and_more_chunks_than_scan_threads(nt):
+    buf, offs = hm.many_short()
+    assert len(offs) > hm.SEQ_THREADS  # ntc_hpc.hip:261: the stride loops of hpc_mark_kernel and hpc_offsets_kernel take a second turn
+    n_chunks = compress_on_device(nt, buf, offs)
+    assert n_chunks > hm.SCAN_THREADS  # ntc_hpc.hip:117: per = 2, a thread of hpc_scan_kernel owns two chunks
+
+
+@pytest.mark.parametrize("extra,chunks", [(0, 1024), (1, 1025), (5, 1025)])
+def test_scan_at_one_chunk_per_thread_and_just_beyond(nt, extra, chunks):
+    """lead + total = 4 194 304 + extra: 1024 chunks are the last size with one chunk per thread of the scan, 1025 the first with two (the last chunk then
+    holds one or five positions); a run of G lies across the last 4096 positions, the chunk boundary at 4 194 304 and the join of two sequences"""
+    lead = 3
+    buf, offs = hm.three_seqs(4_194_304 - lead + extra)
+    assert lead + buf.size == 4_194_304 + extra
+    assert np.all((buf[-5000:] | 0x20) == ord("g")) and buf.size - 4096 < int(offs[2]) < buf.size
+    n_chunks = compress_on_device(nt, buf, offs, lead=lead, out_lead=extra % 4)
+    assert n_chunks == chunks and (n_chunks + 1023) // 1024 == (1 if extra == 0 else 2)  # ntc_hpc.hip:117
+
+
+def test_scan_with_three_chunks_per_thread(nt):
+    buf, offs = hm.few_large()
+    n_chunks = compress_on_device(nt, buf, offs, lead=1, out_lead=2)
+    per = (n_chunks + 1023) // 1024
+    assert per == 3 and per * 1023 >= n_chunks  # ntc_hpc.hip:117-118: the trailing threads of the scan have no chunk
+
+
+def test_engine_counts_many_short_sequences(nt):
+    """Engine([12], hpc=True) on the 530 000 short sequences: a compaction beyond both thresholds, then — no compressed sequence holds a piece — a gather
+    launch of more row slots than it has waves (ntc_long.hip:143), against the oracle run on the model's output"""
+    buf, offs = hm.many_short()
+    want, want_offs = hm.compress_many(buf, offs)
+    lens = np.diff(want_offs).astype(np.int64)
+    assert len(lens) > 8192 * 4 and lens.max() >= 12 and lens.max() < 1008  # every sequence a row slot, none a piece
+    oc = np.zeros((1, 2, 1 << R), dtype=np.uint16)
+    of1 = orc.sketch_update(oc, want, want_offs, [12], 0, R, S_BITS)
+    assert int(of1[0]) > 0
+    d = torch.from_numpy(np.concatenate([np.full(3, 0x23, dtype=np.uint8), buf, np.full(1, 0x23, dtype=np.uint8)])).cuda()
+    with nt.Engine([12], r_bits=R, s_bits=S_BITS, hpc=True) as e:
+        e.submit_long_device(d.data_ptr(), offs + np.uint64(3))
+        tc, _, f1 = e.finish(counters=True)
+        assert e.hpc_stats() == (buf.size, want.size) and e.long_stats() == (0, 0)
+    assert np.array_equal(f1, of1), (f1, of1)
+    assert np.array_equal(tc, oc)
 
 
 # ---- engines that qualify for the cut ----

@@ -54,6 +54,29 @@ def test_the_device_set_holds_what_the_gpu_tests_say():
                 assert any(hm.CLASS[s0[j]] == hm.CLASS[s0[j + 1]] == hm.CLASS[s0[j + 2]] for j in range(3, len(s0) - 3) if (lead + j - d) % B == 0), (B, lead, d)
 
 
+def test_compress_many_is_compress_per_sequence():
+    """the one-pass model of the large GPU inputs against compress() sequence by sequence: on the device set (with and without bytes in front of the first
+    offset) and on a sample of the 530 000 short sequences"""
+    seqs = hm.device_set()
+    want = hm.model(seqs)
+    for lead in (0, 3):
+        buf = np.frombuffer(b"G" * lead + b"".join(seqs), dtype=np.uint8)
+        out, offs = hm.compress_many(buf, hm.offsets_of(seqs, lead))
+        assert offs.dtype == np.uint64 and np.array_equal(offs, hm.offsets_of(want)) and out.tobytes() == b"".join(want)
+    buf, offs = hm.many_short()
+    out, new = hm.compress_many(buf, offs)
+    assert len(offs) - 1 == 530_000 and int(np.diff(offs).max()) == 20 and int(np.diff(offs).min()) == 0
+    for i in list(range(3000)) + list(range(len(offs) - 3000, len(offs) - 1)):
+        assert hm.compress(buf[int(offs[i]):int(offs[i + 1])].tobytes()) == out[int(new[i]):int(new[i + 1])].tobytes(), i
+    sub, sub_offs = hm.compress_many(buf, offs[1000:2001])  # a call that starts in the middle of the buffer
+    assert np.array_equal(sub_offs, new[1000:2001] - new[1000]) and np.array_equal(sub, out[int(new[1000]):int(new[2000])])
+    for total in (4_194_301, 4_194_306):
+        a, o = hm.three_seqs(total)
+        c, no = hm.compress_many(a, o)
+        assert c.tobytes() == b"".join(hm.compress(a[int(o[i]):int(o[i + 1])].tobytes()) for i in range(3))
+        assert int(no[3] - no[2]) == 1 and (a[int(o[2]) - 1] | 0x20) == ord("g")  # the run goes on across the join: its first byte behind it is kept, alone
+
+
 # ---- ntc_hpc_compress ----
 def c_compress(seq, in_place=False):
     L = _abi.lib()
@@ -76,6 +99,24 @@ def test_compress_matches_the_model(in_place):
         assert c_compress(s, in_place) == hm.compress(s), s
     assert c_compress(b"G" * 1000, in_place) == b"G" and c_compress(b"TtUu", in_place) == b"T" and c_compress(b"NNN", in_place) == b"NNN"
     assert c_compress(b"aAAa", in_place) == b"a"
+
+
+def test_every_pair_of_byte_values():
+    """ntc_hpc_compress on all 256 byte values in front of and behind every other: one sequence that holds every ordered pair, and every pair as a
+    sequence of its own — against the definition, pair by pair"""
+    seq, _ = hm.pair_seq()
+    pairs = {(int(seq[j]), int(seq[j + 1])) for j in range(0, seq.size, 2)}
+    assert len(pairs) == 65536 and seq.size == 131072
+    for in_place in (False, True):
+        assert c_compress(seq.tobytes(), in_place) == hm.compress(seq.tobytes()) == hm.compress_slow(seq.tobytes())
+    want, offs = hm.pair_want()
+    assert int(offs[-1]) == 131072 - 28  # (4 + 4 + 4 + 16 ordered pairs of one class)
+    raw = seq.tobytes()
+    for i in range(65536):
+        got = c_compress(raw[2 * i:2 * i + 2])
+        assert got == want[int(offs[i]):int(offs[i + 1])].tobytes(), (raw[2 * i], raw[2 * i + 1], got)
+    got, got_offs = hm.compress_many(*hm.pair_seqs())
+    assert np.array_equal(got, want) and np.array_equal(got_offs, offs)
 
 
 def test_python_compress():

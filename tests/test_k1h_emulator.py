@@ -63,7 +63,8 @@ def run_ragged(n, C, k, p_bad=0.0, r_bits=14, n_waves=2, seed=1, s_bits=7, gap=0
 
 
 @pytest.mark.parametrize("n,C,k,p_bad,n_waves", [(2048, 10, 32, 0.0, 2), (5000, 10, 32, 0.003, 3), (3000, 3, 32, 0.01, 2), (2100, 4, 25, 0.01, 2),
-                                                 (2500, 2, 12, 0.02, 2), (4100, 5, 17, 0.0, 4), (2048, 3, 31, 0.02, 1), (2048, 2, 20, 0.01, 2), (2300, 1, 12, 0.0, 2)])
+                                                 (2500, 2, 12, 0.02, 2), (4100, 5, 17, 0.0, 4), (2048, 3, 31, 0.02, 1), (2048, 2, 20, 0.01, 2), (2300, 1, 12, 0.0, 2),
+                                                 (70, 257, 32, 0.001, 2)])  # (the smallest ragged batch whose chunk index needs nine bits)
 def test_k1h_emulated_ragged_batches(n, C, k, p_bad, n_waves):
     """reads of unequal length (ntRead takes any string, ntcard.cpp:173-189): a batch of reads 16 C - 15 .. 16 C bases long, tiles sorted longest first,
     the steps that end in the last piece masked to the prefix of the tile that is long enough (gen_k1h.Gen.emit_tail_step)"""
@@ -75,6 +76,7 @@ def test_k1h_emulated_ragged_batches(n, C, k, p_bad, n_waves):
     (4097, 47, 32, 0.02, 3),      # a partial last tile of one read
     (2100, 64, 25, 0.01, 2), (2049, 33, 20, 0.0, 2), (3000, 30, 16, 0.01, 2), (2500, 20, 12, 0.02, 2),  # other k: window start chunk, phase, table groups
     (1, 150, 32, 0.0, 2), (2048, 160, 32, 0.001, 2),  # a virtual chunk behind the read (blocks = chunks + 1)
+    (70, 4112, 32, 0.001, 2),     # 257 chunks: the smallest read length whose chunk index needs nine bits
 ])
 def test_k1h_emulated_matches_oracle(n, L, k, p_bad, n_waves):
     run(n, L, k, p_bad, n_waves=n_waves)
