@@ -139,6 +139,30 @@ typedef struct {
  *     counted without the flag into an engine with it (or the other way round) is the caller's mistake to avoid.  The dump and generator tools ignore it.
  * (Bits 4, 256, 2048 and 1 << 20 stay refused as unknown flags.) */
 #define NTC_FLAG_HPC 8192u
+/* SIGNATURES (additive to ABI 6: one flag bit, the ntc_signature* calls and ntc_sig_header; ntc_config and NTC_ABI_VERSION are unchanged).  The engine keeps,
+ * per plane (a k of the list, or a mask), every value h it hands to ntComp (ntcard.cpp:132-145) that ntComp SAMPLES —
+ *     sample 0: (h >> (63 - s)) == 1          sample 1: (h >> (64 - s)) == (1 << (s - 1)) - 1           s = s_bits
+ * — with its exact multiplicity: a FracMinHash signature of the read set at rate ~ 2 * 2^-s.  h is whatever the engine counts: the canonical, forward or reverse
+ * value, plain or under a mask, of a homopolymer-compressed sequence or not.  Two read sets counted with the same planes, strand, hpc and s_bits sample the same
+ * k-mers, so the intersection of their signatures estimates Jaccard similarity and containment (ntc_signature_compare), and the multiplicities are a
+ * collision-free cross-check of the estimator.  Everything else is unchanged: t_Counter, F1 and the outputs of a signature engine are bit-identical to those of
+ * the same engine without the flag.  A signature plane is a list of pairs (uint64 hash, uint32 count), strictly ascending by hash, counts saturating at
+ * 2^32 - 1; h == 0 cannot be sampled (both patterns hold a 1 bit) and marks an empty slot.
+ *   - Valid in ntc_create and ntc_create_seeded beside the strand flags, NTC_FLAG_HPC, NTC_FLAG_DIRECT_ATOMICS, _ALWAYS_LOG, _PARTITION_ALWAYS, _LANE_KERNEL
+ *     and _DEFER_REDO; beside NTC_FLAG_SIMPLE_KERNEL it is NTC_ERR_ARG; ntc_hll_create_ex refuses it.  Checked before a device is looked for.
+ *   - Every plane of a signature engine is the general kernel's (K1), exactly as for a strand engine without NTC_FLAG_STRAND_TILED: tiled, ragged and binned
+ *     batches are re-laid out on the device, NTC_FLAG_REQUIRE_TILED makes those submits fail with nothing counted, host batches take row slots,
+ *     ntc_submit_long_device gathers every sequence whole (ntc_long_stats stays (0, 0)); NTC_FLAG_STRAND_TILED is accepted and has no effect.
+ *   - K1 appends the sampled values to a per-plane log on the device; an insert pass moves the log into an open-addressing table per plane (12 B per slot,
+ *     at most half full: 24 .. 48 B per distinct value), which doubles as it fills.  The engine books a launch's WINDOWS in the log (a read set may sample
+ *     every window; plus one chunk of 1024 entries per wave), so a batch with more windows than the log holds is counted in several launches; every insert
+ *     pass waits for the stream once (it reads the log's fill and the tables' live counts back): once per 2^27 booked windows, not once per submit.  A table that cannot grow makes the submit or sync fail with NTC_ERR_MEMORY; nothing is dropped
+ *     silently.  Environment, read per engine: NTC_SIG_SLOTS (initial slots per plane, a power of two >= 64; default 2^16), NTC_SIG_LOG_ENTRIES (the value
+ *     log's capacity per plane in entries; default 2^27 = 1 GiB, allocated as far as the batches need it).
+ *   - ntc_reset empties the signatures, ntc_destroy frees them; ntc_merge_devices refuses a mix of engines with and without the flag and unions the
+ *     signatures of engines 1 .. into engine 0's (counts added); ntc_merge_counters moves no signature.
+ * (Bits 4, 256, 2048 and 1 << 20 stay refused as unknown flags.)  DESIGN.md §4 "Signatures". */
+#define NTC_FLAG_SIGNATURE 16384u
 #define NTC_FLAG_DIRECT_ATOMICS 2u /* no hit log: every sampled k-mer is one device atomic on the sketch
                                       (the literal form of ntcard.cpp:142-143; cross-check and A/B runs) */
 
@@ -294,6 +318,43 @@ int ntc_hpc_compress_device(int32_t device, void *stream, const void *d_in, cons
 int ntc_hpc_stats(ntc_engine *e, uint64_t *bytes_in, uint64_t *bytes_out);
 /* milliseconds of the compaction kernels of ntc_submit_long_device while profiling (ntc_set_profiling), outside ntc_kernel_time's spans, like ntc_long_time */
 int ntc_hpc_time(ntc_engine *e, double *ms);
+
+/* ---- signatures (NTC_FLAG_SIGNATURE); plane: index into the k list / seed list.  NTC_ERR_STATE on an engine without the flag, NTC_ERR_ARG for a bad plane ---- */
+/* brings pending work in (the value log is inserted; waits for the stream) and returns the number of distinct sampled values of the plane */
+int ntc_signature_size(ntc_engine *e, uint32_t plane, uint64_t *n);
+/* the plane's pairs, strictly ascending by hash: hashes[cap], counts[cap] (HOST; counts may be NULL), *n = the pairs written.  cap smaller than the
+ * plane's size: NTC_ERR_ARG and nothing is written, *n included (ask ntc_signature_size).  The pairs are gathered on the device and sorted on the host. */
+int ntc_signature(ntc_engine *e, uint32_t plane, uint64_t *hashes, uint32_t *counts, uint64_t cap, uint64_t *n);
+/* adds n pairs to the plane's signature: the merge-in for checkpoints and peers (and how tests drive the container on chosen keys).  counts == NULL: 1
+ * each; duplicates inside a call are legal and add up; zeros are skipped; counts saturate at 2^32 - 1.  ntc_signature_inject: HOST arrays (copied before
+ * the call returns).  ntc_signature_inject_device: DEVICE arrays, read stream-ordered on the engine's stream (they may be reused once the stream has
+ * passed the call; the call itself waits for the stream only when a table has to grow).  Neither touches t_Counter or F1. */
+int ntc_signature_inject(ntc_engine *e, uint32_t plane, const uint64_t *hashes, const uint32_t *counts, uint64_t n);
+int ntc_signature_inject_device(ntc_engine *e, uint32_t plane, const void *d_hashes_u64, const void *d_counts_u32, uint64_t n);
+/* |A n B| of two hash lists (a pure host function): both strictly ascending, else NTC_ERR_ARG.  Jaccard = c / (na + nb - c), containment of A in B = c / na. */
+int ntc_signature_compare(const uint64_t *a, uint64_t na, const uint64_t *b, uint64_t nb, uint64_t *n_common);
+/* diagnostics: the table slots of all planes together and the doublings of a table since create / reset (a table that grows 64 -> 65536 slots in one
+ * rehash counts 10); ntc_signature_time: milliseconds of the insert passes and of the rehashes while profiling (ntc_set_profiling), outside ntc_kernel_time */
+int ntc_signature_stats(ntc_engine *e, uint64_t *slots, uint64_t *grows);
+int ntc_signature_time(ntc_engine *e, double *insert_ms, double *grow_ms);
+/* A signature FILE (`ntcard --signature`, bin/ntsig): little-endian; the 8 bytes "NTCSIG1\0", uint32 k, gap, strand, hpc, s_bits, mask_len, uint64 n, the mask
+ * (mask_len bytes '0' / '1', all '1' for plain k; zero-padded to a multiple of 8), uint64 hashes[n], uint32 counts[n].  The header says how the file was
+ * counted: two files compare only when they agree in everything but n.  Pure host functions.
+ *   ntc_signature_write  h->mask: k characters; NTC_ERR_ARG for a bad header, hashes that are not strictly ascending or a file that cannot be written
+ *   ntc_signature_read   fills *h; hashes / counts (either may be NULL: skipped) have room for cap pairs — cap < n with a non-NULL array: NTC_ERR_ARG after
+ *                        *h is filled, so a first call with cap = 0 and NULL arrays learns n; NTC_ERR_ARG for a file that is not a signature or is cut short */
+#define NTC_SIG_MASK_MAX 608
+typedef struct {
+    uint32_t k, gap;            /* window length; -g of the run (0: none, or a mask given with --seed) */
+    uint32_t strand, hpc;       /* 0 canonical, 1 forward, 2 reverse; 1: homopolymer-compressed */
+    uint32_t s_bits, reserved;
+    uint64_t n;                 /* pairs */
+    char mask[NTC_SIG_MASK_MAX]; /* NUL-terminated */
+} ntc_sig_header;
+int ntc_signature_write(const char *path, const ntc_sig_header *h, const uint64_t *hashes, const uint32_t *counts);
+int ntc_signature_read(const char *path, ntc_sig_header *h, uint64_t *hashes, uint32_t *counts, uint64_t cap);
+/* the header of plane `plane` of a signature engine (k, gap, mask, strand, hpc, s_bits; n = 0): what ntc_signature_write needs beside the pairs */
+int ntc_signature_header(ntc_engine *e, uint32_t plane, ntc_sig_header *h);
 
 int ntc_sync(ntc_engine *e); /* wait for all submitted work */
 

@@ -21,7 +21,23 @@ ABI_SYMBOLS = [
     "ntc_create_seeded", "ntc_hash_dump_seed_device", "ntc_hash_dump_strand_device",
     "ntc_submit_long_device", "ntc_long_plan", "ntc_long_stats", "ntc_long_time",
     "ntc_hpc_compress", "ntc_hpc_compress_device", "ntc_hpc_stats", "ntc_hpc_time",
+    "ntc_signature_size", "ntc_signature", "ntc_signature_inject", "ntc_signature_inject_device", "ntc_signature_compare", "ntc_signature_stats",
+    "ntc_signature_time", "ntc_signature_header", "ntc_signature_write", "ntc_signature_read",
 ]
+
+
+class NtcSigHeader(C.Structure):
+    """ntc_sig_header"""
+    _fields_ = [
+        ("k", C.c_uint32),
+        ("gap", C.c_uint32),
+        ("strand", C.c_uint32),
+        ("hpc", C.c_uint32),
+        ("s_bits", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("n", C.c_uint64),
+        ("mask", C.c_char * 608),
+    ]
 
 
 class NtcHllConfig(C.Structure):
@@ -104,6 +120,16 @@ def lib():
     L.ntc_hpc_compress_device.argtypes = [i32, p, p, p, u64, p, p]
     L.ntc_hpc_stats.argtypes = [p, C.POINTER(u64), C.POINTER(u64)]
     L.ntc_hpc_time.argtypes = [p, C.POINTER(C.c_double)]
+    L.ntc_signature_size.argtypes = [p, u32, C.POINTER(u64)]
+    L.ntc_signature.argtypes = [p, u32, p, p, u64, C.POINTER(u64)]
+    L.ntc_signature_inject.argtypes = [p, u32, p, p, u64]
+    L.ntc_signature_inject_device.argtypes = [p, u32, p, p, u64]
+    L.ntc_signature_compare.argtypes = [p, u64, p, u64, C.POINTER(u64)]
+    L.ntc_signature_stats.argtypes = [p, C.POINTER(u64), C.POINTER(u64)]
+    L.ntc_signature_time.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.ntc_signature_header.argtypes = [p, u32, C.POINTER(NtcSigHeader)]
+    L.ntc_signature_write.argtypes = [C.c_char_p, C.POINTER(NtcSigHeader), p, p]
+    L.ntc_signature_read.argtypes = [C.c_char_p, C.POINTER(NtcSigHeader), p, p, u64]
     L.ntc_sync.argtypes = [p]
     L.ntc_finish.argtypes = [p, p, p, p]
     L.ntc_merge_counters.argtypes = [p, p, p]

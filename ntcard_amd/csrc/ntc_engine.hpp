@@ -252,6 +252,24 @@ struct ntc_engine {
 	uint64_t hpc_bytes_in = 0, hpc_bytes_out = 0;
 	std::vector<ntc_eng::Span> hpc_events;
 	double hpc_ms = 0.0;
+	// NTC_FLAG_SIGNATURE (ntc_signature.hip): per plane an open-addressing table of the sampled 64-bit values and their counts, fed from a u64 value log
+	// that K1's signature instantiations append to.  d_sigstate: per plane {log cursor, live keys, values in the log} (device uint64), then one scratch cursor for the compaction.
+	// sig_booked: the WINDOWS of the launches since the last insert pass plus one chunk per wave of them, per plane — a hard bound of the log's cursor (a
+	// read set may sample every window; a wave books the log in chunks of sig_chunk entries and leaves at most one of them partly unused).
+	// live_ub: the live keys at the last read-back plus everything injected since (the insert pass reads the exact figure before it decides on growth)
+	struct SigPlane {
+		DevBuf<unsigned long long> keys;
+		DevBuf<uint32_t> counts;
+		uint64_t slots = 0, live_ub = 0;
+	};
+	bool sig = false;
+	std::vector<SigPlane> sig_planes;
+	DevBuf<unsigned long long> d_siglog, d_sigstate, d_sigtmp_k; // [planes][sig_log_cap]; the state words; compaction / inject scratch (keys)
+	DevBuf<uint32_t> d_sigtmp_c;                                  // ... (counts)
+	uint64_t sig_log_cap = 0, sig_log_limit = 0, sig_booked = 0, sig_init_slots = 0, sig_grows = 0;
+	uint32_t sig_chunk = 64;
+	std::vector<ntc_eng::Span> sig_insert_events, sig_grow_events;
+	double sig_insert_ms = 0.0, sig_grow_ms = 0.0;
 	DevBuf<uint32_t> d_tmeta;       // K1's slot table (len | len << 16 per read) of a RAGGED tiled batch under a list of which a part is K1's
 	uint32_t hll_bits = 0;          // != 0: nthll engine (d_sketch holds uint32 M[1<<hll_bits])
 	DevBuf<uint32_t> d_hll_thr;
@@ -327,5 +345,15 @@ int run_batch(ntc_engine* e, const unsigned char* d_slots, const uint32_t* d_met
 // call, so their K1f may not wait (whatever NTC_FLAG_DEFER_REDO promised for the caller's own buffers)
 int run_tiled_segs(ntc_engine* e, const TiledSeg* segs_in, uint32_t n_in, uint64_t n_submits = 1, bool k1f_now = false);
 int defer_or_run_tiled(ntc_engine* e, const TiledSeg& sg);
+
+// ---- ntc_signature.hip: NTC_FLAG_SIGNATURE (the caller holds e->mu) ----
+int sig_setup(ntc_engine* e);                       // create: the knobs, the state words (the tables come with the reset)
+int sig_reset(ntc_engine* e);                       // empty tables of the initial size; the stream is idle
+uint64_t sig_max_slots(ntc_engine* e, uint64_t windows_per_slot); // the row slots one K1 launch may take (a multiple of 4; the log grows to at least four slots' need)
+uint64_t sig_need(const ntc_engine* e, uint64_t n_slots, uint64_t windows_per_slot); // log entries a launch over n_slots may book: its windows + a chunk per wave
+int sig_book(ntc_engine* e, uint64_t entries);      // room for a launch's sig_need in every plane's log: an insert pass first if it would not fit
+void sig_args(const ntc_engine* e, ntc::HfArgs& a, size_t first, size_t n); // the log of planes first .. first + n into a K1 launch
+int sig_flush(ntc_engine* e);                       // the pending log into the tables (waits for the stream)
+int sig_merge_from(ntc_engine* root, ntc_engine* other); // other's signatures added to root's (both flushed; the caller holds both locks)
 
 } // namespace ntc_eng

@@ -76,6 +76,14 @@ struct HfArgs {
 	uint32_t seed_nroll;        // spaced seed: toggle pairs of the rolling form (0: every wave takes the closed-form XOR-out)
 	uint32_t seed_extra;        // spaced seed: bytes of the blob behind its XOR-out tables (SeedPlan::extra_bytes)
 	uint32_t roll_t[kMaxRollPairs]; // spaced seed: toggle pair p = t_a | t_b << 16 (bytes q - k + t of step q)
+	// NTC_FLAG_SIGNATURE (ntc_signature.hip; the kSig instantiations only, behind everything the others read): per fused plane the u64 value log of the
+	// sampled k-mers and its cursor (entries booked so far, all launches since the last insert round).  A wave books sig_chunk entries at a time (one
+	// atomic), fills them round by round — a round may end one chunk and begin the next — and zeroes the rest of its last one.  sig_cap entries per log — the host books a launch's WINDOWS plus one chunk
+	// per wave, so the cursor cannot pass it; a write behind it is dropped and shows as cursor > sig_cap at the next read-back
+	unsigned long long* sig_log[kMaxFusedK];
+	unsigned long long* sig_cursor[kMaxFusedK]; // [0] the cursor, [2] the VALUES logged (without the zeroed rests: what the table must make room for)
+	uint64_t sig_cap;           // != 0 selects the signature instantiations (row slots; plain k lists and spaced seeds, canonical or one strand)
+	uint32_t sig_chunk;         // >= 64 (a resolve round holds up to 64 values)
 };
 
 // TILED slot layout (ntc_submit_tiled_device): tile t = reads [2048 t, 2048 t + 2048); the 16 raw bytes of bases [16 c, 16 c + 16) of read r
@@ -238,6 +246,20 @@ hipError_t launch_log_set_fill(uint32_t* fill, uint32_t n_regions, uint32_t regi
 hipError_t launch_split(const SplitArgs& a, unsigned grid, hipStream_t st);
 hipError_t launch_count(const CountArgs& a, unsigned grid, hipStream_t st);
 hipError_t set_apply_smem_limit();
+
+// ---- signatures (ntc_signature.hip; NTC_FLAG_SIGNATURE) ----
+// One plane's container: an open-addressing table, keys[slots] (0 = empty) + counts[slots], slots a power of two, linear probing from a multiplicative
+// home slot; *live = the keys it holds.  The HOST keeps it at most half full (ntc_signature.hip: sig_room), so a probe always ends.
+struct SigTable {
+	unsigned long long* keys;
+	uint32_t* counts;
+	uint64_t slots;
+	unsigned long long* live;
+};
+// adds n pairs (in_keys[i], in_counts ? in_counts[i] : 1), zeros skipped, duplicates summed, counts saturating at 2^32 - 1 (in_counts == nullptr: n < 2^31)
+hipError_t launch_sig_insert(const SigTable& t, const unsigned long long* in_keys, const uint32_t* in_counts, uint64_t n, hipStream_t st);
+// the live pairs of a table, in slot order of arrival, to out_keys / out_counts (room for *live entries); *cursor (zeroed by the caller) counts them
+hipError_t launch_sig_compact(const SigTable& t, unsigned long long* out_keys, uint32_t* out_counts, unsigned long long* cursor, hipStream_t st);
 
 hipError_t launch_hash(int mode, const HashArgs& a, unsigned grid, size_t smem, hipStream_t st);
 hipError_t set_hash_smem_limit(size_t smem);

@@ -139,6 +139,10 @@ int drain_events(ntc_engine* e)
 	if (int rc = elapsed(e->long_cut_events, e->long_cut_ms, nullptr)) return rc;
 	if (int rc = elapsed(e->long_gather_events, e->long_gather_ms, nullptr)) return rc;
 	if (int rc = elapsed(e->hpc_events, e->hpc_ms, nullptr)) return rc;
+	if (int rc = elapsed(e->sig_insert_events, e->sig_insert_ms, nullptr)) return rc;
+	if (int rc = elapsed(e->sig_grow_events, e->sig_grow_ms, nullptr)) return rc;
+	e->sig_insert_events.clear();
+	e->sig_grow_events.clear();
 	e->pending.clear();
 	e->apply_pending.clear();
 	e->k1f_events.clear();
@@ -402,6 +406,7 @@ int launch_k1_group(ntc_engine* e, const SlotBatch& b, size_t first, size_t n)
 	}
 	a.sketch0 = e->d_sketch;
 	a.sk_dirty = e->d_skdirty;
+	if (e->sig) sig_args(e, a, first, n);
 	HIP_TRY(ntc::launch_sketch_hf(a, hp.grid, hp.wpb, hp.smem, e->stream));
 	return 0;
 }
@@ -409,6 +414,17 @@ int launch_k1_group(ntc_engine* e, const SlotBatch& b, size_t first, size_t n)
 int run_k1(ntc_engine* e, const SlotBatch& b, const std::vector<uint8_t>* skip)
 {
 	auto mine = [&](size_t ki) { return !(skip && (*skip)[ki]); };
+	if (e->sig) {
+		// NTC_FLAG_SIGNATURE: a plane's value log must hold every WINDOW of a launch (ntc_signature.hip) — a batch with more is counted in several launches
+		const uint32_t len = b.meta ? b.stride : b.read_len, kmin = *std::min_element(e->klist.begin(), e->klist.end());
+		const uint64_t per = len >= kmin ? (uint64_t)(len - kmin + 1u) : 1u, max_slots = sig_max_slots(e, per);
+		if (b.n > max_slots) {
+			for (uint64_t done = 0; done < b.n; done += max_slots)
+				if (int rc = run_batch(e, b.slots + done * b.stride, b.meta ? b.meta + done : nullptr, std::min<uint64_t>(max_slots, b.n - done), b.read_len, b.stride, b.tiled, skip))
+					return rc;
+			return 0;
+		}
+	}
 	double per_slot = 0.0;
 	for (size_t ki = 0; ki < e->klist.size(); ++ki)
 		if (mine(ki)) per_slot += sampled_per_read(b.meta ? b.stride : b.read_len, e->klist[ki], e->s_bits);
@@ -420,6 +436,10 @@ int run_k1(ntc_engine* e, const SlotBatch& b, const std::vector<uint8_t>* skip)
 			if (int rc = run_batch(e, b.slots, nullptr, head, b.read_len, b.stride, b.tiled, skip)) return rc;
 			return run_batch(e, b.slots + head * b.stride, nullptr, b.n - head, b.read_len, b.stride, b.tiled, skip);
 		}
+	}
+	if (e->sig) { // (behind the probe's cut: every launch books itself)
+		const uint32_t len = b.meta ? b.stride : b.read_len, kmin = *std::min_element(e->klist.begin(), e->klist.end());
+		if (int rc = sig_book(e, sig_need(e, b.n, len >= kmin ? (uint64_t)(len - kmin + 1u) : 1u))) return rc;
 	}
 	// this batch's sampled k-mers + what every wave may leave unused at the end of a region
 	if (e->d_log)
@@ -523,7 +543,7 @@ bool route_tiled(ntc_engine* e, const Segs& segs, bool any_tails, int& rc)
 	rc = 0;
 	if (!e->ts_all && e->ts_required)
 		rc = fail(NTC_ERR_ARG, "ntc_submit_tiled_device: the tiled kernel is not available for this configuration (NTC_FLAG_REQUIRE_TILED)");
-	else if (!e->ts_ok && any_tails && !e->seeded && e->strand == 0)
+	else if (!e->ts_ok && any_tails && !e->seeded && e->strand == 0 && !e->sig) // (a strand or signature engine is K1's by contract: its ragged batches are re-laid out)
 		rc = fail(NTC_ERR_ARG, "ntc_submit_tiled_ragged_device: the tiled kernels are not built for any k of this configuration");
 	else if (!e->ts_ok) { // this configuration is K1's
 		for (size_t i = 0; i < segs.size() && !rc; ++i) {

@@ -45,13 +45,15 @@ namespace {
 int check_config(const ntc_config* cfg)
 {
 	constexpr uint32_t kKnownFlags = NTC_FLAG_SIMPLE_KERNEL | NTC_FLAG_DIRECT_ATOMICS | NTC_FLAG_ALWAYS_LOG | NTC_FLAG_PARTITION_ALWAYS | NTC_FLAG_LANE_KERNEL |
-	                                 NTC_FLAG_REQUIRE_TILED | NTC_FLAG_DEFER_REDO | NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE | NTC_FLAG_STRAND_TILED | NTC_FLAG_HPC;
+	                                 NTC_FLAG_REQUIRE_TILED | NTC_FLAG_DEFER_REDO | NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE | NTC_FLAG_STRAND_TILED | NTC_FLAG_HPC | NTC_FLAG_SIGNATURE;
 	if (cfg->flags & ~kKnownFlags) // (ABI 4's NTC_FLAG_BITSLICE_KERNEL = 4 and NTC_FLAG_TILED_TEAMS = 256 selected kernels that no longer exist)
 		return fail(NTC_ERR_ARG, "ntc_create: unknown flag bits 0x%x", cfg->flags & ~kKnownFlags);
 	if ((cfg->flags & NTC_FLAG_STRAND_FORWARD) && (cfg->flags & NTC_FLAG_STRAND_REVERSE))
 		return fail(NTC_ERR_ARG, "ntc_create: NTC_FLAG_STRAND_FORWARD and NTC_FLAG_STRAND_REVERSE exclude each other");
 	if ((cfg->flags & NTC_FLAG_STRAND_TILED) && !(cfg->flags & (NTC_FLAG_STRAND_FORWARD | NTC_FLAG_STRAND_REVERSE)))
 		return fail(NTC_ERR_ARG, "ntc_create: NTC_FLAG_STRAND_TILED needs NTC_FLAG_STRAND_FORWARD or NTC_FLAG_STRAND_REVERSE (it picks the kernels of a one-strand engine)");
+	if ((cfg->flags & NTC_FLAG_SIGNATURE) && (cfg->flags & NTC_FLAG_SIMPLE_KERNEL))
+		return fail(NTC_ERR_ARG, "ntc_create: NTC_FLAG_SIGNATURE needs the production kernel (the simple validation kernel keeps no sampled values)");
 	for (uint32_t i = 0; i < cfg->n_k; ++i)
 		if (cfg->k[i] < 1 || cfg->k[i] > kMaxK)
 			return fail(NTC_ERR_ARG, "ntc_create: k=%u outside 1..%u", cfg->k[i], kMaxK);
@@ -129,6 +131,7 @@ int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, 
 	e->seeded = seeded;
 	e->strand = (cfg->flags & NTC_FLAG_STRAND_FORWARD) ? 1u : (cfg->flags & NTC_FLAG_STRAND_REVERSE) ? 2u : 0u;
 	e->hpc = (cfg->flags & NTC_FLAG_HPC) != 0;
+	e->sig = (cfg->flags & NTC_FLAG_SIGNATURE) != 0;
 	e->masks.assign(nk, std::string());
 	e->kgap.assign(nk, 0u);
 	e->seeds.assign(nk, ntc::SeedPlan());
@@ -194,8 +197,9 @@ int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, 
 	// One strand: the canonical K1h walks both strands bit-sliced — without NTC_FLAG_STRAND_TILED no k of a strand engine is the pair's (tiled batches:
 	// re-laid out, then K1).  With the flag the one-strand K1h kernels + K1f take the engine when EVERY plane is one of theirs; a list of which only a part
 	// qualifies stays K1's as a whole (K1 has no one-strand instantiation that stages tiles).
+	// NTC_FLAG_SIGNATURE: the 64-bit value is on hand in K1's resolve stage only — every plane of a signature engine is K1's, NTC_FLAG_STRAND_TILED or not.
 	const bool strand_ok = e->strand == 0 || (cfg->flags & NTC_FLAG_STRAND_TILED);
-	const bool ts_pre = e->kernel_kind == KIND_HF && !(cfg->flags & NTC_FLAG_LANE_KERNEL) && e->hll_bits == 0 && strand_ok &&
+	const bool ts_pre = e->kernel_kind == KIND_HF && !(cfg->flags & NTC_FLAG_LANE_KERNEL) && e->hll_bits == 0 && strand_ok && !e->sig &&
 	                    nk * e->plane_elems() <= (1ull << 32);
 	e->k_tiled.assign(nk, 0);
 	e->ts_ok = false;
@@ -223,6 +227,8 @@ int create_engine(const ntc_config* cfg, const std::vector<std::string>& masks, 
 		if (!e->d_t4s[ki].upload(t4) || !e->d_k1h_tabs[ki].upload(tab))
 			return fail(NTC_ERR_MEMORY, "ntc_create: cannot allocate the closed-form tables of the tiled kernels on device");
 	}
+	if (e->sig)
+		if (int rc = sig_setup(e.get())) return rc;
 	e->ts_required = (cfg->flags & NTC_FLAG_REQUIRE_TILED) != 0;
 	e->defer_redo = (cfg->flags & NTC_FLAG_DEFER_REDO) != 0;
 	e->hfk.resize(nk);
@@ -388,6 +394,8 @@ int ntc_reset(ntc_engine* e)
 	HIP_TRY(hipMemsetAsync(e->d_f1, 0, e->klist.size() * 8, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	if (int rc = drain_events(e)) return rc;
+	if (e->sig)
+		if (int rc = sig_reset(e)) return rc;
 	e->ms_total = 0.0;
 	e->launches = 0;
 	e->apply_ms = 0.0;
@@ -406,6 +414,7 @@ int ntc_sync(ntc_engine* e)
 	std::lock_guard<std::mutex> lk(e->mu);
 	HIP_TRY(hipSetDevice(e->device));
 	if (int rc = join_k1f(e)) return rc;   // (K1f reads the batches too)
+	if (int rc = sig_flush(e)) return rc;  // (NTC_FLAG_SIGNATURE: the value log into the tables; a table that cannot grow fails here)
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	return drain_events(e);
 }
@@ -427,6 +436,7 @@ int ntc_finish(ntc_engine* e, uint16_t* t_counter_out, uint32_t* p_hist_out, uin
 	const size_t nk = e->klist.size();
 	const uint64_t per_sample = 1ull << e->r_bits;
 	if (int rc = apply_log(e)) return rc; // pending increments first: compEst reads the counters (ntcard.cpp:240-247)
+	if (int rc = sig_flush(e)) return rc;
 	if (t_counter_out && !e->d_out16.reserve(2 * per_sample * sizeof(uint16_t))) return fail(NTC_ERR_MEMORY, "ntc_finish: cannot allocate uint16 staging");
 	if (p_hist_out || t_counter_out) {
 		HIP_TRY(hipMemsetAsync(e->d_phist, 0, nk * 2 * 65536 * 4, e->stream));

@@ -110,7 +110,7 @@ int ntc_merge_devices(ntc_engine* const* engines, int32_t n_engines)
 	if (!root) return fail(NTC_ERR_ARG, "ntc_merge_devices: null engine");
 	for (int32_t i = 0; i < n_engines; ++i) {
 		ntc_engine* e = engines[i];
-		if (!e || e->klist != root->klist || e->masks != root->masks || e->strand != root->strand || e->hpc != root->hpc || e->r_bits != root->r_bits || e->s_bits != root->s_bits || e->hll_bits != root->hll_bits)
+		if (!e || e->klist != root->klist || e->masks != root->masks || e->strand != root->strand || e->hpc != root->hpc || e->sig != root->sig || e->r_bits != root->r_bits || e->s_bits != root->s_bits || e->hll_bits != root->hll_bits)
 			return fail(NTC_ERR_ARG, "ntc_merge_devices: engine %d is not configured like engine 0", i);
 		for (int32_t j = 0; j < i; ++j)
 			if (engines[j] == e) return fail(NTC_ERR_ARG, "ntc_merge_devices: engine %d listed twice", i);
@@ -126,6 +126,7 @@ int ntc_merge_devices(ntc_engine* const* engines, int32_t n_engines)
 	for (int32_t i = 0; i < n_engines; ++i) {
 		HIP_TRY(hipSetDevice(engines[i]->device));
 		if (int rc = apply_log(engines[i])) return rc;
+		if (int rc = sig_flush(engines[i])) return rc;
 		HIP_TRY(hipStreamSynchronize(engines[i]->stream));
 	}
 	if (n_engines == 1) return 0;
@@ -225,6 +226,10 @@ int ntc_merge_devices(ntc_engine* const* engines, int32_t n_engines)
 		release_peers(peers);
 		if (rc) return rc;
 	}
+	// NTC_FLAG_SIGNATURE: the compacted pairs of engines 1 .. travel to engine 0's device and are injected there (counts add up)
+	if (root->sig)
+		for (int32_t i = 1; i < n_engines; ++i)
+			if (int rc = sig_merge_from(root, engines[i])) return rc;
 	// 4. everything now lives in engine 0 (counters as their value mod 2^16, which is all t_Counter ever held): the others start
 	//    from zero again, the sum stays what it was
 	locks.clear(); // (ntc_reset takes the engine's lock itself)

@@ -143,7 +143,9 @@ namespace ntc {
 constexpr bool mode_spaced(int mode) { return (mode & 1) != 0; }
 constexpr bool mode_hll(int mode) { return mode >= 2; }
 
-template <bool kMulti, int kMode, int kPref, bool kDump = false, bool kTiled = false, bool kOne = false>
+// kSig: NTC_FLAG_SIGNATURE — the resolve stage also appends the 64-bit value of every sampled k-mer to the plane's value log (HfArgs::sig_log), in chunks
+// a wave books with one cursor atomic each; instantiations of their own, so that the others carry neither the registers nor a branch for it
+template <bool kMulti, int kMode, int kPref, bool kDump = false, bool kTiled = false, bool kOne = false, bool kSig = false>
 __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(const HfArgs a)
 {
 #ifdef NTC_HF_CLOCKS
@@ -220,6 +222,17 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 	const unsigned char* tabHb = reinterpret_cast<const unsigned char*>(tabH[0]);
 	uint32_t* sketch_k = a.ks[0].sketch;
 	uint32_t key_base = a.ks[0].key_base;
+	unsigned long long* sig_log_k = kSig ? a.sig_log[0] : nullptr;
+	unsigned long long* sig_cur_k = kSig ? a.sig_cursor[0] : nullptr;
+	uint64_t sig_at[kMaxFusedK] = {0, 0, 0, 0}; // kSig: per fused plane, the wave's place in its current chunk and the entries left of it (wave-uniform)
+	uint32_t sig_room[kMaxFusedK] = {0, 0, 0, 0};
+	uint32_t sig_vals[kMaxFusedK] = {0, 0, 0, 0}; // values this wave has logged (a launch's windows per wave stay far below 2^32)
+	uint64_t sig_at_k = 0;
+	uint32_t sig_room_k = 0;
+	auto sig_zero = [&](unsigned long long* log, uint64_t at, uint32_t room) { // the unused rest of a chunk
+		for (uint32_t i = (uint32_t)lane; i < room; i += 64u)
+			if (at + i < a.sig_cap) log[at + i] = 0ull;
+	};
 
 	// sample windows on the top bits (ntcard.cpp:135-138); VGPR-resident on purpose (SGPR sources halve the VALU rate)
 	uint32_t lo0 = 1u << (31 - a.s_bits);
@@ -380,6 +393,12 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 		tabHb = reinterpret_cast<const unsigned char*>(tabH[ki]);
 		sketch_k = a.ks[ki].sketch;
 		key_base = a.ks[ki].key_base;
+		if constexpr (kSig) {
+			sig_log_k = a.sig_log[ki];
+			sig_cur_k = a.sig_cursor[ki];
+			sig_at_k = sig_at[ki];
+			sig_room_k = sig_room[ki];
+		}
 		shb = (0u - k) & 3u;
 		uint64_t f1_wave = 0;
 		int32_t endq = (int32_t)(len < wlim + k - 1 ? len : wlim + k - 1); // steps q in [0,endq)
@@ -487,6 +506,7 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 			}
 			bool hit = false;
 			uint32_t key = 0, rel = 0; // rel: counter index inside this k's plane pair; key: index in the engine's whole sketch (hit-log keys)
+			uint32_t sig_hi = 0, sig_lo = 0; // kSig: the value itself
 			if (act && (dirty & 0x01010101u) == 0u) { // a window with a non-ACGTU byte yields no k-mer (ntHashIterator.hpp:59-86)
 				const bool rev = !kOne && ((rhi < fhi) | ((rhi == fhi) & (rlo < flo))); // nthash.hpp:275-279 (one strand: no choice to make)
 				const uint32_t hi = rev ? rhi : fhi;
@@ -513,6 +533,40 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 					hit = c0 | c1;
 					rel = (lo & rmask) + (c1 ? rbuck : 0u);
 					key = key_base + rel;
+					if constexpr (kSig) {
+						sig_hi = hi;
+						sig_lo = lo;
+					}
+				}
+			}
+			if constexpr (kSig) {
+				// the sampled values of this round, behind one another in the wave's current CHUNK of the plane's value log.  A chunk is booked with one
+				// cursor atomic (one per resolve round on the one address cost K1 about 3 ms per 18 M values, profiles/signature.txt).  A round that does
+				// not fit the rest of the chunk fills it and goes on in the next one, so a wave leaves nothing unused but the rest of its LAST chunk,
+				// which it zeroes on its way out — no sampled value is 0, the insert pass skips zeros
+				const uint64_t m = ballot(hit);
+				if (m != 0) {
+					const uint32_t c = (uint32_t)__popcll(m);
+					const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+					const unsigned long long v = ((unsigned long long)sig_hi << 32) | sig_lo;
+					uint32_t skip = 0; // values of this round that went into the chunk just filled
+					if (c > sig_room_k) {
+						skip = sig_room_k;
+						if (hit && pos < skip && sig_at_k + pos < a.sig_cap) sig_log_k[sig_at_k + pos] = v;
+						uint32_t b_lo = 0, b_hi = 0;
+						if (lane == 0) {
+							const unsigned long long b = atomicAdd(sig_cur_k, (unsigned long long)a.sig_chunk);
+							b_lo = (uint32_t)b;
+							b_hi = (uint32_t)(b >> 32);
+						}
+						sig_at_k = ((uint64_t)__builtin_amdgcn_readfirstlane(b_hi) << 32) | __builtin_amdgcn_readfirstlane(b_lo);
+						sig_room_k = a.sig_chunk; // (>= 64: what is left of a round always fits a fresh chunk)
+					}
+					const uint64_t at = sig_at_k + (pos - skip);
+					if (hit && pos >= skip && at < a.sig_cap) sig_log_k[at] = v;
+					sig_at_k += c - skip;
+					sig_room_k -= c - skip;
+					sig_vals[ki] += c;
 				}
 			}
 			if constexpr (!mode_hll(kMode) && !kDump) {
@@ -898,11 +952,20 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 		// ---- leftovers of the compaction queue: one last, partially filled resolve round ----
 		if (npend != 0) resolve_round(pend, npend);
 		f1_acc[ki] += f1_wave;
+		if constexpr (kSig) {
+			sig_at[ki] = sig_at_k;
+			sig_room[ki] = sig_room_k;
+		}
 		} // k list
 	}
 	for (uint32_t j = 0; j < n_k; ++j)
 		if (lane == 0 && f1_acc[j]) atomicAdd(a.ks[j].f1, (unsigned long long)f1_acc[j]);
 	if (use_log && lane == 0 && lreg < a.log_regions) a.log_fill[lreg] = lfill;
+	if constexpr (kSig)
+		for (uint32_t j = 0; j < n_k; ++j) {
+			sig_zero(a.sig_log[j], sig_at[j], sig_room[j]);
+			if (lane == 0 && sig_vals[j] != 0u) atomicAdd(a.sig_cursor[j] + 2, (unsigned long long)sig_vals[j]);
+		}
 #ifdef NTC_HF_CLOCKS
 	if (lane == 0 && gwave < 8192u) {
 		g_hf_clocks[2 * gwave] = hc_t0;
@@ -918,6 +981,23 @@ hipError_t launch_sketch_hf(const HfArgs& a, unsigned grid, unsigned waves_per_b
 	if (a.tiled != 0u && (a.dump != nullptr || a.gap != 0 || a.hll_bits != 0)) return hipErrorInvalidValue; // (tiled staging: plain k-mer mode only)
 	if (a.ks[0].strand > 2u || (a.ks[0].strand != 0u && a.tiled != 0u)) return hipErrorInvalidValue; // (one strand: row slots)
 	if (a.hll_bits != 0 && (a.n_k != 1 || a.dump != nullptr || a.hll_thr == nullptr)) return hipErrorInvalidValue; // (nthll: one plane per launch)
+	if (a.sig_cap != 0) { // NTC_FLAG_SIGNATURE: row slots only (tiled batches are re-laid out first); slots beyond the 10-chunk prefetch stage with blocking loads
+		if (a.tiled != 0u || a.dump != nullptr || a.hll_bits != 0 || a.sig_chunk < 64u) return hipErrorInvalidValue;
+		const bool one = a.ks[0].strand != 0u;
+		if (a.gap != 0 && one)
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, false, false, true, true>), g, b, smem, st, a);
+		else if (a.gap != 0)
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, false, false, false, true>), g, b, smem, st, a);
+		else if (a.n_k > 1 && one)
+			hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 10, false, false, true, true>), g, b, smem, st, a);
+		else if (a.n_k > 1)
+			hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 10, false, false, false, true>), g, b, smem, st, a);
+		else if (one)
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, false, false, true, true>), g, b, smem, st, a);
+		else
+			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, false, false, false, true>), g, b, smem, st, a);
+		return hipGetLastError();
+	}
 	if (a.ks[0].strand != 0u) { // the one-strand copies of the instantiations a strand engine can reach (its tiled batches are re-laid out as row slots)
 		if (a.hll_bits != 0 && a.gap != 0)
 			hipLaunchKernelGGL((sketch_hf_kernel<false, 3, 10, false, false, true>), g, b, smem, st, a);
@@ -1008,7 +1088,11 @@ hipError_t set_sketch_hf_smem_limit(size_t smem)
 		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, true, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, true, false, true>),
 		              // nthll under a spaced seed, nthll of one strand
 		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 3, 10>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 2, 10, false, false, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 3, 10, false, false, true>) };
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 3, 10, false, false, true>),
+		              // signatures
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, false, false, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 10, false, false, false, true>),
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, false, false, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, false, false, true, true>),
+		              reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 10, false, false, true, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, false, false, true, true>) };
 	for (const void* f : fns) {
 		const hipError_t rc = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 		if (rc != hipSuccess) return rc;

@@ -53,6 +53,8 @@ void usage(std::ostream& os)
 	   << "\t\tno effect (and a warning) without --strand=forward|reverse\n"
 	   << "      --hpc\tcount homopolymer-compressed k-mers: every run of one base (A, C, G, T = U, either case) is collapsed to its first letter before the\n"
 	   << "\t\tk-mers are taken (N and other letters are kept and break runs); with -k, -g, --seed and --strand; output files unchanged\n"
+	   << "      --signature\tbeside every <STRING>_k<k>.hist (-p) also write <STRING>_k<k>.sig: every sampled k-mer hash with its exact count, for\n"
+	   << "\t\tbin/ntsig (info, compare: Jaccard and containment of two runs with the same k, seed, strand, --hpc and sampling rate)\n"
 	   << "      --help\tdisplay this help and exit\n"
 	   << "      --version\toutput version information and exit\n";
 }
@@ -70,6 +72,7 @@ struct Options {
 	uint32_t strand_flag = 0;       // --strand: NTC_FLAG_STRAND_FORWARD / _REVERSE, 0 = canonical
 	bool strand_tiled = true;       // --strand-kernel: NTC_FLAG_STRAND_TILED beside a strand flag
 	bool hpc = false;               // --hpc: NTC_FLAG_HPC
+	bool signature = false;         // --signature: NTC_FLAG_SIGNATURE, a .sig beside every .hist
 };
 
 void process_file(const std::string& path, ntc_engine* eng)
@@ -99,7 +102,7 @@ int main(int argc, char** argv)
 {
 	const auto t_start = std::chrono::steady_clock::now();
 	static const char shortopts[] = "t:s:r:k:c:l:p:f:o:g:";
-	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED, OPT_STRAND, OPT_STRAND_KERNEL, OPT_HPC };
+	enum { OPT_HELP = 1, OPT_VERSION, OPT_SEED, OPT_STRAND, OPT_STRAND_KERNEL, OPT_HPC, OPT_SIGNATURE };
 	bool strand_kernel_given = false;
 	static const struct option longopts[] = { { "threads", required_argument, nullptr, 't' },
 		                                      { "kmer", required_argument, nullptr, 'k' },
@@ -115,6 +118,7 @@ int main(int argc, char** argv)
 		                                      { "strand", required_argument, nullptr, OPT_STRAND },
 		                                      { "strand-kernel", required_argument, nullptr, OPT_STRAND_KERNEL },
 		                                      { "hpc", no_argument, nullptr, OPT_HPC },
+		                                      { "signature", no_argument, nullptr, OPT_SIGNATURE },
 		                                      { nullptr, 0, nullptr, 0 } };
 	Options opt;
 	bool die = false;
@@ -171,6 +175,7 @@ int main(int argc, char** argv)
 			break;
 		}
 		case OPT_HPC: opt.hpc = true; break;
+		case OPT_SIGNATURE: opt.signature = true; break;
 		case 'k': {
 			std::istringstream arg(optarg ? optarg : "");
 			std::string token;
@@ -228,6 +233,10 @@ int main(int argc, char** argv)
 		std::cerr << PROGRAM << ": missing argument -p/-o ... \n";
 		die = true;
 	}
+	if (opt.signature && (opt.prefix.empty() || !opt.output.empty())) {
+		std::cerr << PROGRAM << ": --signature writes <prefix>_k<k>.sig beside the .hist files: it needs -p and no -o\n";
+		die = true;
+	}
 	if (opt.gap != 0 && opt.klist.size() != 1) {
 		std::cerr << PROGRAM << ": -g does not support multiple k currently.\n";
 		die = true;
@@ -283,7 +292,7 @@ int main(int argc, char** argv)
 	cfg.r_bits = opt.r_bits;
 	cfg.s_bits = opt.s_bits;
 	if (strand_kernel_given && !opt.strand_flag) std::cerr << PROGRAM << ": warning: --strand-kernel has no effect on a canonical run (no --strand=forward|reverse)\n";
-	cfg.flags = opt.strand_flag | (opt.strand_flag && opt.strand_tiled ? NTC_FLAG_STRAND_TILED : 0u) | (opt.hpc ? NTC_FLAG_HPC : 0u);
+	cfg.flags = opt.strand_flag | (opt.strand_flag && opt.strand_tiled ? NTC_FLAG_STRAND_TILED : 0u) | (opt.hpc ? NTC_FLAG_HPC : 0u) | (opt.signature ? NTC_FLAG_SIGNATURE : 0u);
 	// Devices: NTCARD_DEVICES="0,1,2,..." spreads the input files over several GPUs (one private sketch each, merged
 	// at the end: counting is a commutative sum); NTCARD_DEVICE=<n> or nothing selects a single one.
 	std::vector<int> devices;
@@ -340,6 +349,20 @@ int main(int argc, char** argv)
 			if (ntc_write_hist(name.str().c_str(), f1[ki], F0, f.data(), opt.cov_max) != 0) {
 				std::cerr << PROGRAM << ": cannot write " << name.str() << "\n";
 				return EXIT_FAILURE;
+			}
+			if (opt.signature) { // the same label as the .hist beside it
+				std::string sig = name.str();
+				sig.replace(sig.size() - 5, 5, ".sig");
+				ntc_sig_header h;
+				uint64_t n = 0;
+				if (ntc_signature_header(eng, (uint32_t)ki, &h) != 0 || ntc_signature_size(eng, (uint32_t)ki, &n) != 0) die_engine();
+				std::vector<uint64_t> hashes(n);
+				std::vector<uint32_t> counts(n);
+				if (ntc_signature(eng, (uint32_t)ki, hashes.data(), counts.data(), n, &h.n) != 0) die_engine();
+				if (ntc_signature_write(sig.c_str(), &h, hashes.data(), counts.data()) != 0) {
+					std::cerr << PROGRAM << ": cannot write " << sig << "\n";
+					return EXIT_FAILURE;
+				}
 			}
 		}
 	} else { // outCompact, ntcard.cpp:300-315

@@ -24,6 +24,7 @@ FLAG_STRAND_FORWARD = 512  # NTC_FLAG_STRAND_FORWARD: count the forward value fh
 FLAG_STRAND_REVERSE = 1024  # NTC_FLAG_STRAND_REVERSE: count the reverse value rh (the forward value of the window's reverse complement)
 FLAG_STRAND_TILED = 4096  # NTC_FLAG_STRAND_TILED: a one-strand engine whose planes are all the tiled kernels' counts on the one-strand K1h + K1f instead of K1
 FLAG_HPC = 8192  # NTC_FLAG_HPC: homopolymer-compressed counting — every run of one base is collapsed to its first byte before the windows are taken
+FLAG_SIGNATURE = 16384  # NTC_FLAG_SIGNATURE: keep every sampled 64-bit value with its exact count, per plane (Engine.signature)
 _STRAND_FLAGS = {"canonical": 0, "forward": FLAG_STRAND_FORWARD, "reverse": FLAG_STRAND_REVERSE}
 SIZE_RULE_BYTES = 50_000_000_000  # ntcard.cpp:430: total input < 50 GB => sBits = 7
 
@@ -57,13 +58,14 @@ def _strand_flags(flags, strand, strand_tiled=False):
 
 class Engine:
     def __init__(self, klist, gap=0, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0, strand=None,
-                 strand_tiled=False, hpc=False):
+                 strand_tiled=False, hpc=False, signature=False):
         """strand: "canonical" (the default, what ntcard counts), "forward" or "reverse" — which value of a window is counted
         (include/ntcard_hip.h: NTC_FLAG_STRAND_FORWARD / _REVERSE).  strand_tiled: a one-strand engine whose planes are all the tiled kernels' (plain
         k = 12 .. 32, the two tiled gap seeds, sBits >= 7) counts on the one-strand K1h + K1f instead of the general kernel (NTC_FLAG_STRAND_TILED;
         the results are the same).  hpc: count homopolymer-compressed sequences (NTC_FLAG_HPC: submit / submit_spans compress on the host,
-        submit_long_device on the device; the fixed-layout device batches are refused)"""
-        flags = _strand_flags(flags, strand, strand_tiled) | (FLAG_HPC if hpc else 0)
+        submit_long_device on the device; the fixed-layout device batches are refused).  signature: keep every sampled 64-bit value with its exact count
+        (NTC_FLAG_SIGNATURE: signature(), signature_inject(), signature_stats(); every plane is then the general kernel's)"""
+        flags = _strand_flags(flags, strand, strand_tiled) | (FLAG_HPC if hpc else 0) | (FLAG_SIGNATURE if signature else 0)
         self._lib = _abi.lib()
         self.klist = [int(k) for k in klist]
         self.gap, self.r_bits, self.s_bits, self.device = int(gap), int(r_bits), int(s_bits), int(device)
@@ -85,10 +87,10 @@ class Engine:
 
     @classmethod
     def from_seeds(cls, seeds, r_bits=27, s_bits=7, device=0, stream=None, ext_sketch=None, ext_f1=None, flags=0, log_entries=0, strand=None,
-                   strand_tiled=False, hpc=False):
+                   strand_tiled=False, hpc=False, signature=False):
         """an engine whose planes are spaced seeds given as masks of '0' / '1' (include/ntcard_hip.h: ntc_create_seeded); its klist is
-        the masks' lengths, so finish, merge_counters and the rest work as for a k list; strand, strand_tiled and hpc as for Engine()"""
-        flags = _strand_flags(flags, strand, strand_tiled) | (FLAG_HPC if hpc else 0)
+        the masks' lengths, so finish, merge_counters and the rest work as for a k list; strand, strand_tiled, hpc and signature as for Engine()"""
+        flags = _strand_flags(flags, strand, strand_tiled) | (FLAG_HPC if hpc else 0) | (FLAG_SIGNATURE if signature else 0)
         self = cls.__new__(cls)
         self._lib = _abi.lib()
         self.seeds = [s.decode() if isinstance(s, bytes) else str(s) for s in seeds]
@@ -208,6 +210,52 @@ class Engine:
         ms = C.c_double()
         check(self._lib.ntc_hpc_time(self._h, C.byref(ms)))
         return ms.value
+
+    # -- signatures (NTC_FLAG_SIGNATURE) -------------------------------------------------------
+    def signature_size(self, plane=0):
+        """the distinct sampled values of a plane; brings pending work in (ntc_signature_size)"""
+        n = C.c_uint64()
+        check(self._lib.ntc_signature_size(self._h, int(plane), C.byref(n)))
+        return n.value
+
+    def signature(self, plane=0):
+        """-> (hashes uint64[n] strictly ascending, counts uint32[n]): every sampled value of the plane with its exact count (ntc_signature)"""
+        cap = self.signature_size(plane)
+        h = np.zeros(max(cap, 1), dtype=np.uint64)
+        c = np.zeros(max(cap, 1), dtype=np.uint32)
+        n = C.c_uint64()
+        check(self._lib.ntc_signature(self._h, int(plane), _np_ptr(h), _np_ptr(c), cap, C.byref(n)))
+        return h[:n.value].copy(), c[:n.value].copy()
+
+    def signature_inject(self, hashes, counts=None, plane=0, device=False):
+        """add pairs to a plane's signature: counts None = 1 each, duplicates add up, zeros are skipped (ntc_signature_inject).  device=True: hashes and
+        counts are (device pointer, n) and device pointer or None, read stream-ordered (ntc_signature_inject_device)"""
+        if device:
+            ptr, n = hashes
+            check(self._lib.ntc_signature_inject_device(self._h, int(plane), C.c_void_p(ptr) if n else None, C.c_void_p(counts) if counts else None, int(n)))
+            return
+        h = np.ascontiguousarray(hashes, dtype=np.uint64)
+        c = np.ascontiguousarray(counts, dtype=np.uint32) if counts is not None else None
+        assert c is None or c.size == h.size
+        check(self._lib.ntc_signature_inject(self._h, int(plane), _np_ptr(h) if h.size else None, _np_ptr(c) if c is not None and c.size else None, h.size))
+
+    def signature_stats(self):
+        """-> (table slots of all planes, doublings of a table since create / reset) (ntc_signature_stats)"""
+        slots, grows = C.c_uint64(), C.c_uint64()
+        check(self._lib.ntc_signature_stats(self._h, C.byref(slots), C.byref(grows)))
+        return slots.value, grows.value
+
+    def signature_time(self):
+        """-> (insert ms, grow ms) of the signature passes while profiling (ntc_signature_time)"""
+        a, b = C.c_double(), C.c_double()
+        check(self._lib.ntc_signature_time(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def signature_header(self, plane=0):
+        """-> dict(k, gap, strand, hpc, s_bits, mask, n=0): how this plane is counted, as a signature file records it (ntc_signature_header)"""
+        h = _abi.NtcSigHeader()
+        check(self._lib.ntc_signature_header(self._h, int(plane), C.byref(h)))
+        return _sig_header_dict(h)
 
     def sync(self):
         check(self._lib.ntc_sync(self._h))
@@ -347,6 +395,41 @@ def merge_devices(engines):
     the others are reset (ntc_merge_devices)"""
     arr = (C.c_void_p * len(engines))(*[e._h for e in engines])
     check(_abi.lib().ntc_merge_devices(arr, len(engines)))
+
+
+def _sig_header_dict(h):
+    return dict(k=h.k, gap=h.gap, strand=h.strand, hpc=h.hpc, s_bits=h.s_bits, mask=h.mask.decode(), n=h.n)
+
+
+def signature_compare(a, b):
+    """two hash lists (strictly ascending uint64) -> (common, jaccard, containment_a_in_b, containment_b_in_a); host only (ntc_signature_compare)"""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    c = C.c_uint64()
+    check(_abi.lib().ntc_signature_compare(_np_ptr(a) if a.size else None, a.size, _np_ptr(b) if b.size else None, b.size, C.byref(c)))
+    common, union = c.value, a.size + b.size - c.value
+    return common, (common / union if union else 0.0), (common / a.size if a.size else 0.0), (common / b.size if b.size else 0.0)
+
+
+def signature_write(path, header, hashes, counts):
+    """a signature file; header: dict(k, gap, strand, hpc, s_bits, mask) as Engine.signature_header() gives it (ntc_signature_write)"""
+    hs = np.ascontiguousarray(hashes, dtype=np.uint64)
+    cs = np.ascontiguousarray(counts, dtype=np.uint32)
+    assert hs.size == cs.size
+    h = _abi.NtcSigHeader()
+    h.k, h.gap, h.strand, h.hpc, h.s_bits, h.n = int(header["k"]), int(header["gap"]), int(header["strand"]), int(header["hpc"]), int(header["s_bits"]), hs.size
+    h.mask = header["mask"].encode()
+    check(_abi.lib().ntc_signature_write(str(path).encode(), C.byref(h), _np_ptr(hs) if hs.size else None, _np_ptr(cs) if cs.size else None))
+
+
+def signature_read(path):
+    """-> (header dict, hashes uint64[n], counts uint32[n]) of a signature file (ntc_signature_read)"""
+    h = _abi.NtcSigHeader()
+    check(_abi.lib().ntc_signature_read(str(path).encode(), C.byref(h), None, None, 0))
+    hs = np.zeros(max(h.n, 1), dtype=np.uint64)
+    cs = np.zeros(max(h.n, 1), dtype=np.uint32)
+    check(_abi.lib().ntc_signature_read(str(path).encode(), C.byref(h), _np_ptr(hs), _np_ptr(cs), max(h.n, 1)))
+    return _sig_header_dict(h), hs[:h.n].copy(), cs[:h.n].copy()
 
 
 # -- stateless entry points ---------------------------------------------------------------------
