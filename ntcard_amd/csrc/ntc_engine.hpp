@@ -108,6 +108,8 @@ struct Span {
 	}
 };
 
+enum Timer { T_HASH, T_APPLY, T_K1F, T_LONG_CUT, T_LONG_GATHER, T_HPC, T_SIG_INSERT, T_SIG_GROW, kTimers }; // ntc_engine::timers (T_K1F: outside the hash spans)
+
 // One device-resident tiled batch: equal-length reads (d_tails == nullptr) or one length bin of a ragged read set (read_len = 16 C)
 struct TiledSeg {
 	const unsigned char* d_tiles;
@@ -225,9 +227,12 @@ struct ntc_engine {
 	// batch, a sync).  `run` is that bracket while it is open (ev0 only).
 	bool profiling = false;
 	ntc_eng::Span run;
-	std::vector<ntc_eng::Span> pending, apply_pending, k1f_events; // closed spans: hash kernels, applies, K1f launches (outside the hash kernels' spans)
-	double ms_total = 0.0, apply_ms = 0.0, k1f_ms = 0.0;
-	uint64_t launches = 0, applies = 0;
+	struct {
+		std::vector<ntc_eng::Span> spans; // closed, not yet read: drain_events adds them to ms and count (the submits they covered) and drops them
+		double ms = 0.0;
+		uint64_t count = 0;
+	} timers[ntc_eng::kTimers];
+	uint64_t applies = 0; // (counted whether or not the engine is profiling)
 	bool ts_ok = false;             // the tiled kernel pair K1h + K1f is built for SOME k of this configuration (k_tiled says which) ...
 	bool ts_all = false;            // ... for every k (then nothing of a tiled batch is left to K1)
 	std::vector<uint8_t> k_tiled;   // per k of the list: K1h + K1f take it from tiled batches (the others are K1's, which stages the same tiles)
@@ -241,8 +246,6 @@ struct ntc_engine {
 	// d_untile; what ntc_long_stats and ntc_long_time report
 	DevBuf<unsigned char> d_long;
 	uint64_t long_pieces = 0, long_seqs = 0;
-	std::vector<ntc_eng::Span> long_cut_events, long_gather_events; // (filled while profiling, like `pending`)
-	double long_cut_ms = 0.0, long_gather_ms = 0.0;
 	// NTC_FLAG_HPC (ntc_submit.hip, ntc_hpc.hip): homopolymer-compressed counting.  ntc_submit_long_device compacts a round of whole sequences into d_hpc —
 	// an owner of its own: d_long is recycled by the rounds of the cut that then READ d_hpc — with d_hpc_aux as the kernels' scratch (offsets, keep bits,
 	// prefix table); hpc_mu serialises such calls (a round leaves e->mu between its compaction and its count); what ntc_hpc_stats / ntc_hpc_time report
@@ -250,8 +253,6 @@ struct ntc_engine {
 	DevBuf<unsigned char> d_hpc, d_hpc_aux;
 	std::mutex hpc_mu;
 	uint64_t hpc_bytes_in = 0, hpc_bytes_out = 0;
-	std::vector<ntc_eng::Span> hpc_events;
-	double hpc_ms = 0.0;
 	// NTC_FLAG_SIGNATURE (ntc_signature.hip): per plane an open-addressing table of the sampled 64-bit values and their counts, fed from a u64 value log
 	// that K1's signature instantiations append to.  d_sigstate: per plane {log cursor, live keys, values in the log} (device uint64), then one scratch cursor for the compaction.
 	// sig_booked: the WINDOWS of the launches since the last insert pass plus one chunk per wave of them, per plane — a hard bound of the log's cursor (a
@@ -268,8 +269,6 @@ struct ntc_engine {
 	DevBuf<uint32_t> d_sigtmp_c;                                  // ... (counts)
 	uint64_t sig_log_cap = 0, sig_log_limit = 0, sig_booked = 0, sig_init_slots = 0, sig_grows = 0;
 	uint32_t sig_chunk = 64;
-	std::vector<ntc_eng::Span> sig_insert_events, sig_grow_events;
-	double sig_insert_ms = 0.0, sig_grow_ms = 0.0;
 	DevBuf<uint32_t> d_tmeta;       // K1's slot table (len | len << 16 per read) of a RAGGED tiled batch under a list of which a part is K1's
 	uint32_t hll_bits = 0;          // != 0: nthll engine (d_sketch holds uint32 M[1<<hll_bits])
 	DevBuf<uint32_t> d_hll_thr;

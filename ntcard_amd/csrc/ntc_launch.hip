@@ -108,7 +108,7 @@ int close_span(Span& s, hipStream_t st, std::vector<Span>& into, hipEvent_t* rec
 }
 
 // the end of a bracketed run of tiled hash launches (ntc_engine::run)
-int close_run(ntc_engine* e, hipEvent_t* recorded) { return close_span(e->run, e->stream, e->pending, recorded); }
+int close_run(ntc_engine* e, hipEvent_t* recorded) { return close_span(e->run, e->stream, e->timers[T_HASH].spans, recorded); }
 
 namespace {
 int open_run(ntc_engine* e, hipEvent_t borrow = nullptr) // (borrow: the event a K1f in the middle of a k list has just left)
@@ -123,32 +123,15 @@ int drain_events(ntc_engine* e)
 {
 	if (int rc = close_run(e)) return rc;
 	// every span first (a span may borrow its first event from another list's), then the events go
-	auto elapsed = [](std::vector<Span>& v, double& ms_sum, uint64_t* launches) -> int {
-		for (const Span& s : v) {
+	for (auto& t : e->timers)
+		for (const Span& s : t.spans) {
 			float ms = 0.f;
 			HIP_TRY(hipEventSynchronize(s.ev1));
 			HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-			ms_sum += ms;
-			if (launches) *launches += s.submits;
+			t.ms += ms;
+			t.count += s.submits;
 		}
-		return 0;
-	};
-	if (int rc = elapsed(e->pending, e->ms_total, &e->launches)) return rc;
-	if (int rc = elapsed(e->apply_pending, e->apply_ms, nullptr)) return rc;
-	if (int rc = elapsed(e->k1f_events, e->k1f_ms, nullptr)) return rc;
-	if (int rc = elapsed(e->long_cut_events, e->long_cut_ms, nullptr)) return rc;
-	if (int rc = elapsed(e->long_gather_events, e->long_gather_ms, nullptr)) return rc;
-	if (int rc = elapsed(e->hpc_events, e->hpc_ms, nullptr)) return rc;
-	if (int rc = elapsed(e->sig_insert_events, e->sig_insert_ms, nullptr)) return rc;
-	if (int rc = elapsed(e->sig_grow_events, e->sig_grow_ms, nullptr)) return rc;
-	e->sig_insert_events.clear();
-	e->sig_grow_events.clear();
-	e->pending.clear();
-	e->apply_pending.clear();
-	e->k1f_events.clear();
-	e->long_cut_events.clear();
-	e->long_gather_events.clear();
-	e->hpc_events.clear();
+	for (auto& t : e->timers) t.spans.clear();
 	return 0;
 }
 
@@ -183,7 +166,7 @@ int join_k1f(ntc_engine* e, hipEvent_t* last)
 	const uint32_t n = e->k1f_n;
 	e->k1f_n = 0;
 	HIP_TRY(ntc::launch_k1h_fixup(e->k1f_batch, n, cus, e->stream));
-	return close_span(sp, e->stream, e->k1f_events, last);
+	return close_span(sp, e->stream, e->timers[T_K1F].spans, last);
 }
 
 namespace {
@@ -307,7 +290,7 @@ int apply_log(ntc_engine* e)
 	HIP_TRY(ntc::launch_count(c, std::min<unsigned>(ap.n_slices, (ap.slice_bits >= 15 ? 2u : 4u) * cus), e->stream));
 	e->sk_host_dirty = true;
 	if (c.mode == 0) HIP_TRY(hipMemsetAsync(e->d_logfill, 0, (size_t)e->all_log_regions() * 4, e->stream));
-	if (int rc = close_span(sp, e->stream, e->apply_pending)) return rc;
+	if (int rc = close_span(sp, e->stream, e->timers[T_APPLY].spans)) return rc;
 	e->log_pending = false;
 	e->log_est = 0.0;
 	e->applies += 1;
@@ -457,7 +440,7 @@ int run_k1(ntc_engine* e, const SlotBatch& b, const std::vector<uint8_t>* skip)
 		if (int rc = launch_k1_group(e, b, first, n)) return rc;
 		first += n;
 	}
-	if (int rc = close_span(sp, e->stream, e->pending)) return rc;
+	if (int rc = close_span(sp, e->stream, e->timers[T_HASH].spans)) return rc;
 	if (e->d_log && e->adaptive && !e->probed && e->log_est >= (double)(1u << 20)) { // enough logged since the reset: sample the log, decide log vs atomics
 		e->probed = true;
 		HIP_TRY(ntc::launch_log_probe(e->d_log, e->d_logfill, e->log_region_cap, std::min<uint32_t>(e->log_regions, 1024), 256, e->d_probe, 1u << 20,
@@ -491,7 +474,7 @@ int run_simple(ntc_engine* e, const SlotBatch& b) // the validation kernel: one 
 		Span sp;
 		if (int rc = open_span(e, sp)) return rc;
 		HIP_TRY(ntc::launch_hash(0, a, grid, smem, e->stream));
-		if (int rc = close_span(sp, e->stream, e->pending)) return rc;
+		if (int rc = close_span(sp, e->stream, e->timers[T_HASH].spans)) return rc;
 	}
 	return 0;
 }

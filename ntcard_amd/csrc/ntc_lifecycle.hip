@@ -396,14 +396,9 @@ int ntc_reset(ntc_engine* e)
 	if (int rc = drain_events(e)) return rc;
 	if (e->sig)
 		if (int rc = sig_reset(e)) return rc;
-	e->ms_total = 0.0;
-	e->launches = 0;
-	e->apply_ms = 0.0;
+	for (auto& t : e->timers) t.ms = 0.0, t.count = 0; // (drain_events has emptied their spans)
 	e->applies = 0;
-	e->k1f_ms = 0.0;
-	e->long_cut_ms = e->long_gather_ms = 0.0;
 	e->long_pieces = e->long_seqs = 0;
-	e->hpc_ms = 0.0;
 	e->hpc_bytes_in = e->hpc_bytes_out = 0;
 	return 0;
 }
@@ -489,21 +484,21 @@ int ntc_device_state(ntc_engine* e, void** d_sketch_u32, uint64_t* n_counters, v
 
 namespace {
 // the timing getters: drain the finished spans, then report a sum and (optionally) a count
-int timing(ntc_engine* e, const char* who, const double ntc_engine::*ms, double* ms_out, const uint64_t ntc_engine::*count, uint64_t* count_out)
+int timing(ntc_engine* e, const char* who, Timer t, double* ms_out, uint64_t* count_out = nullptr)
 {
 	if (!e) return fail(NTC_ERR_ARG, "%s: null engine", who);
 	std::lock_guard<std::mutex> lk(e->mu);
 	HIP_TRY(hipSetDevice(e->device));
 	if (int rc = drain_events(e)) return rc;
-	if (ms_out) *ms_out = e->*ms;
-	if (count_out) *count_out = e->*count;
+	if (ms_out) *ms_out = e->timers[t].ms;
+	if (count_out) *count_out = t == T_APPLY ? e->applies : e->timers[t].count;
 	return 0;
 }
 } // namespace
 
-int ntc_kernel_time(ntc_engine* e, double* ms_total, uint64_t* launches) { return timing(e, "ntc_kernel_time", &ntc_engine::ms_total, ms_total, &ntc_engine::launches, launches); }
-int ntc_apply_time(ntc_engine* e, double* ms_total, uint64_t* applies) { return timing(e, "ntc_apply_time", &ntc_engine::apply_ms, ms_total, &ntc_engine::applies, applies); }
-int ntc_fixup_time(ntc_engine* e, double* ms_total) { return timing(e, "ntc_fixup_time", &ntc_engine::k1f_ms, ms_total, &ntc_engine::applies, nullptr); }
+int ntc_kernel_time(ntc_engine* e, double* ms_total, uint64_t* launches) { return timing(e, "ntc_kernel_time", T_HASH, ms_total, launches); }
+int ntc_apply_time(ntc_engine* e, double* ms_total, uint64_t* applies) { return timing(e, "ntc_apply_time", T_APPLY, ms_total, applies); }
+int ntc_fixup_time(ntc_engine* e, double* ms_total) { return timing(e, "ntc_fixup_time", T_K1F, ms_total); }
 
 int ntc_merge_allocations(ntc_engine* e, uint64_t* n)
 {
@@ -524,8 +519,8 @@ int ntc_long_stats(ntc_engine* e, uint64_t* pieces, uint64_t* sequences)
 
 int ntc_long_time(ntc_engine* e, double* cut_ms, double* gather_ms)
 {
-	if (int rc = timing(e, "ntc_long_time", &ntc_engine::long_cut_ms, cut_ms, &ntc_engine::applies, nullptr)) return rc;
-	return timing(e, "ntc_long_time", &ntc_engine::long_gather_ms, gather_ms, &ntc_engine::applies, nullptr);
+	if (int rc = timing(e, "ntc_long_time", T_LONG_CUT, cut_ms)) return rc;
+	return timing(e, "ntc_long_time", T_LONG_GATHER, gather_ms);
 }
 
 int ntc_hpc_stats(ntc_engine* e, uint64_t* bytes_in, uint64_t* bytes_out)
@@ -537,7 +532,7 @@ int ntc_hpc_stats(ntc_engine* e, uint64_t* bytes_in, uint64_t* bytes_out)
 	return 0;
 }
 
-int ntc_hpc_time(ntc_engine* e, double* ms) { return timing(e, "ntc_hpc_time", &ntc_engine::hpc_ms, ms, &ntc_engine::applies, nullptr); }
+int ntc_hpc_time(ntc_engine* e, double* ms) { return timing(e, "ntc_hpc_time", T_HPC, ms); }
 
 int ntc_update_mode(ntc_engine* e, uint32_t* mode_out)
 {

@@ -193,7 +193,7 @@ int sig_room(ntc_engine* e, size_t pl, uint64_t add)
 		if (int rc = open_span(e, sp)) return rc;
 		HIP_TRY(hipMemsetAsync(sig_scratch(e), 0, 8, e->stream));
 		HIP_TRY(ntc::launch_sig_insert(ntc::SigTable{next.keys.get(), next.counts.get(), next.slots, sig_scratch(e)}, p.keys, p.counts, p.slots, e->stream));
-		if (int rc = close_span(sp, e->stream, e->sig_grow_events)) return rc;
+		if (int rc = close_span(sp, e->stream, e->timers[T_SIG_GROW].spans)) return rc;
 		HIP_TRY(hipStreamSynchronize(e->stream)); // (the new table is complete before the old one goes)
 		HIP_TRY(hipMemcpyAsync(sig_live(e, pl), sig_scratch(e), 8, hipMemcpyDeviceToDevice, e->stream));
 		return 0;
@@ -288,7 +288,6 @@ int sig_reset(ntc_engine* e)
 	}
 	e->sig_booked = 0;
 	e->sig_grows = 0;
-	e->sig_insert_ms = e->sig_grow_ms = 0.0;
 	return 0;
 }
 
@@ -360,7 +359,7 @@ int sig_flush(ntc_engine* e)
 		HIP_TRY(ntc::launch_sig_insert(sig_table(e, pl), e->d_siglog.get() + pl * e->sig_log_cap, nullptr, entries, e->stream));
 		HIP_TRY(hipMemsetAsync(sig_cursor(e, pl), 0, 8, e->stream));
 		HIP_TRY(hipMemsetAsync(sig_cursor(e, pl) + 2, 0, 8, e->stream));
-		if (int rc = close_span(sp, e->stream, e->sig_insert_events)) return rc;
+		if (int rc = close_span(sp, e->stream, e->timers[T_SIG_INSERT].spans)) return rc;
 		e->sig_planes[pl].live_ub += values;
 	}
 	e->sig_booked = 0;
@@ -508,8 +507,8 @@ int ntc_signature_time(ntc_engine* e, double* insert_ms, double* grow_ms)
 	std::lock_guard<std::mutex> lk(e->mu);
 	HIP_TRY(hipSetDevice(e->device));
 	if (int rc = drain_events(e)) return rc;
-	if (insert_ms) *insert_ms = e->sig_insert_ms;
-	if (grow_ms) *grow_ms = e->sig_grow_ms;
+	if (insert_ms) *insert_ms = e->timers[T_SIG_INSERT].ms;
+	if (grow_ms) *grow_ms = e->timers[T_SIG_GROW].ms;
 	return 0;
 }
 

@@ -974,78 +974,52 @@ __global__ __launch_bounds__(kPref <= 10 ? 1024 : 768) void sketch_hf_kernel(con
 #endif
 }
 
+// Every instantiation of K1, once: X(kMulti, kMode, kPref, kDump, kTiled, kOne, kSig).  Dispatch (launch_sketch_hf) and the dynamic-LDS attribute
+// (set_sketch_hf_smem_limit) both read the table below.  The order of the rows is the order the kernels are emitted in.
+#define HF_VARIANTS(X)                                                                                                                  \
+	/* NTC_FLAG_SIGNATURE: row slots, the 10-chunk prefetch only */                                                                     \
+	X(false, 1, 10, false, false, true, true) X(false, 1, 10, false, false, false, true) X(true, 0, 10, false, false, true, true)       \
+	X(true, 0, 10, false, false, false, true) X(false, 0, 10, false, false, true, true) X(false, 0, 10, false, false, false, true)      \
+	/* one strand: what a strand engine can reach (its tiled batches are re-laid out as row slots) */                                   \
+	X(false, 3, 10, false, false, true, false) X(false, 2, 10, false, false, true, false) X(false, 1, 10, true, false, true, false)     \
+	X(false, 0, 10, true, false, true, false) X(false, 1, 10, false, false, true, false) X(true, 0, 16, false, false, true, false)      \
+	X(true, 0, 10, false, false, true, false) X(false, 0, 16, false, false, true, false) X(false, 0, 10, false, false, true, false)     \
+	/* canonical: hash dump, nthll, spaced seed, tiled staging, row slots */                                                            \
+	X(false, 1, 10, true, false, false, false) X(false, 0, 10, true, false, false, false) X(false, 3, 10, false, false, false, false)   \
+	X(false, 2, 10, false, false, false, false) X(false, 1, 10, false, false, false, false) X(true, 0, 16, false, true, false, false)   \
+	X(true, 0, 10, false, true, false, false) X(false, 0, 16, false, true, false, false) X(false, 0, 10, false, true, false, false)     \
+	X(true, 0, 16, false, false, false, false) X(true, 0, 10, false, false, false, false) X(false, 0, 16, false, false, false, false)   \
+	X(false, 0, 10, false, false, false, false)
+
+struct HfVariant {
+	bool multi;
+	int mode, pref;
+	bool dump, tiled, one, sig;
+	void (*fn)(const HfArgs);
+};
+#define HF_ROW(multi, mode, pref, dump, tiled, one, sig) { multi, mode, pref, dump, tiled, one, sig, &sketch_hf_kernel<multi, mode, pref, dump, tiled, one, sig> },
+static const HfVariant kHfVariants[] = { HF_VARIANTS(HF_ROW) };
+#undef HF_ROW
+
 hipError_t launch_sketch_hf(const HfArgs& a, unsigned grid, unsigned waves_per_block, size_t smem, hipStream_t st)
 {
-	const dim3 g(grid), b(64u * waves_per_block);
-	const bool deep = sketch_hf_deep_prefetch(a.stride) && waves_per_block <= 12; // plain k-mer mode only
 	if (a.tiled != 0u && (a.dump != nullptr || a.gap != 0 || a.hll_bits != 0)) return hipErrorInvalidValue; // (tiled staging: plain k-mer mode only)
 	if (a.ks[0].strand > 2u || (a.ks[0].strand != 0u && a.tiled != 0u)) return hipErrorInvalidValue; // (one strand: row slots)
 	if (a.hll_bits != 0 && (a.n_k != 1 || a.dump != nullptr || a.hll_thr == nullptr)) return hipErrorInvalidValue; // (nthll: one plane per launch)
-	if (a.sig_cap != 0) { // NTC_FLAG_SIGNATURE: row slots only (tiled batches are re-laid out first); slots beyond the 10-chunk prefetch stage with blocking loads
-		if (a.tiled != 0u || a.dump != nullptr || a.hll_bits != 0 || a.sig_chunk < 64u) return hipErrorInvalidValue;
-		const bool one = a.ks[0].strand != 0u;
-		if (a.gap != 0 && one)
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, false, false, true, true>), g, b, smem, st, a);
-		else if (a.gap != 0)
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, false, false, false, true>), g, b, smem, st, a);
-		else if (a.n_k > 1 && one)
-			hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 10, false, false, true, true>), g, b, smem, st, a);
-		else if (a.n_k > 1)
-			hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 10, false, false, false, true>), g, b, smem, st, a);
-		else if (one)
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, false, false, true, true>), g, b, smem, st, a);
-		else
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, false, false, false, true>), g, b, smem, st, a);
-		return hipGetLastError();
-	}
-	if (a.ks[0].strand != 0u) { // the one-strand copies of the instantiations a strand engine can reach (its tiled batches are re-laid out as row slots)
-		if (a.hll_bits != 0 && a.gap != 0)
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 3, 10, false, false, true>), g, b, smem, st, a);
-		else if (a.hll_bits != 0)
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 2, 10, false, false, true>), g, b, smem, st, a);
-		else if (a.dump != nullptr && a.gap != 0)
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, true, false, true>), g, b, smem, st, a);
-		else if (a.dump != nullptr)
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, true, false, true>), g, b, smem, st, a);
-		else if (a.gap != 0)
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, false, false, true>), g, b, smem, st, a);
-		else if (a.n_k > 1 && deep)
-			hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 16, false, false, true>), g, b, smem, st, a);
-		else if (a.n_k > 1)
-			hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 10, false, false, true>), g, b, smem, st, a);
-		else if (deep)
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 16, false, false, true>), g, b, smem, st, a);
-		else
-			hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, false, false, true>), g, b, smem, st, a);
-		return hipGetLastError();
-	}
-	if (a.dump != nullptr && a.gap != 0)
-		hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10, true>), g, b, smem, st, a);
-	else if (a.dump != nullptr)
-		hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, true>), g, b, smem, st, a);
-	else if (a.hll_bits != 0 && a.gap != 0)
-		hipLaunchKernelGGL((sketch_hf_kernel<false, 3, 10>), g, b, smem, st, a);
-	else if (a.hll_bits != 0)
-		hipLaunchKernelGGL((sketch_hf_kernel<false, 2, 10>), g, b, smem, st, a);
-	else if (a.gap != 0)
-		hipLaunchKernelGGL((sketch_hf_kernel<false, 1, 10>), g, b, smem, st, a);
-	else if (a.tiled != 0u && a.n_k > 1 && deep)
-		hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 16, false, true>), g, b, smem, st, a);
-	else if (a.tiled != 0u && a.n_k > 1)
-		hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 10, false, true>), g, b, smem, st, a);
-	else if (a.tiled != 0u && deep)
-		hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 16, false, true>), g, b, smem, st, a);
-	else if (a.tiled != 0u)
-		hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10, false, true>), g, b, smem, st, a);
-	else if (a.n_k > 1 && deep)
-		hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 16>), g, b, smem, st, a);
-	else if (a.n_k > 1)
-		hipLaunchKernelGGL((sketch_hf_kernel<true, 0, 10>), g, b, smem, st, a);
-	else if (deep)
-		hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 16>), g, b, smem, st, a);
-	else
-		hipLaunchKernelGGL((sketch_hf_kernel<false, 0, 10>), g, b, smem, st, a);
-	return hipGetLastError();
+	// NTC_FLAG_SIGNATURE: row slots only (tiled batches are re-laid out first)
+	if (a.sig_cap != 0 && (a.tiled != 0u || a.dump != nullptr || a.hll_bits != 0 || a.sig_chunk < 64u)) return hipErrorInvalidValue;
+	// the wanted row.  A spaced seed or a dump takes the single-k form whatever n_k; the 16-chunk prefetch is for plain k-mer mode without signatures
+	// (their slots beyond the 10-chunk prefetch stage with blocking loads)
+	const bool sig = a.sig_cap != 0, one = a.ks[0].strand != 0u, dump = a.dump != nullptr, tiled = a.tiled != 0u;
+	const int mode = (a.gap != 0 ? 1 : 0) | (a.hll_bits != 0 ? 2 : 0);
+	const bool multi = a.n_k > 1 && mode == 0 && !dump;
+	const int pref = (mode == 0 && !dump && !sig && sketch_hf_deep_prefetch(a.stride) && waves_per_block <= 12) ? 16 : 10;
+	for (const HfVariant& v : kHfVariants)
+		if (v.multi == multi && v.mode == mode && v.pref == pref && v.dump == dump && v.tiled == tiled && v.one == one && v.sig == sig) {
+			hipLaunchKernelGGL(v.fn, dim3(grid), dim3(64u * waves_per_block), smem, st, a);
+			return hipGetLastError();
+		}
+	return hipErrorInvalidValue;
 }
 
 // validation: per read, the hashes of the valid windows in window order (the layout ntc_hash_dump_device documents)
@@ -1075,26 +1049,8 @@ bool sketch_hf_deep_prefetch(uint32_t stride) { return 64u * stride > 10u * 1024
 
 hipError_t set_sketch_hf_smem_limit(size_t smem)
 {
-	const void* fns[] = { reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 10>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 16>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 16>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 2, 10>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 10, false, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 16, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 16, false, true>),
-		              // one strand
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, false, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 10, false, false, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 16, false, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 16, false, false, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, false, false, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, true, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, true, false, true>),
-		              // nthll under a spaced seed, nthll of one strand
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 3, 10>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 2, 10, false, false, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 3, 10, false, false, true>),
-		              // signatures
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, false, false, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 10, false, false, false, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, false, false, false, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 0, 10, false, false, true, true>),
-		              reinterpret_cast<const void*>(&sketch_hf_kernel<true, 0, 10, false, false, true, true>), reinterpret_cast<const void*>(&sketch_hf_kernel<false, 1, 10, false, false, true, true>) };
-	for (const void* f : fns) {
-		const hipError_t rc = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+	for (const HfVariant& v : kHfVariants) {
+		const hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void*>(v.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 		if (rc != hipSuccess) return rc;
 	}
 	return hipSuccess;

@@ -282,7 +282,7 @@ int run_long_rounds(ntc_engine* e, const unsigned char* d_src, const ntc::LongSe
 			Span sp;
 			if (int rc = open_span(e, sp)) return rc;
 			HIP_TRY(ntc::launch_cut_tiles(d_src, d_seqs, (uint32_t)n_cut_seqs, first, np, L - (kmax - 1u), L, e->d_long, e->stream));
-			if (int rc = close_span(sp, e->stream, e->long_cut_events)) return rc;
+			if (int rc = close_span(sp, e->stream, e->timers[T_LONG_CUT].spans)) return rc;
 			const TiledSeg sg{e->d_long, np, L, nullptr, cut_k};
 			if (int rc = run_tiled_segs(e, &sg, 1, 1, true)) return rc; // (the tiles are recycled by the next round: their K1f may not be deferred)
 			e->long_pieces += np;
@@ -300,7 +300,7 @@ int run_long_rounds(ntc_engine* e, const unsigned char* d_src, const ntc::LongSe
 			Span sp;
 			if (int rc = open_span(e, sp)) return rc;
 			HIP_TRY(ntc::launch_gather_slots(d_src, d_spans + first, ns, rp.stride, e->d_long, d_meta, e->stream));
-			if (int rc = close_span(sp, e->stream, e->long_gather_events)) return rc;
+			if (int rc = close_span(sp, e->stream, e->timers[T_LONG_GATHER].spans)) return rc;
 			if (int rc = run_batch(e, e->d_long, d_meta, ns, (uint32_t)rp.len0, rp.stride)) return rc;
 		}
 	}
@@ -532,7 +532,7 @@ int submit_long_hpc(ntc_engine* e, const unsigned char* d_bases, const uint64_t*
 			Span sp;
 			if (int rc = open_span(e, sp)) return rc;
 			HIP_TRY(ntc::launch_hpc_compact(d_bases, offsets + s0, ns, e->d_hpc, e->d_hpc_aux.get(), e->stream));
-			if (int rc = close_span(sp, e->stream, e->hpc_events)) return rc;
+			if (int rc = close_span(sp, e->stream, e->timers[T_HPC].spans)) return rc;
 			HIP_TRY(hipMemcpyAsync(noff.data(), ntc::hpc_aux_offsets(e->d_hpc_aux.get(), ns), (ns + 1) * 8, hipMemcpyDeviceToHost, e->stream));
 			HIP_TRY(hipStreamSynchronize(e->stream));
 			e->hpc_bytes_in += n;

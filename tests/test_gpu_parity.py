@@ -916,3 +916,51 @@ def test_engine_lifecycle_returns_device_memory(nt):
     bound = len(klist) * 2 * 65536 * 4
     print("free device memory after each cycle:", free, "bound:", bound)
     assert max(free) - min(free) < bound, (free, bound)
+
+
+def test_every_timer_runs_and_reset_zeroes_it(nt):
+    """The engine's timed span kinds, each driven once with profiling on: the hash kernels and K1f (a tiled batch of 2049 reads, one tile and a read), the
+    apply (a flush), the cut and the gather of ntc_submit_long_device (one sequence with full pieces and a remainder, three without a piece), the homopolymer
+    compaction and the signature insert pass.  Every one reports a time above zero; ntc_kernel_time's launch count is the submits — one for the tiled batch,
+    and one each for the pieces and for the gathered row slots of the long submit — and ntc_reset leaves every figure, the signature grow time included, at zero."""
+    rng = random.Random(2049)
+    n, L = 2049, 150
+    reads = [rseq(rng, L, pn=0.0, plow=0.0) for _ in range(n)]
+    tiles = torch.from_numpy(nt.tile_reads(reads, L)).cuda()
+    seqs = [rseq(rng, m, pn=0.0, plow=0.0) for m in (5000, 100, 100, 100)]
+    offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+    d_seqs = torch.from_numpy(np.frombuffer(b"".join(seqs) + b"A" * 16, dtype=np.uint8).copy()).cuda()
+    with nt.Engine([32], r_bits=20, s_bits=7) as e:
+        e.set_profiling(True)
+        e.submit_tiled_device(tiles.data_ptr(), n, L)
+        e.flush()
+        ms, launches = e.kernel_time()
+        assert ms > 0.0 and launches == 1
+        assert e.fixup_time() > 0.0
+        ms, applies = e.apply_time()
+        assert ms > 0.0 and applies == 1
+        e.submit_long_device(d_seqs.data_ptr(), offs, 256)
+        e.sync()
+        cut, gather = e.long_time()
+        assert cut > 0.0 and gather > 0.0
+        assert e.kernel_time()[1] == 3
+        e.reset()
+        assert e.kernel_time() == (0.0, 0) and e.fixup_time() == 0.0 and e.apply_time() == (0.0, 0) and e.long_time() == (0.0, 0.0)
+    with nt.Engine([32], r_bits=20, s_bits=7, hpc=True) as e:
+        e.set_profiling(True)
+        e.submit_long_device(d_seqs.data_ptr(), offs, 256)
+        e.sync()
+        assert e.hpc_time() > 0.0
+        e.reset()
+        assert e.hpc_time() == 0.0 and e.kernel_time() == (0.0, 0) and e.long_time() == (0.0, 0.0)
+    slots, stride = to_slots(reads[:130], stride=152)
+    slots[slots == 10] = ord("A")
+    d_slots = torch.from_numpy(slots).cuda()
+    with nt.Engine([32], r_bits=20, s_bits=7, signature=True) as e:
+        e.set_profiling(True)
+        e.submit_device(d_slots.data_ptr(), 130, L, stride)
+        e.sync()
+        assert e.signature_time()[0] > 0.0 and e.kernel_time()[1] == 1
+        e.reset()
+        assert e.signature_time() == (0.0, 0.0) and e.kernel_time() == (0.0, 0)

@@ -206,6 +206,21 @@ def test_forms(nt, name):
     assert int(tc.sum()) == int(want[1].sum())  # every sampled value is one increment
 
 
+def test_fused_k_list_of_one_strand(nt):
+    """K1's row <true, 0, 10, false, false, true, true> (profiles/k1_variants.txt), which no other test dispatches: a fused k list on a forward engine, 130 reads in
+    row slots (two full waves and a partial one) — every plane's pairs against the model, the counters against strand_model"""
+    d, _, L, stride = device_slots()
+    rs, klist = reads()[:130], [64, 96]
+    with nt.Engine(klist, r_bits=R, s_bits=4, strand="forward", signature=True) as e:
+        e.submit_device(d.data_ptr(), len(rs), L, stride)
+        for pl, k in enumerate(klist):
+            want = sig_model.model(rs, k, "forward", 4)
+            assert want[0].size > 100 and same_sig(e.signature(pl), want)
+        tc, _, f1 = e.finish(counters=True)
+    wc, wf1 = sm.model_sketch(rs, ["1" * k for k in klist], sm.FORWARD, R, 4)
+    assert np.array_equal(f1, wf1) and np.array_equal(tc, wc)
+
+
 # ---- 7. routes ----
 def test_tiled_batches_are_relaid_out(nt):
     want = sig_model.equal_model(32, "canonical", 7)

@@ -308,6 +308,22 @@ def test_tiled_batches_with_a_mixed_k_list(nt, klist, s_bits, L, sizes):
             e.submit_tiled_device(keep[0].data_ptr(), len(parts[0]), L)
 
 
+def test_mixed_k_list_on_200_base_tiles_fuses_with_the_deep_prefetch(nt):
+    """K1's row <true, 0, 16, false, true> (profiles/k1_variants.txt), which no other test dispatches: k = 32,64,96 over ONE tiled batch of 2049 reads (a tile and a
+    read) of 200 bases — K1h + K1f take k = 32, K1 stages the same tiles for 64 and 96 in one fused launch, and 13 chunks per read (64 x 208 B = 13 KiB a wave)
+    are beyond the 10-chunk prefetch"""
+    rng = np.random.default_rng(200)
+    L, klist = 200, [32, 64, 96]
+    reads = _ragged_reads(rng, 2049, L, L, 0.003)
+    oc, of1 = orc.sketch_reads(reads, klist, 0, 18, 7)
+    t = torch.from_numpy(nt.tile_reads(reads, L)).cuda()
+    with nt.Engine(klist, r_bits=18, s_bits=7) as e:
+        e.submit_tiled_device(t.data_ptr(), len(reads), L)
+        tc, _, f1 = e.finish(counters=True)
+    assert np.array_equal(f1, of1), (f1, of1)
+    assert np.array_equal(tc, oc)
+
+
 def test_mixed_k_list_with_reads_too_long_for_tiled_staging(nt):
     """`-k 32,64` on equal-length 4 kb reads.  K1 cannot stage 64 slots of 4 kb next to its tables, so the host batch must take row slots
     (chunked) instead of tiles, and a device-resident tiled batch of such reads is refused with NOTHING counted (K1h used to count its k first)"""
