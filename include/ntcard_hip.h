@@ -139,7 +139,7 @@ typedef struct {
  *     counted without the flag into an engine with it (or the other way round) is the caller's mistake to avoid.  The dump and generator tools ignore it.
  * (Bits 4, 256, 2048 and 1 << 20 stay refused as unknown flags.) */
 #define NTC_FLAG_HPC 8192u
-/* SIGNATURES (additive to ABI 6: one flag bit, the ntc_signature* calls and ntc_sig_header; ntc_config and NTC_ABI_VERSION are unchanged).  The engine keeps,
+/* SIGNATURES (additive to ABI 6: one flag bit, the ntc_signature* calls — the device sort, compare and matrix among them — and ntc_sig_header; ntc_config and NTC_ABI_VERSION are unchanged).  The engine keeps,
  * per plane (a k of the list, or a mask), every value h it hands to ntComp (ntcard.cpp:132-145) that ntComp SAMPLES —
  *     sample 0: (h >> (63 - s)) == 1          sample 1: (h >> (64 - s)) == (1 << (s - 1)) - 1           s = s_bits
  * — with its exact multiplicity: a FracMinHash signature of the read set at rate ~ 2 * 2^-s.  h is whatever the engine counts: the canonical, forward or reverse
@@ -323,8 +323,12 @@ int ntc_hpc_time(ntc_engine *e, double *ms);
 /* brings pending work in (the value log is inserted; waits for the stream) and returns the number of distinct sampled values of the plane */
 int ntc_signature_size(ntc_engine *e, uint32_t plane, uint64_t *n);
 /* the plane's pairs, strictly ascending by hash: hashes[cap], counts[cap] (HOST; counts may be NULL), *n = the pairs written.  cap smaller than the
- * plane's size: NTC_ERR_ARG and nothing is written, *n included (ask ntc_signature_size).  The pairs are gathered on the device and sorted on the host. */
+ * plane's size: NTC_ERR_ARG and nothing is written, *n included (ask ntc_signature_size).  The pairs are gathered AND sorted on the device (ntc_signature_sort_device's kernels, with scratch the engine keeps: a
+ * second pair buffer and the sort's histograms, 12 B per pair); when that scratch cannot be had: NTC_ERR_MEMORY and nothing is written.
+ * ntc_signature_device: the same with the sorted pairs left in caller-owned DEVICE arrays on the engine's device (d_counts_u32 may be NULL); the same
+ * checks, the same refusal of a short cap; the arrays are complete when the call returns. */
 int ntc_signature(ntc_engine *e, uint32_t plane, uint64_t *hashes, uint32_t *counts, uint64_t cap, uint64_t *n);
+int ntc_signature_device(ntc_engine *e, uint32_t plane, void *d_hashes_u64, void *d_counts_u32, uint64_t cap, uint64_t *n);
 /* adds n pairs to the plane's signature: the merge-in for checkpoints and peers (and how tests drive the container on chosen keys).  counts == NULL: 1
  * each; duplicates inside a call are legal and add up; zeros are skipped; counts saturate at 2^32 - 1.  ntc_signature_inject: HOST arrays (copied before
  * the call returns).  ntc_signature_inject_device: DEVICE arrays, read stream-ordered on the engine's stream (they may be reused once the stream has
@@ -337,6 +341,25 @@ int ntc_signature_compare(const uint64_t *a, uint64_t na, const uint64_t *b, uin
  * rehash counts 10); ntc_signature_time: milliseconds of the insert passes and of the rehashes while profiling (ntc_set_profiling), outside ntc_kernel_time */
 int ntc_signature_stats(ntc_engine *e, uint64_t *slots, uint64_t *grows);
 int ntc_signature_time(ntc_engine *e, double *insert_ms, double *grow_ms);
+/* milliseconds of the device sorts of ntc_signature / ntc_signature_device while profiling (their one wait for the digit histograms included) */
+int ntc_signature_sort_time(ntc_engine *e, double *ms);
+/* Engine-less device tools (like ntc_hpc_compress_device: `device`, `stream` a hipStream_t or NULL; all three are synchronous and free their scratch).
+ *   ntc_signature_sort_device    sorts n pairs (uint64 key, uint32 value) in place, ascending by unsigned key and STABLE (equal keys keep their order);
+ *       d_vals_u32 may be NULL (keys only).  An LSD radix sort of 8-bit digits that skips every digit in which all keys agree; up to 4096 pairs are sorted by
+ *       one launch in LDS.  NTC_ERR_ARG for a NULL key array with n != 0 or n >= 2^32 (before the device is touched); NTC_ERR_MEMORY when the scratch — a
+ *       second key and value array plus histograms — cannot be had, with nothing changed; n == 0 touches nothing.
+ *   ntc_signature_compare_device *n_common = |A n B| of two strictly ascending DEVICE lists; when both count arrays and min_sum are non-NULL, *min_sum = the
+ *       sum of min(count_a, count_b) over the common hashes (uint64: the numerator of the abundance-weighted Jaccard), else min_sum is left alone.  Ascent
+ *       is checked on the device: NTC_ERR_ARG names the list and an offending entry, as ntc_signature_compare does.  NULL n_common, or a NULL list with a
+ *       length: NTC_ERR_ARG before the device is touched.  Empty lists are legal.
+ *   ntc_signature_matrix_device  all pairs at once: d_hashes_u64 is a HOST array of n_sigs DEVICE lists (1 <= n_sigs <= 1024; list i has n[i] strictly
+ *       ascending hashes, NULL allowed where n[i] == 0), common_out a HOST array [n_sigs][n_sigs]: common_out[i][j] = |S_i n S_j|, symmetric, the diagonal
+ *       n[i].  Every list's ascent is checked once; NTC_ERR_ARG names the index of an unsorted list.  The pairs are cut into work items (a pair and 4096
+ *       entries of its shorter list) that run 2^18 per launch.  On any error common_out is left alone. */
+int ntc_signature_sort_device(int32_t device, void *stream, void *d_keys_u64, void *d_vals_u32, uint64_t n);
+int ntc_signature_compare_device(int32_t device, void *stream, const void *d_a_u64, const void *d_ca_u32, uint64_t na, const void *d_b_u64,
+                                 const void *d_cb_u32, uint64_t nb, uint64_t *n_common, uint64_t *min_sum);
+int ntc_signature_matrix_device(int32_t device, void *stream, uint32_t n_sigs, const void *const *d_hashes_u64, const uint64_t *n, uint64_t *common_out);
 /* A signature FILE (`ntcard --signature`, bin/ntsig): little-endian; the 8 bytes "NTCSIG1\0", uint32 k, gap, strand, hpc, s_bits, mask_len, uint64 n, the mask
  * (mask_len bytes '0' / '1', all '1' for plain k; zero-padded to a multiple of 8), uint64 hashes[n], uint32 counts[n].  The header says how the file was
  * counted: two files compare only when they agree in everything but n.  Pure host functions.

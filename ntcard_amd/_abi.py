@@ -23,6 +23,7 @@ ABI_SYMBOLS = [
     "ntc_hpc_compress", "ntc_hpc_compress_device", "ntc_hpc_stats", "ntc_hpc_time",
     "ntc_signature_size", "ntc_signature", "ntc_signature_inject", "ntc_signature_inject_device", "ntc_signature_compare", "ntc_signature_stats",
     "ntc_signature_time", "ntc_signature_header", "ntc_signature_write", "ntc_signature_read",
+    "ntc_signature_device", "ntc_signature_sort_time", "ntc_signature_sort_device", "ntc_signature_compare_device", "ntc_signature_matrix_device",
 ]
 
 
@@ -130,6 +131,11 @@ def lib():
     L.ntc_signature_header.argtypes = [p, u32, C.POINTER(NtcSigHeader)]
     L.ntc_signature_write.argtypes = [C.c_char_p, C.POINTER(NtcSigHeader), p, p]
     L.ntc_signature_read.argtypes = [C.c_char_p, C.POINTER(NtcSigHeader), p, p, u64]
+    L.ntc_signature_device.argtypes = [p, u32, p, p, u64, C.POINTER(u64)]
+    L.ntc_signature_sort_time.argtypes = [p, C.POINTER(C.c_double)]
+    L.ntc_signature_sort_device.argtypes = [i32, p, p, p, u64]
+    L.ntc_signature_compare_device.argtypes = [i32, p, p, p, u64, p, p, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.ntc_signature_matrix_device.argtypes = [i32, p, u32, C.POINTER(p), C.POINTER(u64), p]
     L.ntc_sync.argtypes = [p]
     L.ntc_finish.argtypes = [p, p, p, p]
     L.ntc_merge_counters.argtypes = [p, p, p]

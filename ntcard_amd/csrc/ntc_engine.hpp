@@ -1,7 +1,8 @@
 // ntc_engine.hpp — the engine behind the C ABI (include/ntcard_hip.h): its state, the owners of its device resources and the functions its
 // translation units share.  ntc_plan.hip: launch geometry and policy (no HIP calls); ntc_launch.hip: everything that enters the engine's stream;
 // ntc_submit.hip: host packing, length bins, the staging pool; ntc_lifecycle.hip: create .. finish and the queries; ntc_merge.hip: multi-GPU merge
-// and log exchange; ntc_device_tools.hip: the entry points that need no engine.
+// and log exchange; ntc_device_tools.hip: the entry points that need no engine (those of signatures — sort, compare, matrix — sit with their kernels in
+// ntc_sig_sort.hip).
 //
 // Host-side mirror of the reference seam B2: ntc_create = the allocation/zeroing main() does (ntcard.cpp:433-439),
 // ntc_submit = a batch of ntRead/stRead calls (ntcard.cpp:147-171), ntc_finish = the state compEst reads (ntcard.cpp:237-247) + F1
@@ -108,7 +109,7 @@ struct Span {
 	}
 };
 
-enum Timer { T_HASH, T_APPLY, T_K1F, T_LONG_CUT, T_LONG_GATHER, T_HPC, T_SIG_INSERT, T_SIG_GROW, kTimers }; // ntc_engine::timers (T_K1F: outside the hash spans)
+enum Timer { T_HASH, T_APPLY, T_K1F, T_LONG_CUT, T_LONG_GATHER, T_HPC, T_SIG_INSERT, T_SIG_GROW, T_SIG_SORT, kTimers }; // ntc_engine::timers (T_K1F: outside the hash spans)
 
 // One device-resident tiled batch: equal-length reads (d_tails == nullptr) or one length bin of a ragged read set (read_len = 16 C)
 struct TiledSeg {
@@ -267,6 +268,11 @@ struct ntc_engine {
 	std::vector<SigPlane> sig_planes;
 	DevBuf<unsigned long long> d_siglog, d_sigstate, d_sigtmp_k; // [planes][sig_log_cap]; the state words; compaction / inject scratch (keys)
 	DevBuf<uint32_t> d_sigtmp_c;                                  // ... (counts)
+	// ntc_signature / ntc_signature_device sort the compaction on the device (ntc_sig_sort.hip): the second pair buffer the radix passes alternate with, and the
+	// sort's histograms; grow-only like the compaction's scratch, untouched while a plane fits the one-launch sort
+	DevBuf<unsigned long long> d_sigalt_k;
+	DevBuf<uint32_t> d_sigalt_c;
+	DevBuf<unsigned char> d_sigsort;
 	uint64_t sig_log_cap = 0, sig_log_limit = 0, sig_booked = 0, sig_init_slots = 0, sig_grows = 0;
 	uint32_t sig_chunk = 64;
 	DevBuf<uint32_t> d_tmeta;       // K1's slot table (len | len << 16 per read) of a RAGGED tiled batch under a list of which a part is K1's

@@ -6,10 +6,10 @@
 // home slot = the top bits of h * 0x9E3779B97F4A7C15 (the bits ntComp's patterns fix — the top s + 1 of h — only add a constant to the product), linear probing,
 // a 64-bit atomicCAS claims a slot, atomicAdd counts.  The host keeps every table at most half full BEFORE a launch inserts into it (sig_room), so no probe
 // runs round a full table and no kernel waits on another workgroup.  The same kernel re-inserts a table into its successor (growth), takes device or host
-// pairs (ntc_signature_inject*) and a peer's compacted pairs (ntc_merge_devices).  Vector stores and plain C++ only; every launch is on the engine's stream.
+// pairs (ntc_signature_inject*) and a peer's compacted pairs (ntc_merge_devices).  ntc_signature / ntc_signature_device compact a table and sort the compaction on
+// the device (ntc_sig_sort.hip).  Vector stores and plain C++ only; every launch is on the engine's stream.
 #include <cerrno>
 #include <cstdio>
-#include <numeric>
 
 #include "ntc_engine.hpp"
 
@@ -250,6 +250,33 @@ int sig_check(ntc_engine* e, uint32_t plane, const char* who)
 	return 0;
 }
 
+// the plane's pairs, strictly ascending by hash, in the engine's scratch: *k, *c (valid until the engine compacts again), *n of them.  Pending work is brought in,
+// the table is compacted and the compaction sorted on the device (ntc_sig_sort.hip); cap < n, or no memory for the scratch: an error before anything moves
+int sig_sorted(ntc_engine* e, uint32_t plane, uint64_t cap, const char* who, uint64_t* n, const unsigned long long** k, const uint32_t** c)
+{
+	if (int rc = join_k1f(e)) return rc;
+	if (int rc = sig_flush(e)) return rc;
+	std::vector<unsigned long long> st;
+	if (int rc = sig_read_state(e, st)) return rc;
+	const uint64_t live = st[kSigWords * plane + 1];
+	if (cap < live) return fail(NTC_ERR_ARG, "%s: plane %u holds %llu values, the arrays have room for %llu", who, plane, (unsigned long long)live, (unsigned long long)cap);
+	if (live >> 32) return fail(NTC_ERR_ARG, "%s: plane %u holds %llu values (fewer than 2^32 are sorted)", who, plane, (unsigned long long)live);
+	if (live > ntc::sig_sort_one_launch() &&
+	    (!e->d_sigalt_k.reserve(live * 8) || !e->d_sigalt_c.reserve(live * 4) || !e->d_sigsort.reserve(ntc::sig_sort_aux_bytes(live)))) {
+		(void)hipGetLastError();
+		return fail(NTC_ERR_MEMORY, "%s: cannot allocate %llu B of sort scratch on device; nothing was written", who, (unsigned long long)(live * 12 + ntc::sig_sort_aux_bytes(live)));
+	}
+	if (int rc = sig_compact(e, plane, n)) return rc;
+	bool in_alt = false;
+	Span sp;
+	if (int rc = open_span(e, sp)) return rc;
+	HIP_TRY(ntc::sig_sort(e->d_sigtmp_k, e->d_sigtmp_c, e->d_sigalt_k, e->d_sigalt_c, *n, e->d_sigsort.get(), e->stream, &in_alt));
+	if (int rc = close_span(sp, e->stream, e->timers[T_SIG_SORT].spans)) return rc;
+	*k = in_alt ? e->d_sigalt_k.get() : e->d_sigtmp_k.get();
+	*c = in_alt ? e->d_sigalt_c.get() : e->d_sigtmp_c.get();
+	return 0;
+}
+
 uint64_t env_u64(const char* name)
 {
 	const char* v = std::getenv(name);
@@ -417,28 +444,34 @@ int ntc_signature(ntc_engine* e, uint32_t plane, uint64_t* hashes, uint32_t* cou
 	if (!n_out || (!hashes && cap)) return fail(NTC_ERR_ARG, "ntc_signature: null argument");
 	std::lock_guard<std::mutex> lk(e->mu);
 	HIP_TRY(hipSetDevice(e->device));
-	if (int rc = join_k1f(e)) return rc;
-	if (int rc = sig_flush(e)) return rc;
-	std::vector<unsigned long long> st;
-	if (int rc = sig_read_state(e, st)) return rc;
-	const uint64_t n = st[kSigWords * plane + 1];
-	if (cap < n) return fail(NTC_ERR_ARG, "ntc_signature: plane %u holds %llu values, the arrays have room for %llu", plane, (unsigned long long)n, (unsigned long long)cap);
 	uint64_t got = 0;
-	if (int rc = sig_compact(e, plane, &got)) return rc;
-	std::vector<unsigned long long> k(got);
-	std::vector<uint32_t> c(got);
+	const unsigned long long* k = nullptr;
+	const uint32_t* c = nullptr;
+	if (int rc = sig_sorted(e, plane, cap, "ntc_signature", &got, &k, &c)) return rc;
 	if (got) {
-		HIP_TRY(hipMemcpyAsync(k.data(), e->d_sigtmp_k, got * 8, hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipMemcpyAsync(c.data(), e->d_sigtmp_c, got * 4, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(hashes, k, got * 8, hipMemcpyDeviceToHost, e->stream));
+		if (counts) HIP_TRY(hipMemcpyAsync(counts, c, got * 4, hipMemcpyDeviceToHost, e->stream));
 	}
 	HIP_TRY(hipStreamSynchronize(e->stream));
-	std::vector<uint64_t> order(got); // the final sort runs on the host: finish is not hot
-	std::iota(order.begin(), order.end(), 0);
-	std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return k[x] < k[y]; });
-	for (uint64_t i = 0; i < got; ++i) {
-		hashes[i] = k[order[i]];
-		if (counts) counts[i] = c[order[i]];
+	*n_out = got;
+	return drain_events(e);
+}
+
+int ntc_signature_device(ntc_engine* e, uint32_t plane, void* d_hashes, void* d_counts, uint64_t cap, uint64_t* n_out)
+{
+	if (int rc = sig_check(e, plane, "ntc_signature_device")) return rc;
+	if (!n_out || (!d_hashes && cap)) return fail(NTC_ERR_ARG, "ntc_signature_device: null argument");
+	std::lock_guard<std::mutex> lk(e->mu);
+	HIP_TRY(hipSetDevice(e->device));
+	uint64_t got = 0;
+	const unsigned long long* k = nullptr;
+	const uint32_t* c = nullptr;
+	if (int rc = sig_sorted(e, plane, cap, "ntc_signature_device", &got, &k, &c)) return rc;
+	if (got) {
+		HIP_TRY(hipMemcpyAsync(d_hashes, k, got * 8, hipMemcpyDeviceToDevice, e->stream));
+		if (d_counts) HIP_TRY(hipMemcpyAsync(d_counts, c, got * 4, hipMemcpyDeviceToDevice, e->stream));
 	}
+	HIP_TRY(hipStreamSynchronize(e->stream)); // (the arrays are complete, and the engine's scratch is free again)
 	*n_out = got;
 	return drain_events(e);
 }
@@ -509,6 +542,16 @@ int ntc_signature_time(ntc_engine* e, double* insert_ms, double* grow_ms)
 	if (int rc = drain_events(e)) return rc;
 	if (insert_ms) *insert_ms = e->timers[T_SIG_INSERT].ms;
 	if (grow_ms) *grow_ms = e->timers[T_SIG_GROW].ms;
+	return 0;
+}
+
+int ntc_signature_sort_time(ntc_engine* e, double* ms)
+{
+	if (int rc = sig_check(e, 0, "ntc_signature_sort_time")) return rc;
+	std::lock_guard<std::mutex> lk(e->mu);
+	HIP_TRY(hipSetDevice(e->device));
+	if (int rc = drain_events(e)) return rc;
+	if (ms) *ms = e->timers[T_SIG_SORT].ms;
 	return 0;
 }
 

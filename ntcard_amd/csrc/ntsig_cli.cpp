@@ -1,7 +1,11 @@
 // ntsig_cli.cpp — `ntsig`: signature files (`ntcard --signature`, include/ntcard_hip.h: ntc_signature_write) from the command line.
 //   ntsig info F.sig            the header: how the file was counted, and how many values it holds
 //   ntsig compare A.sig B.sig   |A n B|, Jaccard and both containments — refused when the headers differ in anything but n
-// Host code over the library's reader and ntc_signature_compare; needs no GPU.
+//   ntsig matrix [--containment] A.sig B.sig ...   all pairs at once, as a TSV: Jaccard, or the containment of the row's file in the column's
+// info and compare are host code over the library's reader and ntc_signature_compare and need no GPU; matrix reads every header first (files counted
+// differently are refused before a device is looked for), then uploads the hash lists and calls ntc_signature_matrix_device.
+#include <hip/hip_runtime_api.h>
+
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,9 +48,85 @@ void print_header(const char* path, const ntc_sig_header& h)
 	            (unsigned long long)h.n);
 }
 
+// what two headers differ in beside n (nullptr: nothing — their values compare)
+const char* differs_in(const ntc_sig_header& a, const ntc_sig_header& b)
+{
+	if (a.k != b.k) return "k";
+	if (std::strcmp(a.mask, b.mask) != 0) return "mask";
+	if (a.gap != b.gap) return "gap";
+	if (a.strand != b.strand) return "strand";
+	if (a.hpc != b.hpc) return "hpc";
+	if (a.s_bits != b.s_bits) return "sBits";
+	return nullptr;
+}
+
+int refuse(const char* a, const char* b, const char* differs)
+{
+	std::fprintf(stderr, "ntsig: %s and %s were counted differently (%s differs): their values cannot be compared\n", a, b, differs);
+	return EXIT_FAILURE;
+}
+
+// device copies of the hash lists, freed on every way out
+struct DeviceLists {
+	std::vector<void*> p;
+	~DeviceLists()
+	{
+		for (void* q : p)
+			if (q) (void)hipFree(q);
+	}
+};
+
+int matrix(int n_files, char** files, bool containment)
+{
+	std::vector<Sig> sigs(n_files);
+	for (int i = 0; i < n_files; ++i)
+		if (!load(files[i], sigs[i], false)) return EXIT_FAILURE;
+	for (int i = 1; i < n_files; ++i)
+		if (const char* d = differs_in(sigs[0].h, sigs[i].h)) return refuse(files[0], files[i], d);
+	for (int i = 0; i < n_files; ++i)
+		if (!load(files[i], sigs[i], true)) return EXIT_FAILURE;
+	// the library says whether a device can be used: the matrix of one empty list touches the device and nothing else
+	uint64_t none = 0, probe = 0;
+	const void* null_list = nullptr;
+	if (ntc_signature_matrix_device(0, nullptr, 1, &null_list, &none, &probe) != 0) {
+		std::fprintf(stderr, "ntsig: %s\n", ntc_last_error());
+		return EXIT_FAILURE;
+	}
+	DeviceLists d;
+	d.p.assign(n_files, nullptr);
+	std::vector<uint64_t> n(n_files);
+	for (int i = 0; i < n_files; ++i) {
+		n[i] = sigs[i].h.n;
+		if (n[i] == 0) continue;
+		hipError_t rc = hipMalloc(&d.p[i], n[i] * 8);
+		if (rc == hipSuccess) rc = hipMemcpy(d.p[i], sigs[i].hashes.data(), n[i] * 8, hipMemcpyHostToDevice);
+		if (rc != hipSuccess) {
+			std::fprintf(stderr, "ntsig: cannot bring the %llu values of %s to the device: %s\n", (unsigned long long)n[i], files[i], hipGetErrorString(rc));
+			return EXIT_FAILURE;
+		}
+	}
+	std::vector<uint64_t> common((size_t)n_files * n_files);
+	if (ntc_signature_matrix_device(0, nullptr, (uint32_t)n_files, d.p.data(), n.data(), common.data()) != 0) {
+		std::fprintf(stderr, "ntsig: %s\n", ntc_last_error());
+		return EXIT_FAILURE;
+	}
+	for (int j = 0; j < n_files; ++j)
+		std::printf("\t%s", files[j]);
+	std::printf("\n");
+	for (int i = 0; i < n_files; ++i) {
+		std::printf("%s", files[i]);
+		for (int j = 0; j < n_files; ++j) {
+			const uint64_t c = common[(size_t)i * n_files + j], den = containment ? n[i] : n[i] + n[j] - c;
+			std::printf("\t%.6f", den ? (double)c / (double)den : 0.0);
+		}
+		std::printf("\n");
+	}
+	return EXIT_SUCCESS;
+}
+
 int usage()
 {
-	std::fprintf(stderr, "Usage: ntsig info F.sig\n       ntsig compare A.sig B.sig\n");
+	std::fprintf(stderr, "Usage: ntsig info F.sig\n       ntsig compare A.sig B.sig\n       ntsig matrix [--containment] A.sig B.sig ...\n");
 	return EXIT_FAILURE;
 }
 
@@ -65,17 +145,7 @@ int main(int argc, char** argv)
 	if (cmd == "compare" && argc == 4) {
 		Sig a, b;
 		if (!load(argv[2], a, true) || !load(argv[3], b, true)) return EXIT_FAILURE;
-		const char* differs = nullptr;
-		if (a.h.k != b.h.k) differs = "k";
-		else if (std::strcmp(a.h.mask, b.h.mask) != 0) differs = "mask";
-		else if (a.h.gap != b.h.gap) differs = "gap";
-		else if (a.h.strand != b.h.strand) differs = "strand";
-		else if (a.h.hpc != b.h.hpc) differs = "hpc";
-		else if (a.h.s_bits != b.h.s_bits) differs = "sBits";
-		if (differs) {
-			std::fprintf(stderr, "ntsig: %s and %s were counted differently (%s differs): their values cannot be compared\n", argv[2], argv[3], differs);
-			return EXIT_FAILURE;
-		}
+		if (const char* differs = differs_in(a.h, b.h)) return refuse(argv[2], argv[3], differs);
 		uint64_t common = 0;
 		if (ntc_signature_compare(a.hashes.data(), a.h.n, b.hashes.data(), b.h.n, &common) != 0) {
 			std::fprintf(stderr, "ntsig: %s\n", ntc_last_error());
@@ -86,6 +156,12 @@ int main(int argc, char** argv)
 		std::printf("jaccard\t%.6f\ncontainment_a_in_b\t%.6f\ncontainment_b_in_a\t%.6f\n", uni ? (double)common / (double)uni : 0.0,
 		            a.h.n ? (double)common / (double)a.h.n : 0.0, b.h.n ? (double)common / (double)b.h.n : 0.0);
 		return EXIT_SUCCESS;
+	}
+	if (cmd == "matrix") {
+		const bool containment = argc > 2 && std::strcmp(argv[2], "--containment") == 0;
+		const int first = containment ? 3 : 2;
+		if (argc - first < 1 || argc - first > 1024) return usage();
+		return matrix(argc - first, argv + first, containment);
 	}
 	return usage();
 }

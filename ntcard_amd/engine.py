@@ -227,6 +227,24 @@ class Engine:
         check(self._lib.ntc_signature(self._h, int(plane), _np_ptr(h), _np_ptr(c), cap, C.byref(n)))
         return h[:n.value].copy(), c[:n.value].copy()
 
+    def signature_device(self, plane=0):
+        """-> (hashes torch.int64[n] — the uint64 values' bits —, counts torch.int32[n] — uint32 likewise —, n): signature() with the sorted pairs left on the
+        engine's device (ntc_signature_device)"""
+        import torch
+        cap = self.signature_size(plane)
+        dev = torch.device("cuda", self.device)
+        h = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        c = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        n = C.c_uint64()
+        check(self._lib.ntc_signature_device(self._h, int(plane), C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), cap, C.byref(n)))
+        return h[:n.value], c[:n.value], n.value
+
+    def signature_sort_time(self):
+        """-> ms of the device sorts of signature() / signature_device() while profiling (ntc_signature_sort_time)"""
+        ms = C.c_double()
+        check(self._lib.ntc_signature_sort_time(self._h, C.byref(ms)))
+        return ms.value
+
     def signature_inject(self, hashes, counts=None, plane=0, device=False):
         """add pairs to a plane's signature: counts None = 1 each, duplicates add up, zeros are skipped (ntc_signature_inject).  device=True: hashes and
         counts are (device pointer, n) and device pointer or None, read stream-ordered (ntc_signature_inject_device)"""
@@ -409,6 +427,36 @@ def signature_compare(a, b):
     check(_abi.lib().ntc_signature_compare(_np_ptr(a) if a.size else None, a.size, _np_ptr(b) if b.size else None, b.size, C.byref(c)))
     common, union = c.value, a.size + b.size - c.value
     return common, (common / union if union else 0.0), (common / a.size if a.size else 0.0), (common / b.size if b.size else 0.0)
+
+
+def signature_sort_device(ptr_keys, ptr_vals, n, device=0, stream=None):
+    """n device pairs (uint64 key, uint32 value; ptr_vals None or 0: keys only) sorted in place, ascending by key and stable; synchronous
+    (ntc_signature_sort_device)"""
+    check(_abi.lib().ntc_signature_sort_device(device, C.c_void_p(stream) if stream else None, C.c_void_p(ptr_keys) if ptr_keys else None,
+                                               C.c_void_p(ptr_vals) if ptr_vals else None, int(n)))
+
+
+def signature_compare_device(ptr_a, ptr_counts_a, na, ptr_b, ptr_counts_b, nb, device=0, stream=None):
+    """two device hash lists (strictly ascending uint64; counts uint32 or None) -> (common, min_sum): |A n B| and, when both have counts, the sum of
+    min(count_a, count_b) over the common hashes, else None; synchronous (ntc_signature_compare_device)"""
+    c, m = C.c_uint64(), C.c_uint64()
+    both = bool(ptr_counts_a) and bool(ptr_counts_b)
+    check(_abi.lib().ntc_signature_compare_device(device, C.c_void_p(stream) if stream else None, C.c_void_p(ptr_a) if ptr_a else None,
+                                                  C.c_void_p(ptr_counts_a) if ptr_counts_a else None, int(na), C.c_void_p(ptr_b) if ptr_b else None,
+                                                  C.c_void_p(ptr_counts_b) if ptr_counts_b else None, int(nb), C.byref(c), C.byref(m) if both else None))
+    return c.value, (m.value if both else None)
+
+
+def signature_matrix_device(ptrs, ns, device=0, stream=None):
+    """device hash lists ptrs[i] of ns[i] strictly ascending uint64 each -> np.ndarray[uint64] (len, len): the size of every pair's intersection, the diagonal
+    ns; synchronous (ntc_signature_matrix_device)"""
+    assert len(ptrs) == len(ns)
+    k = len(ptrs)
+    arr = (C.c_void_p * max(k, 1))(*[C.c_void_p(int(p)) if p else None for p in ptrs])
+    n = (C.c_uint64 * max(k, 1))(*[int(x) for x in ns])
+    out = np.zeros((k, k), dtype=np.uint64)
+    check(_abi.lib().ntc_signature_matrix_device(device, C.c_void_p(stream) if stream else None, k, arr, n, _np_ptr(out) if k else None))
+    return out
 
 
 def signature_write(path, header, hashes, counts):
