@@ -7,6 +7,8 @@ import random
 
 import numpy as np
 
+from support import offsets_of
+
 NONE = 255
 CLASS = np.full(256, NONE, dtype=np.uint8)
 for letters, c in ((b"Aa", 0), (b"Cc", 1), (b"Gg", 2), (b"TtUu", 3)):
@@ -53,13 +55,6 @@ def compress_many(buf, offsets):
     pre = np.zeros(a.size + 1, dtype=np.uint64)
     np.cumsum(keep, dtype=np.uint64, out=pre[1:])
     return a[keep], pre[offs - offs[0]]
-
-
-def offsets_of(seqs, lead=0):
-    offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
-    offs[0] = lead
-    offs[1:] = lead + np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    return offs
 
 
 def runs_seq(rng, n, p_more=0.5, p_low=0.1, p_other=0.01):
@@ -173,12 +168,6 @@ def runs_array(gen, n, p_more=0.5, p_low=0.1, p_other=0.01):
     return a
 
 
-def lens_offsets(lens):
-    offs = np.zeros(len(lens) + 1, dtype=np.uint64)
-    offs[1:] = np.cumsum(lens, dtype=np.uint64)
-    return offs
-
-
 @functools.lru_cache(maxsize=None)
 def pair_seq():
     """one sequence that holds every ordered pair of byte values: (a, b) for a, b = 0 .. 255 behind one another, 131072 bytes"""
@@ -200,7 +189,7 @@ def pair_want():
     drop = (CLASS[s[:, 1]] != NONE) & (CLASS[s[:, 1]] == CLASS[s[:, 0]])
     keep = np.ones(s.shape, dtype=bool)
     keep[:, 1] = ~drop
-    return s[keep], lens_offsets(2 - drop.astype(np.int64))
+    return s[keep], offsets_of(2 - drop.astype(np.int64))
 
 
 @functools.lru_cache(maxsize=None)
@@ -208,7 +197,7 @@ def many_short():
     """530 000 sequences of 0 .. 20 bytes over ACGTacgtUuNR, 5.3 MB: more sequences than the mark and offsets kernels have threads, more chunks than the scan
     kernel has threads"""
     gen = np.random.default_rng(530)
-    offs = lens_offsets(gen.integers(0, 21, size=530_000))
+    offs = offsets_of(gen.integers(0, 21, size=530_000))
     return np.frombuffer(b"ACGTacgtUuNR", dtype=np.uint8)[gen.integers(0, 12, size=int(offs[-1]))], offs
 
 
@@ -227,4 +216,4 @@ def few_large():
     """about 8.5 MiB in four sequences"""
     gen = np.random.default_rng(85)
     lens = [3_000_001, 2_500_003, 7, 3_412_000]
-    return runs_array(gen, sum(lens)), lens_offsets(lens)
+    return runs_array(gen, sum(lens)), offsets_of(lens)

@@ -19,13 +19,13 @@ import numpy as np
 
 import k1h_model as km
 import orc
+from support import TILE, sampled, tile  # noqa: F401  (re-exported: kc.tile)
 
 Case = collections.namedtuple("Case", "reads read_len k s_bits gap tails")
 
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 MIMIC = {ord("A"): ord("H"), ord("C"): ord("K"), ord("T"): ord("D"), ord("G"): ord("N")}  # same (byte >> 1) & 3, no base
 SLOT_BYTES = (1, 3, 4, 5, 7)  # bases to the reference's seed table, no letters to the packing kernels
-TILE = 2048
 FILL_TO = TILE + 1 + 3
 POOL_MIN = 16
 N = ord("N")
@@ -45,18 +45,6 @@ def _filled(reads, rng, L):
     return reads
 
 
-def tile(reads, read_len, unused=ord("A")):
-    """reads (list of bytes, none longer than 16 ceil(read_len / 16)) -> the tiled layout; bytes behind a read's end hold 'A' (the ABI asks for a base
-    letter there), the slots behind the batch's last read hold `unused`"""
-    n, Cn = len(reads), (read_len + 15) // 16
-    ntl = (n + TILE - 1) // TILE
-    a = np.full((ntl * TILE, Cn * 16), ord("A"), dtype=np.uint8)
-    a[n:] = unused
-    for i, r in enumerate(reads):
-        a[i, :len(r)] = np.frombuffer(r, dtype=np.uint8)
-    return np.ascontiguousarray(a.reshape(ntl, TILE, Cn, 16).transpose(0, 2, 1, 3)).reshape(-1)
-
-
 # ---- planted windows ----------------------------------------------------------------------------------------------------------------
 def _strand_hashes(idx, k, gap):
     """forward and reverse ntHash of every window of a sequence given as indices into "ACGT" (the closed form, nthash.hpp:220-239; spaced seed: the
@@ -72,15 +60,6 @@ def _strand_hashes(idx, k, gap):
         f ^= tf[idx[i:i + n]]
         r ^= tr[idx[i:i + n]]
     return f, r
-
-
-def key_of(h, s_bits):
-    """ntComp's two patterns (ntcard.cpp:132-145) -> 0 / 1, or None"""
-    if (h >> (63 - s_bits)) == 1:
-        return 0
-    if (h >> (64 - s_bits)) == (1 << (s_bits - 1)) - 1:
-        return 1
-    return None
 
 
 @functools.lru_cache(maxsize=None)
@@ -105,12 +84,12 @@ def pools(k, s_bits, gap=0):
             ok, fv, rv = km.window_hashes(win, k, gap)
             assert ok and fv == int(f[s]) and rv == int(r[s])
             cf, cr = km.flags_of(fv, rv, s_bits)
-            sampled = key_of(min(fv, rv), s_bits) is not None
+            hit = bool(sampled(min(fv, rv), s_bits))
             if cf and cr:
                 out["tie"].append(win)
             elif cf or cr:
-                assert sampled or s_bits >= 8
-                out["plain" if sampled else "below"].append(win)
+                assert hit or s_bits >= 8
+                out["plain" if hit else "below"].append(win)
         for s in range(0, n - k, 997):
             ok, fv, rv = km.window_hashes(seq[s:s + k], k, gap)
             if not any(km.flags_of(fv, rv, s_bits)) and len(out["none"]) < 64:

@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "ntcard_amd", "csrc"))
 import gen_k1h  # noqa: E402
 from k1h_asm import Emu  # noqa: E402
 import orc  # noqa: E402
+from support import key_of  # noqa: E402
 
 CODE2_OF = {ord("A"): 0, ord("C"): 1, ord("T"): 2, ord("G"): 3, ord("U"): 2, ord("a"): 0, ord("c"): 1, ord("t"): 2, ord("g"): 3, ord("u"): 2}
 BASE_OF_CODE2 = "ACTG"
@@ -171,13 +172,6 @@ def k1f_model(reads, read_len, k, r_bits, s_bits, dirty, tie, sus=None, sus_over
     keys, f1_sub = [], 0
     fh, rh, bad = C.c_uint64(), C.c_uint64(), C.c_uint()
 
-    def key_of(h):
-        if (h >> (63 - s_bits)) == 1:
-            return h & ((1 << r_bits) - 1)
-        if (h >> (64 - s_bits)) == (1 << (s_bits - 1)) - 1:
-            return (1 << r_bits) + (h & ((1 << r_bits) - 1))
-        return None
-
     for r, seq in enumerate(reads):
         t, lane, m = r // 2048, (r % 2048) % 64, (r % 2048) // 64
         for b in range(NB):
@@ -194,7 +188,7 @@ def k1f_model(reads, read_len, k, r_bits, s_bits, dirty, tie, sus=None, sus_over
                     continue
                 cf, cr = flags_of(fv, rv, s_bits)
                 if aff or (tb and cf and cr):  # slow path: every window of a dirty-affected block, and the both-flag windows of tie blocks
-                    kk = key_of(min(fv, rv))
+                    kk = key_of(min(fv, rv), r_bits, s_bits)
                     if kk is not None:
                         keys.append(kk)
     if sus is not None and not sus_overflow:
@@ -203,7 +197,7 @@ def k1f_model(reads, read_len, k, r_bits, s_bits, dirty, tie, sus=None, sus_over
             win = reads[r][w: w + k]
             ok, fv, rv = window_hashes(win, k, gap)
             if ok:
-                kk = key_of(min(fv, rv))
+                kk = key_of(min(fv, rv), r_bits, s_bits)
                 assert kk is not None or s_bits > 7, (r, w)  # (s_bits >= 8: the walk tests a prefix of the patterns, a suspect may turn out to be none)
                 # K1f's fast path: K1h's own verdict stands for every suspect that is not marked as a tie (mark bit 2) — its counter index, and "no hit"
                 # (mark bit 1) where the pattern fails below the 8-bit prefix; a tie is re-derived from the bytes (the entry may be of the wrong strand).

@@ -14,9 +14,9 @@ import numpy as np
 
 import k1h_model as km
 import strand_model as sm
+from support import ALPHA, gap_mask, key_of, random_reads, tile_array
 
 gen_k1h = km.gen_k1h
-ALPHA = np.frombuffer(b"ACGTacgtUuNnRYKM.-*", dtype=np.uint8)
 
 
 @contextlib.contextmanager
@@ -36,23 +36,6 @@ def strand_gen(strand):
 def run_k1h(strand, *args, **kw):
     with strand_gen(strand):
         return km.run_k1h(*args, **kw)
-
-
-def tile_array(arr):
-    n, L = arr.shape
-    C16, ntl = (L + 15) // 16, (n + 2047) // 2048
-    a = np.full((ntl * 2048, C16 * 16), ord("A"), dtype=np.uint8)
-    a[:n, :L] = arr
-    return np.ascontiguousarray(a.reshape(ntl, 2048, C16, 16).transpose(0, 2, 1, 3)).reshape(-1)
-
-
-def key_of(h, r_bits, s_bits):
-    """ntComp (ntcard.cpp:132-145) -> counter index within the plane, or None"""
-    if (h >> (63 - s_bits)) == 1:
-        return h & ((1 << r_bits) - 1)
-    if (h >> (64 - s_bits)) == (1 << (s_bits - 1)) - 1:
-        return (1 << r_bits) + (h & ((1 << r_bits) - 1))
-    return None
 
 
 def k1f_strand_model(reads, read_len, k, r_bits, s_bits, strand, res, gap=0):
@@ -103,23 +86,14 @@ def check(strand, reads, arr, n, read_len, k, r_bits, s_bits, gap, n_waves, tail
     res = run_k1h(strand, tile_array(arr), n, read_len, k, r_bits=r_bits, n_waves=n_waves, s_bits=s_bits, gap=gap, tails=tails, **kw)
     fk, f1_sub = k1f_strand_model(reads, read_len, k, r_bits, s_bits, strand, res, gap=gap)
     got = np.bincount(np.concatenate([res["keys"], np.array(fk, dtype=np.uint32)]).astype(np.int64), minlength=2 << r_bits).astype(np.uint32) + res["sketch"]
-    mask = "1" * ((k - gap) // 2) + "0" * gap + "1" * (k - gap - (k - gap) // 2)   # ntcard's one seed (ntcard.cpp:407-413); gap 0: plain k-mers
-    tc, f1 = sm.model_sketch(reads, [mask], strand, r_bits, s_bits)
+    tc, f1 = sm.model_sketch(reads, [gap_mask(k, gap)], strand, r_bits, s_bits)
     assert res["f1"] - f1_sub == int(f1[0])
     assert np.array_equal(got, tc[0].reshape(-1).astype(np.uint32))
     return res
 
 
-def random_reads(n, L, p_bad, seed):
-    rng = np.random.default_rng(seed)
-    arr = ALPHA[rng.integers(0, 4, size=(n, L))]
-    if p_bad:
-        arr = np.where(rng.random((n, L)) < p_bad, ALPHA[rng.integers(4, len(ALPHA), size=(n, L))], arr).astype(np.uint8)
-    return arr
-
-
 def run(strand, n, L, k, p_bad=0.0, r_bits=14, n_waves=2, seed=1, s_bits=7, gap=0, **kw):
-    arr = random_reads(n, L, p_bad, seed)
+    arr = random_reads(np.random.default_rng(seed), n, L, p_bad)
     return check(strand, [arr[i].tobytes() for i in range(n)], arr, n, L, k, r_bits, s_bits, gap, n_waves, **kw)
 
 

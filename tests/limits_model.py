@@ -1,7 +1,6 @@
 """Inputs and models of the limit tests (tests/test_tiled_limits_gpu.py, tests/test_long_limits_gpu.py): numpy only, so that tests/test_limits_host.py can
 pin them without a GPU.
 
-  tile_array            (n, L) reads -> the tiled layout
   directed_batch        a batch of equal-length reads whose first nine are the directed ones (DIRECTED), the rest random with a few non-base bytes
   assert_directed       ... and the proof that they are there
   forward_sketch        one-strand (forward) t_Counter and F1 of equal-length reads, vectorised (tests/strand_model.py takes one ctypes call per window)
@@ -12,28 +11,12 @@ import numpy as np
 
 import orc
 import strand_model as sm
+from support import ALPHA, random_reads, tile_array  # noqa: F401  (re-exported: lm.tile_array, lm.random_reads)
 
-ALPHA = np.frombuffer(b"ACGTacgtUuNnRYKM.-*", dtype=np.uint8)
 P_BAD = 5e-4  # non-base bytes of the random reads
 N = ord("N")
 DIRECTED = ("clean", "N at 0", "N at L - 1", "N at L - k", "N at L - k - 1", "N around the last chunk's first byte", "slot byte 1 at L - 20",
             "N run of 40 across 32768", "lower case and U")
-
-
-def tile_array(arr):
-    """(n, L) uint8 array of reads -> tiled layout: tile t, chunk c, read r, 16 bytes (include/ntcard_hip.h: ntc_submit_tiled_device)"""
-    n, L = arr.shape
-    C16, ntl = (L + 15) // 16, (n + 2047) // 2048
-    a = np.full((ntl * 2048, C16 * 16), ord("A"), dtype=np.uint8)
-    a[:n, :L] = arr
-    return np.ascontiguousarray(a.reshape(ntl, 2048, C16, 16).transpose(0, 2, 1, 3)).reshape(-1)
-
-
-def random_reads(rng, n, L, p_bad=P_BAD):
-    arr = ALPHA[rng.integers(0, 4, size=(n, L))]
-    if p_bad:
-        arr = np.where(rng.random((n, L)) < p_bad, ALPHA[rng.integers(4, len(ALPHA), size=(n, L))], arr).astype(np.uint8)
-    return np.ascontiguousarray(arr)
 
 
 def run_centre(L):
@@ -43,7 +26,7 @@ def run_centre(L):
 
 def directed_batch(rng, n, L, k):
     """(n, L) reads; n >= 70: rows 0 .. 8 are DIRECTED (no other non-base byte in them); k: the window length the positions refer to"""
-    arr = random_reads(rng, n, L)
+    arr = random_reads(rng, n, L, P_BAD)
     if n < 70:
         return arr
     assert L >= 1009 and k <= 32

@@ -8,12 +8,7 @@ import numpy as np
 import hpc_model as hm
 import orc
 import strand_model as sm
-
-
-def sampled(h, s):
-    """ntComp's two patterns on uint64 values: sample 0 (h >> (63 - s)) == 1, sample 1 (h >> (64 - s)) == (1 << (s - 1)) - 1"""
-    h = np.asarray(h, dtype=np.uint64)
-    return ((h >> np.uint64(63 - s)) == np.uint64(1)) | ((h >> np.uint64(64 - s)) == np.uint64((1 << (s - 1)) - 1))
+from support import sampled
 
 
 def values(reads, spec, strand="canonical"):

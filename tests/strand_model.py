@@ -3,17 +3,15 @@ per read, every window of k bases -> fh, rh (orc_window_hash; under a mask the d
 orc_srol(orc_seed_comp(b), i), nthash.hpp:641-646), the strand's pick, ntComp (ntcard.cpp:132-145) -> t_Counter, F1.
 One ctypes call per window: keep the inputs small."""
 import ctypes as C
-import gzip
-import os
 import random
 
 import numpy as np
 
 import orc
+from support import GOLD, gap_mask, mask_with, masks_for, rseq, sketch_from_values, small_reads  # noqa: F401  (re-exported: sm.GOLD, sm.masks_for, ...)
 
 CANONICAL, FORWARD, REVERSE = 0, 1, 2
 STRANDS = {"canonical": CANONICAL, "forward": FORWARD, "reverse": REVERSE}
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def window_values(seq, mask):
@@ -62,18 +60,7 @@ def values_of(reads, masks):
 
 def sketch_of(values, strand, r_bits, s_bits):
     """ntComp over the strand's values: t_Counter [n][2][1 << r_bits] (uint16, as the engine reports it), F1 [n]"""
-    tc = np.zeros((len(values), 2, 1 << r_bits), dtype=np.uint16)
-    f1 = np.zeros(len(values), dtype=np.uint64)
-    s_mask = np.uint64((1 << (s_bits - 1)) - 1)
-    for mi, (fs, rs) in enumerate(values):
-        h = pick(fs, rs, strand)
-        f1[mi] = h.size
-        s0 = (h >> np.uint64(63 - s_bits)) == np.uint64(1)
-        s1 = (h >> np.uint64(64 - s_bits)) == s_mask
-        sample = np.where(s1, 1, np.where(s0, 0, 2))
-        keep = sample < 2
-        np.add.at(tc[mi], (sample[keep], (h[keep] & np.uint64((1 << r_bits) - 1)).astype(np.int64)), np.uint16(1))
-    return tc, f1
+    return sketch_from_values([pick(fs, rs, strand) for fs, rs in values], r_bits, s_bits)
 
 
 def model_sketch(reads, masks, strand, r_bits, s_bits):
@@ -82,48 +69,6 @@ def model_sketch(reads, masks, strand, r_bits, s_bits):
 
 def revcomp(seq):
     return seq.translate(bytes.maketrans(b"ACGTUacgtu", b"TGCAAtgcaa"))[::-1]
-
-
-def rseq(rng, n, pn=0.0, plow=0.1):
-    out = []
-    for _ in range(n):
-        r = rng.random()
-        if r < pn:
-            out.append(rng.choice("NnRY-"))
-        elif r < pn + plow:
-            out.append(rng.choice("acgtu"))
-        else:
-            out.append(rng.choice("ACGTU"))
-    return "".join(out).encode()
-
-
-def mask_with(k, zeros):
-    m = ["1"] * k
-    for i in zeros:
-        m[i] = "0"
-    return "".join(m)
-
-
-# the mask shapes the kernel distinguishes (tests/test_seeds_gpu.py: masks_for)
-def masks_for(k):
-    if k == 1:
-        return ["1"]
-    out = {"1" * k, mask_with(k, [k // 2]), "1" * (k - 1) + "0", "0" + "1" * (k - 1), ("01" * k)[:k - 1] + "1", "0" * (k - 1) + "1"}
-    if k >= 4:
-        out.add(mask_with(k, range(k // 4, k // 2)))
-        out.add(mask_with(k, list(range(0, k // 4)) + [k - 1]))
-        out.add(mask_with(k, list(range(1, 2)) + list(range(k // 2, k // 2 + 2)) + [k - 2]))
-    return sorted(out)
-
-
-def gap_mask(k, gap):
-    return "1" * ((k - gap) // 2) + "0" * gap + "1" * ((k - gap) // 2)
-
-
-def small_reads():
-    with gzip.open(os.path.join(GOLD, "reads_small.fq.gz"), "rb") as f:
-        lines = f.read().split(b"\n")
-    return [lines[i] for i in range(1, len(lines) - 1, 4)]
 
 
 # ---- the read sets and configurations of tests/test_strand_gpu.py's sketch tests (tests/test_strand_host.py asserts they tell the strands apart) ----

@@ -14,6 +14,7 @@ import pytest
 
 import orc
 from devview import DevArray
+from gpu_support import nt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,13 +22,6 @@ torch = pytest.importorskip("torch")
 
 J_SPARSE = (1, 2, 3, 4, 7)
 HOT_N = (1, 65534, 65535, 65536, 65537, 3 * 65535 + 1)
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
 
 
 def _ceil_log2(x):

@@ -8,13 +8,12 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "ntcard_amd", "bin", "ntcard")
-GOLD = os.path.join(ROOT, "tests", "golden")
+from support import GOLD, ROOT, run_cli
+from support import NTCARD as BIN  # (the name this module has always used)
 
 
 def run(args, cwd=None):
-    return subprocess.run([BIN] + args, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    return run_cli(BIN, args, cwd=cwd, timeout=600)
 
 
 def test_help_and_version_exit_zero():

@@ -2,7 +2,7 @@
 seeded inputs (bit-exact: integer/byte work), against the committed golden fixtures produced by the
 real reference, and — at sizes the oracle cannot reach quickly — through size-independent properties.
 """
-import gzip
+import functools
 import json
 import os
 import random
@@ -12,46 +12,17 @@ import numpy as np
 import pytest
 
 import orc
+import support
 from devview import DevArray as _DevArray
+from gpu_support import nt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
-
-
-def to_slots(reads, stride=None):
-    L = max((len(r) for r in reads), default=0)
-    stride = stride or max(4, (L + 3) & ~3)
-    buf = np.full(len(reads) * stride + 16, 10, dtype=np.uint8)
-    for i, r in enumerate(reads):
-        buf[i * stride: i * stride + len(r)] = np.frombuffer(r, dtype=np.uint8)
-    return buf, stride
-
-
-def rseq(rng, n, pn=0.02, plow=0.1, bad="NnRYKMSWBDHV-.*Xx\r"):
-    out = []
-    for _ in range(n):
-        r = rng.random()
-        if r < pn:
-            out.append(rng.choice(bad))
-        elif r < pn + plow:
-            out.append(rng.choice("acgtu"))
-        else:
-            out.append(rng.choice("ACGTU"))
-    return "".join(out).encode()
-
-
-def small_reads(golden_dir):
-    with gzip.open(os.path.join(golden_dir, "reads_small.fq.gz"), "rb") as f:
-        lines = f.read().split(b"\n")
-    return [lines[i] for i in range(1, len(lines) - 1, 4)]
+rseq = functools.partial(support.rseq, pn=0.02, bad="NnRYKMSWBDHV-.*Xx\r")  # this module's defaults: more non-base letters, and more of them
+to_slots = functools.partial(support.to_slots, fill=10)  # a line feed behind every read
 
 
 # ------------------------------------------------------------------------------------------------
@@ -73,8 +44,8 @@ def test_hash_dump_matches_oracle(nt, L):
     reads[0] = b"N" * L
     reads[1] = (b"ACGT" * 100)[:L]
     reads[2] = (b"acgu" * 100)[:L]
-    buf, stride = to_slots(reads)
-    d = torch.from_numpy(buf).cuda()
+    stride = max(4, (L + 3) & ~3)
+    d = torch.from_numpy(to_slots(reads, stride)).cuda()
     for k in (1, 2, 3, 4, 5, 12, 20, 31, 32, 33, 34, 35, 64, 70, 96, 128, 200):
         maxw = max(L - k + 1, 1)
         dh = torch.zeros(len(reads) * maxw, dtype=torch.int64, device="cuda")
@@ -101,7 +72,8 @@ def test_golden_hash_vectors_through_production_kernel(nt, golden_dir):
 
     def dump(seq, k, gap, k1):
         L = len(seq)
-        buf, stride = to_slots([seq], stride=max(4, (L + 3) & ~3))
+        stride = max(4, (L + 3) & ~3)
+        buf = to_slots([seq], stride)
         buf[buf == 10] = ord("A")
         d = torch.from_numpy(buf).cuda()
         maxw = max(L - k + 1, 1)
@@ -125,7 +97,8 @@ def test_golden_hash_vectors_through_production_kernel(nt, golden_dir):
 
 def test_known_answer_on_device(nt):
     # vendor/ntHash/unittest/UnitTests.cpp:39,45 — the reference's own invariant value
-    buf, stride = to_slots([b"ACGTACACTGGACTGAGTCT"])
+    stride = 20
+    buf = to_slots([b"ACGTACACTGGACTGAGTCT"], stride)
     d = torch.from_numpy(buf).cuda()
     dh = torch.zeros(1, dtype=torch.int64, device="cuda")
     dc = torch.zeros(1, dtype=torch.int32, device="cuda")
@@ -241,7 +214,7 @@ def test_deferred_pass_over_several_buffers(nt):
 
     def batch(n, L, stride, pn):
         reads = [rseq(rng, L, pn=pn, plow=0.05) for _ in range(n)]
-        buf, _ = to_slots(reads, stride=stride)
+        buf = to_slots(reads, stride)
         buf[buf == 10] = ord("A")
         return reads, torch.from_numpy(buf).cuda()
     dropped = batch(2048 * 2 + 5, 150, 152, 0.01)
@@ -267,7 +240,7 @@ def test_submit_device_buffer_may_be_reused_in_stream_order(nt):
     keep the buffer."""
     rng = random.Random(7)
     reads = [rseq(rng, 150, pn=0.01, plow=0.05) for _ in range(2048 * 2 + 333)]
-    buf, _ = to_slots(reads, stride=152)
+    buf = to_slots(reads, 152)
     buf[buf == 10] = ord("A")
     oc, of1 = orc.sketch_reads(reads, [32], 0, 20, 7)
     for flags in (nt.FLAG_ALWAYS_LOG, 0):
@@ -350,7 +323,7 @@ def test_equal_length_row_slots_match_oracle(nt, L, stride, s_bits, pn):
     reads[5] = b"N" * L
     reads[2048 + 9] = (b"acgu" * 64)[:L]
     reads[4096] = (b"ACGT" * 64)[:L - 1] + b"n"
-    buf, _ = to_slots(reads, stride=stride)
+    buf = to_slots(reads, stride)
     buf[buf == 10] = ord("A")  # padding bytes are base letters (ntc_submit_device's contract for the fast path)
     d = torch.from_numpy(buf).cuda()
     with nt.Engine([32], r_bits=20, s_bits=s_bits, flags=nt.FLAG_ALWAYS_LOG) as e:
@@ -380,7 +353,7 @@ def test_log_and_adaptive_modes_agree_at_size(nt):
 
 def test_golden_hist_from_reference(nt, golden_dir, tmp_path):
     """the reference CLI's own .hist outputs (default rBits = 27) reproduced byte for byte"""
-    reads = small_reads(golden_dir)
+    reads = support.small_reads()
     cases = [("ref_k12__out_k12.hist", [12], 27, 7, 1000), ("ref_k32__out_k32.hist", [32], 27, 7, 1000),
              ("ref_k20_c50__out_k20.hist", [20], 27, 7, 50), ("ref_k24_s11_r22__out_k24.hist", [24], 22, 7, 1000)]
     for name, klist, rb, sb, cov in cases:
@@ -402,7 +375,7 @@ def test_golden_hist_from_reference(nt, golden_dir, tmp_path):
 
 
 def test_golden_sketch_digests(nt, golden_dir):
-    reads = small_reads(golden_dir)
+    reads = support.small_reads()
     with open(os.path.join(golden_dir, "sketch_goldens.json")) as f:
         gold = json.load(f)
     for ent in gold:
@@ -453,7 +426,7 @@ def test_equal_length_batches_match_oracle(nt, L, k, gap):
 
 def test_golden_gap_hist_from_reference(nt, golden_dir, tmp_path):
     """the reference CLI's `-k 12 -g 2` output (the shape of its own check-dna-gap target, Makefile.am:53-54,71-72)"""
-    reads = small_reads(golden_dir)
+    reads = support.small_reads()
     with nt.Engine([12], gap=2, r_bits=27, s_bits=7) as e:
         e.submit_reads(reads)
         _, ph, f1 = e.finish()
@@ -954,7 +927,8 @@ def test_every_timer_runs_and_reset_zeroes_it(nt):
         assert e.hpc_time() > 0.0
         e.reset()
         assert e.hpc_time() == 0.0 and e.kernel_time() == (0.0, 0) and e.long_time() == (0.0, 0.0)
-    slots, stride = to_slots(reads[:130], stride=152)
+    stride = 152
+    slots = to_slots(reads[:130], stride)
     slots[slots == 10] = ord("A")
     d_slots = torch.from_numpy(slots).cuda()
     with nt.Engine([32], r_bits=20, s_bits=7, signature=True) as e:

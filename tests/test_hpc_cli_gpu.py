@@ -1,20 +1,15 @@
 """`ntcard --hpc` and `nthll --hpc` (include/ntcard_hip.h: NTC_FLAG_HPC): a run with the option over raw files gives byte for byte what a run without it
 gives over the same records compressed beforehand by the pure-Python model (tests/hpc_model.py)."""
-import os
 import random
-import subprocess
 
 import pytest
 
 import hpc_model as hm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTCARD = os.path.join(ROOT, "ntcard_amd", "bin", "ntcard")
-NTHLL = os.path.join(ROOT, "ntcard_amd", "bin", "nthll")
+from support import NTCARD, NTHLL, run_cli
 
 
 def run(cmd, cwd):
-    return subprocess.run(cmd, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    return run_cli(cmd[0], cmd[1:], cwd=cwd, timeout=600)
 
 
 @pytest.mark.parametrize("binary", [NTCARD, NTHLL])

@@ -14,6 +14,8 @@ import pytest
 import hpc_model as hm
 import orc
 import strand_model as sm
+from gpu_support import nt, on_device, planned  # noqa: F401
+from support import same_sketch
 
 pytestmark = pytest.mark.gpu
 
@@ -22,13 +24,6 @@ torch = pytest.importorskip("torch")
 R, S_BITS = 14, 7
 K, PL = 32, 48
 MASK = "1111111101111111100111111"
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
 
 
 def seqs():
@@ -42,12 +37,9 @@ def comp():
 
 
 @functools.lru_cache(maxsize=None)
-def on_device(lead=3, raw=False):
-    """the sequences (raw: hpc_model.device_set, the bytes 1 and 3 included) behind one another in one device buffer, `lead` bytes in front ->
-    (tensor, host offsets)"""
-    s = hm.device_set() if raw else seqs()
-    host = np.frombuffer(b"#" * lead + b"".join(s) + b"#", dtype=np.uint8).copy()
-    return torch.from_numpy(host).cuda(), hm.offsets_of(s, lead)
+def device_input(lead=3, raw=False):
+    """the sequences (raw: hpc_model.device_set, the bytes 1 and 3 included) on the device, uploaded once per lead -> (tensor, host offsets)"""
+    return on_device(hm.device_set() if raw else seqs(), lead=lead)
 
 
 @functools.lru_cache(maxsize=None)
@@ -69,27 +61,22 @@ def totals():
     return sum(len(s) for s in seqs()), sum(len(c) for c in comp())
 
 
-def planned(nt, kmax, pl):
-    m = [nt.long_plan(kmax, pl, len(c))[0] for c in comp()]
-    return sum(m), sum(1 for x in m if x)
+def planned_comp(nt, kmax, pl):
+    return planned(nt, map(len, comp()), kmax, pl)
 
 
 def count_device(e, piece_len=PL, lead=3):
-    d, offs = on_device(lead)
+    d, offs = device_input(lead)
     e.submit_long_device(d.data_ptr(), offs, piece_len)
     tc, _, f1 = e.finish(counters=True)
     return tc, f1
-
-
-def same(got, want):
-    return np.array_equal(got[1], want[1]) and np.array_equal(got[0], want[0])
 
 
 # ---- the compaction itself ----
 @pytest.mark.parametrize("lead", [0, 1, 2, 3])
 @pytest.mark.parametrize("out_lead", [0, 1, 2, 3])
 def test_compress_device_matches_the_model(nt, lead, out_lead):
-    d, offs = on_device(lead, raw=True)
+    d, offs = device_input(lead, raw=True)
     raw, want_seqs = hm.device_set(), hm.model(hm.device_set())
     assert any(1 in s and 3 in s for s in raw)
     total_in, total_out = totals()
@@ -105,7 +92,7 @@ def test_compress_device_matches_the_model(nt, lead, out_lead):
 
 def test_compress_device_subrange_and_empty(nt):
     """a call may start in the middle of a buffer (offsets[0] != 0) and may hold nothing"""
-    d, offs = on_device(2, raw=True)
+    d, offs = device_input(2, raw=True)
     out = torch.zeros(400_000, dtype=torch.uint8, device="cuda")
     new = nt.hpc_compress_device(d.data_ptr(), offs[5:20], out.data_ptr())
     c = hm.model(hm.device_set())[5:19]
@@ -117,11 +104,10 @@ def test_compress_device_subrange_and_empty(nt):
 def compress_on_device(nt, buf, offs, lead=3, out_lead=0):
     """the sequences [offs[i], offs[i + 1]) of buf through ntc_hpc_compress_device, `lead` bytes behind an aligned address: offsets and bytes against
     the model, nothing written outside the result -> the chunks of the compaction"""
-    host = np.concatenate([np.full(lead, 0x23, dtype=np.uint8), buf, np.full(1, 0x23, dtype=np.uint8)])
-    d = torch.from_numpy(host).cuda()
-    assert d.data_ptr() % 4 == 0 and int(offs[0]) == 0  # (the source's phase in its dword is `lead`)
+    d, d_offs = on_device(buf, offs, lead)  # (at an address that is a multiple of 4: the source's phase in its dword is `lead`)
+    assert int(offs[0]) == 0
     out = torch.full((buf.size + 8,), 0x23, dtype=torch.uint8, device="cuda")
-    new = nt.hpc_compress_device(d.data_ptr(), offs + np.uint64(lead), out.data_ptr() + out_lead)
+    new = nt.hpc_compress_device(d.data_ptr(), d_offs, out.data_ptr() + out_lead)
     want, want_offs = hm.compress_many(buf, offs)
     assert 0 < want.size < buf.size
     assert np.array_equal(new, want_offs)
@@ -177,9 +163,9 @@ def test_engine_counts_many_short_sequences(nt):
     oc = np.zeros((1, 2, 1 << R), dtype=np.uint16)
     of1 = orc.sketch_update(oc, want, want_offs, [12], 0, R, S_BITS)
     assert int(of1[0]) > 0
-    d = torch.from_numpy(np.concatenate([np.full(3, 0x23, dtype=np.uint8), buf, np.full(1, 0x23, dtype=np.uint8)])).cuda()
+    d, d_offs = on_device(buf, offs)
     with nt.Engine([12], r_bits=R, s_bits=S_BITS, hpc=True) as e:
-        e.submit_long_device(d.data_ptr(), offs + np.uint64(3))
+        e.submit_long_device(d.data_ptr(), d_offs)
         tc, _, f1 = e.finish(counters=True)
         assert e.hpc_stats() == (buf.size, want.size) and e.long_stats() == (0, 0)
     assert np.array_equal(f1, of1), (f1, of1)
@@ -190,9 +176,9 @@ def test_engine_counts_many_short_sequences(nt):
 def test_k32(nt):
     with nt.Engine([K], r_bits=R, s_bits=S_BITS, hpc=True) as e:
         got = count_device(e)
-        assert same(got, oracle()), (got[1], oracle()[1])
+        assert same_sketch(got, oracle()), (got[1], oracle()[1])
         assert e.hpc_stats() == totals()
-        assert e.long_stats() == planned(nt, K, PL) and e.long_stats()[0] > 2048
+        assert e.long_stats() == planned_comp(nt, K, PL) and e.long_stats()[0] > 2048
     assert not np.array_equal(oracle()[1], oracle_raw()[1])  # (the inputs tell the flag from its absence)
 
 
@@ -202,33 +188,32 @@ def test_table_slot_bytes_inside_the_pieces(nt):
     raw = hm.slot_piece_set(K, PL)
     c = hm.model(raw)
     assert all(1 in s or 3 in s for s in c)
-    host = np.frombuffer(b"#" + b"".join(raw) + b"#", dtype=np.uint8).copy()
-    d = torch.from_numpy(host).cuda()
+    d, offs = on_device(raw, lead=1)
     with nt.Engine([K], r_bits=R, s_bits=S_BITS, hpc=True, flags=nt.FLAG_REQUIRE_TILED) as e:
-        e.submit_long_device(d.data_ptr(), hm.offsets_of(raw, 1), PL)
+        e.submit_long_device(d.data_ptr(), offs, PL)
         tc, _, f1 = e.finish(counters=True)
         assert e.long_stats()[1] == len(raw)
-    assert same((tc, f1), orc.sketch_reads(c, [K], 0, R, S_BITS))
+    assert same_sketch((tc, f1), orc.sketch_reads(c, [K], 0, R, S_BITS))
 
 
 def test_k_list_on_one_cut(nt):
     kl = (21, 25, 31)
     with nt.Engine(list(kl), r_bits=R, s_bits=S_BITS, hpc=True, flags=nt.FLAG_REQUIRE_TILED) as e:
-        assert same(count_device(e), oracle(kl))
-        assert e.hpc_stats() == totals() and e.long_stats() == planned(nt, 31, PL)
+        assert same_sketch(count_device(e), oracle(kl))
+        assert e.hpc_stats() == totals() and e.long_stats() == planned_comp(nt, 31, PL)
 
 
 @pytest.mark.parametrize("k,gap,pl", [(12, 2, 32), (32, 8, 64)])
 def test_tiled_gap_seeds(nt, k, gap, pl):
     with nt.Engine([k], gap=gap, r_bits=R, s_bits=S_BITS, hpc=True, flags=nt.FLAG_REQUIRE_TILED) as e:
-        assert same(count_device(e, pl), oracle((k,), gap))
-        assert e.hpc_stats() == totals() and e.long_stats() == planned(nt, k, pl)
+        assert same_sketch(count_device(e, pl), oracle((k,), gap))
+        assert e.hpc_stats() == totals() and e.long_stats() == planned_comp(nt, k, pl)
 
 
 def test_forward_strand_on_the_tiled_kernels(nt):
     with nt.Engine([K], r_bits=R, s_bits=S_BITS, hpc=True, strand="forward", strand_tiled=True, flags=nt.FLAG_REQUIRE_TILED) as e:
-        assert same(count_device(e), model_sketch("1" * K, sm.FORWARD))
-        assert e.hpc_stats() == totals() and e.long_stats() == planned(nt, K, PL)
+        assert same_sketch(count_device(e), model_sketch("1" * K, sm.FORWARD))
+        assert e.hpc_stats() == totals() and e.long_stats() == planned_comp(nt, K, PL)
 
 
 # ---- engines that do not ----
@@ -252,7 +237,7 @@ def test_engines_that_do_not_qualify(nt, name):
         dev = count_device(e, 0)
         assert e.long_stats() == (0, 0) and e.hpc_stats() == totals()
     assert int(want()[1].sum()) > 0
-    assert same(dev, host) and same(dev, want())
+    assert same_sketch(dev, host) and same_sketch(dev, want())
 
 
 # ---- the host path ----
@@ -273,7 +258,7 @@ def test_host_submits(nt, monkeypatch, long_min):
             else:
                 e.submit_reads(s)
             tc, _, f1 = e.finish(counters=True)
-            assert same((tc, f1), oracle()), spans
+            assert same_sketch((tc, f1), oracle()), spans
             assert e.hpc_stats() == totals()
             if long_min is not None:  # the compressed sequences of two or more default pieces are cut on the device
                 assert e.long_stats()[1] == sum(1 for c in comp() if nt.long_plan(K, 1008, len(c))[0] >= 2) > 0
@@ -283,21 +268,21 @@ def test_one_sequence_per_round(nt, monkeypatch):
     monkeypatch.setenv("NTC_HPC_ROUND_BYTES", "1")
     monkeypatch.setenv("NTC_LONG_ROUND_BYTES", "1")
     with nt.Engine([K], r_bits=R, s_bits=S_BITS, hpc=True) as e:
-        assert same(count_device(e), oracle())
-        assert e.hpc_stats() == totals() and e.long_stats() == planned(nt, K, PL)
+        assert same_sketch(count_device(e), oracle())
+        assert e.hpc_stats() == totals() and e.long_stats() == planned_comp(nt, K, PL)
 
 
 def test_rounds_of_several_sequences(nt, monkeypatch):
     """a budget that ends rounds between the short sequences and leaves the long ones rounds of their own (the scratch grows to them)"""
     monkeypatch.setenv("NTC_HPC_ROUND_BYTES", "1000")
     with nt.Engine([K], r_bits=R, s_bits=S_BITS, hpc=True) as e:
-        assert same(count_device(e), oracle())
-        assert e.hpc_stats() == totals() and e.long_stats() == planned(nt, K, PL)
+        assert same_sketch(count_device(e), oracle())
+        assert e.hpc_stats() == totals() and e.long_stats() == planned_comp(nt, K, PL)
 
 
 def test_nthll(nt):
     with nt.HllEngine(K, hpc=True) as e:
-        d, offs = on_device(3)
+        d, offs = device_input(3)
         e.submit_long_device(d.data_ptr(), offs)
         regs, f1 = e.finish()
         assert e.hpc_stats() == totals()
@@ -315,13 +300,13 @@ def test_nthll(nt):
 
 
 def test_source_may_change_behind_the_call_on_a_deferring_engine(nt):
-    d0, offs = on_device(3)
+    d0, offs = device_input(3)
     d = d0.clone()
     with nt.Engine([K], r_bits=R, s_bits=S_BITS, hpc=True, flags=nt.FLAG_DEFER_REDO) as e:
         e.submit_long_device(d.data_ptr(), offs, PL)
         d.fill_(ord("N"))  # same stream, behind the call: the engine counts from its own scratch
         tc, _, f1 = e.finish(counters=True)
-    assert same((tc, f1), oracle())
+    assert same_sketch((tc, f1), oracle())
 
 
 def test_fixed_layout_batches_are_refused(nt):
@@ -338,7 +323,7 @@ def test_fixed_layout_batches_are_refused(nt):
 
 
 def test_reset_zeroes_the_stats_and_submits_accumulate(nt):
-    d, offs = on_device(3)
+    d, offs = device_input(3)
     t_in, t_out = totals()
     oc, of1 = oracle()
     with nt.Engine([K], r_bits=R, s_bits=S_BITS, hpc=True) as e:
@@ -366,10 +351,10 @@ def test_merge_refuses_engines_that_differ_in_the_flag(nt):
         b.submit_reads(list(seqs()[30:]))
         nt.merge_devices([a, b])
         tc, _, f1 = a.finish(counters=True)
-    assert same((tc, f1), oracle())
+    assert same_sketch((tc, f1), oracle())
 
 
 def test_an_engine_without_the_flag_is_unchanged(nt):
     with nt.Engine([K], r_bits=R, s_bits=S_BITS) as e:
-        assert same(count_device(e), oracle_raw())
+        assert same_sketch(count_device(e), oracle_raw())
         assert e.hpc_stats() == (0, 0) and e.hpc_time() == 0.0

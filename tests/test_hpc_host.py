@@ -10,8 +10,9 @@ import pytest
 import hpc_model as hm
 import ntcard_amd as nt
 from ntcard_amd import _abi
+from support import abi_config, created, hll_create_ex
 
-ERR_ARG, ERR_DEVICE = -1, -2
+ERR_ARG = -1
 HPC, FWD, REV, STRAND_TILED = 8192, 512, 1024, 4096
 NEW_SYMBOLS = ["ntc_hpc_compress", "ntc_hpc_compress_device", "ntc_hpc_stats", "ntc_hpc_time"]
 
@@ -135,31 +136,11 @@ def test_compress_argument_errors():
 
 
 # ---- the flag ----
-def cfg(flags, k=(32,)):
-    arr = (C.c_uint32 * len(k))(*k)
-    c = _abi.NtcConfig(n_k=len(k), k=C.cast(arr, C.POINTER(C.c_uint32)), gap=0, r_bits=14, s_bits=7, device=0, flags=flags)
-    c._keep = arr
-    return c
-
-
-def no_gpu():
-    import torch
-    return not torch.cuda.is_available()
-
-
-def created(rc, h, L):
-    """the call got past its argument checks: on a machine without a GPU it fails at the device probe, with one it makes an engine"""
-    if h:
-        L.ntc_destroy(h)
-    assert rc == (ERR_DEVICE if no_gpu() else 0), (rc, L.ntc_last_error())
-    return True
-
-
 @pytest.mark.parametrize("beside", [0, 1, 2, 8, 16, 32, 64, 128, FWD, REV, FWD | STRAND_TILED])
 def test_create_takes_the_flag_beside_every_other(beside):
     L = _abi.lib()
     h = C.c_void_p()
-    assert created(L.ntc_create(C.byref(cfg(HPC | beside)), C.byref(h)), h, L)
+    assert created(L.ntc_create(C.byref(abi_config(flags=HPC | beside)), C.byref(h)), h, L)
 
 
 def test_create_seeded_takes_the_flag():
@@ -174,19 +155,13 @@ def test_the_retired_bits_stay_refused_beside_the_flag():
     L = _abi.lib()
     h = C.c_void_p()
     for bit in (4, 256, 2048, 1 << 20):
-        assert L.ntc_create(C.byref(cfg(HPC | bit)), C.byref(h)) == ERR_ARG and b"unknown flag" in L.ntc_last_error()
-    assert L.ntc_create(C.byref(cfg(HPC | FWD | REV)), C.byref(h)) == ERR_ARG
-    assert L.ntc_create(C.byref(cfg(HPC | STRAND_TILED)), C.byref(h)) == ERR_ARG
+        assert L.ntc_create(C.byref(abi_config(flags=HPC | bit)), C.byref(h)) == ERR_ARG and b"unknown flag" in L.ntc_last_error()
+    assert L.ntc_create(C.byref(abi_config(flags=HPC | FWD | REV)), C.byref(h)) == ERR_ARG
+    assert L.ntc_create(C.byref(abi_config(flags=HPC | STRAND_TILED)), C.byref(h)) == ERR_ARG
 
 
 def hll_create(flags):
-    L = _abi.lib()
-    k = (C.c_uint32 * 1)(32)
-    c = _abi.NtcHllConfig()
-    c.n_k, c.k, c.n_bits, c.device, c.flags = 1, C.cast(k, C.POINTER(C.c_uint32)), 12, 0, flags
-    h = C.c_void_p()
-    rc = L.ntc_hll_create_ex(C.byref(c), C.byref(h))
-    return rc, h, L
+    return hll_create_ex(k=[32], n_bits=12, flags=flags)
 
 
 @pytest.mark.parametrize("flags", [HPC, HPC | FWD, HPC | REV])

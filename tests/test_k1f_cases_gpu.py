@@ -14,19 +14,14 @@ import pytest
 
 import k1f_cases as kc
 import orc
+from gpu_support import nt, on_device  # noqa: F401
+from support import assert_same_sketch
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 R_BITS = 14
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
 
 
 FAMILIES = {}
@@ -83,12 +78,7 @@ def run(nt, name, flags=0, unused=ord("A"), log_entries=0):
         return e.finish(counters=True)
 
 
-def check(got, want, what):
-    (tc, ph, f1), (oc, of1) = got, want
-    assert np.array_equal(f1, of1), (what, f1, of1)
-    assert np.array_equal(tc, oc), (what, int((tc != oc).sum()))
-    for ki in range(oc.shape[0]):
-        assert np.array_equal(ph[ki], orc.value_hist(oc[ki], R_BITS)), what
+check = functools.partial(assert_same_sketch, hist_r_bits=R_BITS)  # F1, every counter and the value histogram
 
 
 @pytest.mark.parametrize("name", list(FAMILIES))
@@ -152,11 +142,9 @@ def long_oracle(kl):
     return orc.sketch_reads([kc.trimmed(kl)], list(kl), 0, R_BITS, 7)
 
 
-def count_long(nt, kl, klist):
+def count_trimmed(nt, kl, klist):
     seq = kc.trimmed(kl)
-    lead = 3
-    d = torch.from_numpy(np.frombuffer(b"#" * lead + seq + b"#", dtype=np.uint8).copy()).cuda()
-    offs = np.array([lead, lead + len(seq)], dtype=np.uint64)
+    d, offs = on_device([seq])
     with nt.Engine(list(klist), r_bits=R_BITS, s_bits=7, flags=nt.FLAG_REQUIRE_TILED) as e:
         e.submit_long_device(d.data_ptr(), offs, kc.TRIMMED_PIECE)
         got = e.finish(counters=True)
@@ -170,7 +158,7 @@ def count_long(nt, kl, klist):
 def test_trimmed_pieces_under_a_k_list(nt, monkeypatch, kl, env):
     if env:
         monkeypatch.setenv(*env)
-    check(count_long(nt, kl, kl), long_oracle(kl), (kl, env))
+    check(count_trimmed(nt, kl, kl), long_oracle(kl), (kl, env))
 
 
 @pytest.mark.parametrize("kl", kc.TRIMMED_LISTS, ids=str)
@@ -178,4 +166,4 @@ def test_trimmed_inputs_under_the_largest_k_alone(nt, kl):
     """the single-k engines [32] and [27] on the same buffers (the same cut, no trimming)"""
     oc, of1 = long_oracle(kl)
     ki = list(kl).index(max(kl))
-    check(count_long(nt, kl, (max(kl),)), (oc[ki:ki + 1], of1[ki:ki + 1]), kl)
+    check(count_trimmed(nt, kl, (max(kl),)), (oc[ki:ki + 1], of1[ki:ki + 1]), kl)

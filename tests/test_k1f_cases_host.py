@@ -14,6 +14,7 @@ import pytest
 import k1f_cases as kc
 import k1h_model as km
 import orc
+from support import sampled
 
 R_BITS = 14
 SUS_CAP = 4096  # no family may overflow the suspect list at the engine's sizing (2048 + per wave at least)
@@ -59,7 +60,7 @@ def suspects_of(case, res, planted):
             continue
         reach = sum(1 << j for j in range(3) if w // 16 + j < Cn and 16 * j < w % 16 + case.k)
         ok, fv, rv = km.window_hashes(case.reads[r][w:w + case.k], case.k, case.gap)
-        counts = bool(ok) and kc.key_of(min(fv, rv), case.s_bits) is not None
+        counts = bool(ok) and bool(sampled(min(fv, rv), case.s_bits))
         out.append((r, w, at[(r, w)], int(mark), (int(mark) >> 4) & reach, bool(ok), counts))
     return out
 
@@ -187,7 +188,7 @@ def test_dense_suspects_fill_a_hit_log_region():
     for x, t, rw, mark in res["sus"]:
         r, w = int(t) * 2048 + (int(rw) & 2047), int(rw) >> 11
         ok, fv, rv = km.window_hashes(case.reads[r][w:w + k], k, 0)
-        if ok and kc.key_of(min(fv, rv), 7) is not None:
+        if ok and sampled(min(fv, rv), 7):
             blocks[(int(t), (w + k - 1 - phi) // 16 + 1)] += 1
     print("dense: counting suspects per (tile, block)", dict(blocks), "suspects in all", len(res["sus"]))
     assert max(blocks.values()) > 4 * 256 + 64

@@ -8,22 +8,11 @@ import pytest
 
 import k1h_model as km
 import orc
-
-
-def tile_array(arr):
-    n, L = arr.shape
-    C16, ntl = (L + 15) // 16, (n + 2047) // 2048
-    a = np.full((ntl * 2048, C16 * 16), ord("A"), dtype=np.uint8)
-    a[:n, :L] = arr
-    return np.ascontiguousarray(a.reshape(ntl, 2048, C16, 16).transpose(0, 2, 1, 3)).reshape(-1)
+from support import ALPHA, random_reads, tile_array
 
 
 def run(n, L, k, p_bad=0.0, r_bits=14, n_waves=2, seed=1, s_bits=7, gap=0, **kw):
-    rng = np.random.default_rng(seed)
-    alpha = np.frombuffer(b"ACGTacgtUuNnRYKM.-*", dtype=np.uint8)
-    arr = alpha[rng.integers(0, 4, size=(n, L))]
-    if p_bad:
-        arr = np.where(rng.random((n, L)) < p_bad, alpha[rng.integers(4, len(alpha), size=(n, L))], arr).astype(np.uint8)
+    arr = random_reads(np.random.default_rng(seed), n, L, p_bad)
     res = km.run_k1h(tile_array(arr), n, L, k, r_bits=r_bits, n_waves=n_waves, s_bits=s_bits, gap=gap, **kw)
     reads = [arr[i].tobytes() for i in range(n)]
     fk, f1_sub = km.k1f_model(reads, L, k, r_bits, s_bits, res["dirty"], res["tie"], res["sus"], res["sus_overflow"], gap=gap)
@@ -38,7 +27,6 @@ def run_ragged(n, C, k, p_bad=0.0, r_bits=14, n_waves=2, seed=1, s_bits=7, gap=0
     """a ragged batch: reads of 16 C - 15 .. 16 C bases (or lo .. 16 C), every tile sorted longest first, tails[tile][d] = its reads with more than d
     bases in their last 16-base piece"""
     rng = np.random.default_rng(seed)
-    alpha = np.frombuffer(b"ACGTacgtUuNnRYKM.-*", dtype=np.uint8)
     lens = rng.integers(max(lo or 16 * C - 15, 16 * C - 15), 16 * C + 1, size=n)
     ntl = (n + 2047) // 2048
     reads, tails = [], np.zeros((ntl, 16), dtype=np.uint32)
@@ -48,9 +36,9 @@ def run_ragged(n, C, k, p_bad=0.0, r_bits=14, n_waves=2, seed=1, s_bits=7, gap=0
         for d in range(16):
             tails[t, d] = int(np.count_nonzero(ls - 16 * (C - 1) > d))
         for j, ln in enumerate(ls):
-            row = alpha[rng.integers(0, 4, size=ln)]
+            row = ALPHA[rng.integers(0, 4, size=ln)]
             if p_bad:
-                row = np.where(rng.random(ln) < p_bad, alpha[rng.integers(4, len(alpha), size=ln)], row).astype(np.uint8)
+                row = np.where(rng.random(ln) < p_bad, ALPHA[rng.integers(4, len(ALPHA), size=ln)], row).astype(np.uint8)
             arr[t * 2048 + j, :ln] = row
             reads.append(row.tobytes())
     res = km.run_k1h(tile_array(arr), n, 16 * C, k, r_bits=r_bits, n_waves=n_waves, s_bits=s_bits, gap=gap, tails=tails, **kw)

@@ -10,6 +10,7 @@ import pytest
 import k1h_strand_model as ksm
 import strand_model as sm
 from ntcard_amd import _abi
+from support import abi_config
 
 gen_k1h = ksm.gen_k1h
 BOTH = pytest.mark.parametrize("strand", [sm.FORWARD, sm.REVERSE], ids=["forward", "reverse"])
@@ -103,15 +104,6 @@ def test_strand_variants_budgets():
 
 
 # ---- ABI: NTC_FLAG_STRAND_TILED is valid only beside exactly one strand flag; checked before a device is looked for ----
-def cfg(k=(32,), flags=0):
-    c = _abi.NtcConfig(r_bits=20, s_bits=7, device=0, gap=0, flags=flags)
-    arr = (C.c_uint32 * len(k))(*k)
-    c.n_k = len(k)
-    c.k = C.cast(arr, C.POINTER(C.c_uint32))
-    c._arr = arr
-    return c
-
-
 def test_header_library_and_package_carry_the_flag():
     import os
     import ntcard_amd as nt
@@ -131,7 +123,7 @@ def test_strand_tiled_needs_exactly_one_strand_flag(flags, seeded):
         arr = (C.c_char_p * 1)(b"1" * 32)
         rc = L.ntc_create_seeded(C.byref(c), 1, arr, C.byref(h))
     else:
-        rc = L.ntc_create(C.byref(cfg(flags=flags)), C.byref(h))
+        rc = L.ntc_create(C.byref(abi_config(r_bits=20, flags=flags)), C.byref(h))
     assert rc == ERR_ARG and not h.value
     assert b"device" not in L.ntc_last_error() and b"STRAND" in L.ntc_last_error()
 

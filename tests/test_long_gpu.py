@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 import orc
+from gpu_support import count_long, nt, on_device, planned  # noqa: F401
+from support import rseq_acgt
 
 pytestmark = pytest.mark.gpu
 
@@ -18,31 +20,11 @@ K, PL = 32, 48  # piece_len 48 at k = 32: S = 17 window starts per piece
 STEP = PL - K + 1
 
 
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
-
-
-def rseq(rng, n):
-    return bytes(rng.choice(b"ACGT") for _ in range(n))
-
-
-def on_device(seqs, lead=3):
-    """the sequences behind one another in one device buffer, `lead` bytes in front (start offsets of any alignment) -> (tensor, host offsets)"""
-    offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
-    offs[0] = lead
-    offs[1:] = lead + np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    host = np.frombuffer(b"#" * lead + b"".join(seqs) + b"#", dtype=np.uint8).copy()
-    return torch.from_numpy(host).cuda(), offs
-
-
 @functools.lru_cache(maxsize=None)
 def one_long():
     """one sequence of more than 2048 pieces (the cut crosses a tile boundary) whose remainder has windows"""
     rng = random.Random(7)
-    return (rseq(rng, PL + STEP * 2100 + 20),)
+    return (rseq_acgt(rng, PL + STEP * 2100 + 20),)
 
 
 @functools.lru_cache(maxsize=None)
@@ -51,7 +33,7 @@ def mixed():
     rng = random.Random(11)
     lens = [0, K - 1, K, PL - 1, PL, PL + STEP - 1, PL + STEP, 5 * STEP + K - 1,  # (the last: m = 5 and a remainder of exactly k - 1 bytes — no window)
             3001, 5003, 7777, 2222] + [rng.randrange(1, 400) for _ in range(28)]
-    seqs = [bytearray(rseq(rng, n)) for n in lens]
+    seqs = [bytearray(rseq_acgt(rng, n)) for n in lens]
     assert 5 * STEP + K - 1 >= PL and (5 * STEP + K - 1 - PL) // STEP + 1 == 5
     big = seqs[8]
     big[100] = ord("N")
@@ -77,25 +59,12 @@ def oracle(which, k=K, gap=0):
     return orc.sketch_reads(list(seqs), [k], gap, R, S_BITS)
 
 
-def planned(nt, seqs, k, pl):
-    m = [nt.long_plan(k, pl, len(s))[0] for s in seqs]
-    return sum(m), sum(1 for x in m if x)
-
-
-def count_long(nt, seqs, k=K, gap=0, piece_len=PL, flags=0):
-    d, offs = on_device(seqs)
-    with nt.Engine([k], gap=gap, r_bits=R, s_bits=S_BITS, flags=flags) as e:
-        e.submit_long_device(d.data_ptr(), offs, piece_len)
-        tc, _, f1 = e.finish(counters=True)
-        return tc, f1, e.long_stats()
-
-
 def test_one_sequence_across_a_tile_boundary(nt):
     """48 + 17 * 2100 + 20 bases at piece_len 48, k = 32.  ntc_long_plan's m = floor((n - L) / S) + 1 gives 2102 full pieces for this length (the 20 bases
     behind piece 2100 hold one more step of 17) and a remainder of 34 bytes = 3 windows; the stats are checked against the plan."""
     seqs = one_long()
-    assert planned(nt, seqs, K, PL) == (2102, 1) and len(seqs[0]) - 2102 * STEP >= K
-    tc, f1, stats = count_long(nt, seqs)
+    assert planned(nt, map(len, seqs), K, PL) == (2102, 1) and len(seqs[0]) - 2102 * STEP >= K
+    tc, f1, stats = count_long(nt, *on_device(seqs), [K], PL)
     oc, of1 = oracle("one")
     assert np.array_equal(f1, of1) and np.array_equal(tc, oc)
     assert stats == (2102, 1)
@@ -103,30 +72,30 @@ def test_one_sequence_across_a_tile_boundary(nt):
 
 def test_many_sequences_every_boundary_length(nt):
     seqs = mixed()
-    tc, f1, stats = count_long(nt, seqs)
+    tc, f1, stats = count_long(nt, *on_device(seqs), [K], PL)
     oc, of1 = oracle("mixed")
     assert np.array_equal(f1, of1), (f1, of1)
     assert np.array_equal(tc, oc)
-    assert stats == planned(nt, seqs, K, PL) and stats[0] > 0
+    assert stats == planned(nt, map(len, seqs), K, PL) and stats[0] > 0
 
 
 def test_several_rounds_of_bounded_scratch(nt, monkeypatch):
     """NTC_LONG_ROUND_BYTES = 1: a round is one tile of pieces / 64 row slots, so both inputs take several"""
     monkeypatch.setenv("NTC_LONG_ROUND_BYTES", "1")
     for which, seqs in (("one", one_long()), ("mixed", mixed())):
-        tc, f1, stats = count_long(nt, seqs)
+        tc, f1, stats = count_long(nt, *on_device(seqs), [K], PL)
         oc, of1 = oracle(which)
         assert np.array_equal(f1, of1) and np.array_equal(tc, oc), which
-        assert stats == planned(nt, seqs, K, PL)
+        assert stats == planned(nt, map(len, seqs), K, PL)
 
 
 @pytest.mark.parametrize("k,gap,pl", [(12, 2, 32), (32, 8, 64)])
 def test_tiled_gap_seeds(nt, k, gap, pl):
     seqs = mixed()
-    tc, f1, stats = count_long(nt, seqs, k=k, gap=gap, piece_len=pl, flags=nt.FLAG_REQUIRE_TILED)
+    tc, f1, stats = count_long(nt, *on_device(seqs), [k], pl, gap=gap, flags=nt.FLAG_REQUIRE_TILED)
     oc, of1 = oracle("mixed", k, gap)
     assert np.array_equal(f1, of1) and np.array_equal(tc, oc)
-    assert stats == planned(nt, seqs, k, pl) and stats[0] > 0
+    assert stats == planned(nt, map(len, seqs), k, pl) and stats[0] > 0
 
 
 def test_engine_chooses_the_piece_length(nt):
@@ -134,7 +103,7 @@ def test_engine_chooses_the_piece_length(nt):
     seq = np.frombuffer(b"ACGT", dtype=np.uint8)[gen.integers(0, 4, size=3_000_000)]
     seq[gen.integers(0, seq.size, size=50)] = ord("N")
     seqs = (seq.tobytes(),)
-    tc, f1, stats = count_long(nt, seqs, piece_len=0)
+    tc, f1, stats = count_long(nt, *on_device(seqs), [K], 0)
     oc, of1 = orc.sketch_reads(list(seqs), [K], 0, R, S_BITS)
     assert np.array_equal(f1, of1) and np.array_equal(tc, oc)
     assert stats[0] > 0 and stats[1] == 1
@@ -194,7 +163,7 @@ def test_nthll_engine_counts_like_submit(nt):
 
 def test_host_batches_take_the_path_behind_NTC_LONG_MIN(nt, monkeypatch):
     rng = random.Random(3)
-    seqs = list(mixed()) + [rseq(rng, 150) for _ in range(3000)]
+    seqs = list(mixed()) + [rseq_acgt(rng, 150) for _ in range(3000)]
     oc, of1 = orc.sketch_reads(seqs, [K], 0, R, S_BITS)
     buf = b"".join(seqs)
     lens = np.array([len(s) for s in seqs], dtype=np.uint32)
@@ -236,7 +205,7 @@ def test_reset_zeroes_the_stats_and_submits_accumulate(nt):
     seqs = mixed()
     d, offs = on_device(seqs)
     oc, of1 = oracle("mixed")
-    want = planned(nt, seqs, K, PL)
+    want = planned(nt, map(len, seqs), K, PL)
     with nt.Engine([K], r_bits=R, s_bits=S_BITS) as e:
         e.submit_long_device(d.data_ptr(), offs, PL)
         e.sync()

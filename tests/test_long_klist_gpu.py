@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 import orc
+from gpu_support import count_long, nt, on_device, planned  # noqa: F401
+from support import assert_same_sketch, rseq_acgt
 
 pytestmark = pytest.mark.gpu
 
@@ -24,26 +26,6 @@ LISTS = [(17, 32), (20, 26, 32), (12, 27)]  # spread 15 (L_17 = 33 = 2 x 16 + 1,
 INPUTS = ["one", "mixed", "short"]
 
 
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
-
-
-def rseq(rng, n):
-    return bytes(rng.choice(b"ACGT") for _ in range(n))
-
-
-def on_device(seqs, lead=3):
-    """the sequences behind one another in one device buffer, `lead` bytes in front (start offsets of any alignment) -> (tensor, host offsets)"""
-    offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
-    offs[0] = lead
-    offs[1:] = lead + np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    host = np.frombuffer(b"#" * lead + b"".join(seqs) + b"#", dtype=np.uint8).copy()
-    return torch.from_numpy(host).cuda(), offs
-
-
 def step_of(kl):
     return PL - max(kl) + 1
 
@@ -51,7 +33,7 @@ def step_of(kl):
 def one_long(kl):
     """one sequence of more than 2048 pieces (the cut crosses a tile boundary) whose remainder has windows of every k"""
     rng = random.Random(7)
-    s = rseq(rng, PL + step_of(kl) * 2100 + 20)
+    s = rseq_acgt(rng, PL + step_of(kl) * 2100 + 20)
     m = (len(s) - PL) // step_of(kl) + 1
     assert m > 2048 and len(s) - m * step_of(kl) >= max(kl)
     return (s,)
@@ -66,7 +48,7 @@ def mixed(kl):
             9001, 15003, 17777, 12222, 2222] + [rng.randrange(1, 400) for _ in range(24)]
     for n in lens[9:11]:
         assert (n - PL) // S + 1 == 5
-    seqs = [bytearray(rseq(rng, n)) for n in lens]
+    seqs = [bytearray(rseq_acgt(rng, n)) for n in lens]
     big = seqs[11]
     # piece-relative positions just in front of the overlap [S, L), on its first byte, inside it and on its last byte, in different pieces
     for j, pos in enumerate([S - 2, S - 1, S, S + 1, (S + PL) // 2, PL - 2, PL - 1, kmin - 1, S + kmin - 1, PL - kmin]):
@@ -94,9 +76,9 @@ def many_short(kl):
     S = step_of(kl)
     seqs = []
     for i in range(1200):
-        seqs.append(rseq(rng, PL + (rng.randrange(1, 4) - 1) * S + rng.randrange(0, S)))
+        seqs.append(rseq_acgt(rng, PL + (rng.randrange(1, 4) - 1) * S + rng.randrange(0, S)))
         if i % 2:
-            seqs.append(rseq(rng, rng.randrange(0, PL)))
+            seqs.append(rseq_acgt(rng, rng.randrange(0, PL)))
         if i % 97 == 0:
             dirty = bytearray(seqs[-1])
             if dirty:
@@ -115,50 +97,29 @@ def oracle(which, kl):
     return orc.sketch_reads(list(inputs(which, kl)), list(kl), 0, R, S_BITS)
 
 
-def planned(nt, seqs, kl):
-    m = [nt.long_plan(max(kl), PL, len(s))[0] for s in seqs]
-    return sum(m), sum(1 for x in m if x)
-
-
-def count_long(nt, seqs, kl, piece_len=PL, flags=0, submits=1):
-    d, offs = on_device(seqs)
-    with nt.Engine(list(kl), r_bits=R, s_bits=S_BITS, flags=flags) as e:
-        for _ in range(submits):
-            e.submit_long_device(d.data_ptr(), offs, piece_len)
-        tc, _, f1 = e.finish(counters=True)
-        return tc, f1, e.long_stats()
-
-
-def check(got, want, what):
-    (tc, f1), (oc, of1) = got, want
-    print(what, "F1", f1.tolist(), "oracle", of1.tolist())
-    assert np.array_equal(f1, of1), (what, f1, of1)
-    assert np.array_equal(tc, oc), what
-
-
 @pytest.mark.parametrize("kl", LISTS, ids=str)
 def test_one_sequence_across_a_tile_boundary(nt, kl):
     seqs = inputs("one", kl)
-    tc, f1, stats = count_long(nt, seqs, kl)
+    tc, f1, stats = count_long(nt, *on_device(seqs), kl, PL)
     assert stats == (sum(nt.long_plan(max(kl), PL, len(s))[0] for s in seqs), 1)  # (0, 0) without the list route
-    check((tc, f1), oracle("one", kl), kl)
+    assert_same_sketch((tc, f1), oracle("one", kl), kl)
 
 
 @pytest.mark.parametrize("kl", LISTS, ids=str)
 def test_many_sequences_every_boundary_length(nt, kl):
     seqs = inputs("mixed", kl)
-    tc, f1, stats = count_long(nt, seqs, kl)
-    assert stats == planned(nt, seqs, kl) and stats[0] > 0
-    check((tc, f1), oracle("mixed", kl), kl)
+    tc, f1, stats = count_long(nt, *on_device(seqs), kl, PL)
+    assert stats == planned(nt, map(len, seqs), max(kl), PL) and stats[0] > 0
+    assert_same_sketch((tc, f1), oracle("mixed", kl), kl)
 
 
 @pytest.mark.parametrize("kl", LISTS, ids=str)
 def test_many_short_sequences_in_one_block_of_the_cut(nt, kl):
     seqs = inputs("short", kl)
     assert sum(1 for s in seqs if len(s) >= PL) >= 200 and any(len(s) < PL for s in seqs)
-    tc, f1, stats = count_long(nt, seqs, kl)
-    assert stats == planned(nt, seqs, kl) and stats[1] == 1200
-    check((tc, f1), oracle("short", kl), kl)
+    tc, f1, stats = count_long(nt, *on_device(seqs), kl, PL)
+    assert stats == planned(nt, map(len, seqs), max(kl), PL) and stats[1] == 1200
+    assert_same_sketch((tc, f1), oracle("short", kl), kl)
 
 
 @pytest.mark.parametrize("which", INPUTS)
@@ -167,10 +128,10 @@ def test_several_rounds_of_bounded_scratch(nt, monkeypatch, kl, which):
     """NTC_LONG_ROUND_BYTES = 1: a round is one tile of pieces / 64 row slots; every input holds more than 2048 pieces, so a round begins inside a sequence"""
     monkeypatch.setenv("NTC_LONG_ROUND_BYTES", "1")
     seqs = inputs(which, kl)
-    assert planned(nt, seqs, kl)[0] > 2048
-    tc, f1, stats = count_long(nt, seqs, kl)
-    assert stats == planned(nt, seqs, kl)
-    check((tc, f1), oracle(which, kl), (kl, which))
+    assert planned(nt, map(len, seqs), max(kl), PL)[0] > 2048
+    tc, f1, stats = count_long(nt, *on_device(seqs), kl, PL)
+    assert stats == planned(nt, map(len, seqs), max(kl), PL)
+    assert_same_sketch((tc, f1), oracle(which, kl), (kl, which))
 
 
 @pytest.mark.parametrize("rounds", [False, True])
@@ -180,26 +141,26 @@ def test_one_k_on_the_same_inputs(nt, monkeypatch, which, rounds):
     if rounds:
         monkeypatch.setenv("NTC_LONG_ROUND_BYTES", "1")
     seqs = inputs(which, (17, 32))
-    tc, f1, stats = count_long(nt, seqs, (32,))
+    tc, f1, stats = count_long(nt, *on_device(seqs), (32,), PL)
     oc, of1 = oracle(which, (17, 32))
-    assert stats == planned(nt, seqs, (32,))
-    check((tc, f1), (oc[1:], of1[1:]), which)
+    assert stats == planned(nt, map(len, seqs), 32, PL)
+    assert_same_sketch((tc, f1), (oc[1:], of1[1:]), which)
 
 
 def test_require_tiled_accepts_a_list(nt):
     kl = (17, 32)
     seqs = inputs("mixed", kl)
-    tc, f1, stats = count_long(nt, seqs, kl, flags=nt.FLAG_REQUIRE_TILED)  # raises without the list route
-    assert stats == planned(nt, seqs, kl)
-    check((tc, f1), oracle("mixed", kl), kl)
+    tc, f1, stats = count_long(nt, *on_device(seqs), kl, PL, flags=nt.FLAG_REQUIRE_TILED)  # raises without the list route
+    assert stats == planned(nt, map(len, seqs), max(kl), PL)
+    assert_same_sketch((tc, f1), oracle("mixed", kl), kl)
 
 
 def test_submits_accumulate_on_a_deferring_engine(nt):
     kl = (20, 26, 32)
     seqs = inputs("mixed", kl)
     oc, of1 = oracle("mixed", kl)
-    want = planned(nt, seqs, kl)
-    tc, f1, stats = count_long(nt, seqs, kl, flags=nt.FLAG_DEFER_REDO, submits=2)
+    want = planned(nt, map(len, seqs), max(kl), PL)
+    tc, f1, stats = count_long(nt, *on_device(seqs), kl, PL, flags=nt.FLAG_DEFER_REDO, submits=2)
     assert stats == (2 * want[0], 2 * want[1])
     assert np.array_equal(f1, 2 * of1), (f1, of1)
     assert np.array_equal(tc, (2 * oc.astype(np.uint32)).astype(np.uint16))  # t_Counter wraps at 16 bits
@@ -217,7 +178,7 @@ def test_piece_length_below_kmax_plus_15_is_refused(nt):
 def test_host_batches_take_the_path_behind_NTC_LONG_MIN(nt, monkeypatch):
     kl = (20, 26, 32)
     rng = random.Random(3)
-    seqs = list(inputs("mixed", kl)) + [rseq(rng, 150) for _ in range(3000)]
+    seqs = list(inputs("mixed", kl)) + [rseq_acgt(rng, 150) for _ in range(3000)]
     want = orc.sketch_reads(seqs, list(kl), 0, R, S_BITS)
     buf = b"".join(seqs)
     lens = np.array([len(s) for s in seqs], dtype=np.uint32)
@@ -235,10 +196,10 @@ def test_host_batches_take_the_path_behind_NTC_LONG_MIN(nt, monkeypatch):
     monkeypatch.delenv("NTC_LONG_MIN", raising=False)
     for spans in (False, True):
         tc, f1, stats = run(spans)
-        check((tc, f1), want, ("default", spans))
+        assert_same_sketch((tc, f1), want, ("default", spans))
         assert stats == (0, 0)  # the default leaves host batches of this size on row slots
     monkeypatch.setenv("NTC_LONG_MIN", "1")
     for spans in (False, True):
         tc, f1, stats = run(spans)
-        check((tc, f1), want, ("NTC_LONG_MIN=1", spans))
+        assert_same_sketch((tc, f1), want, ("NTC_LONG_MIN=1", spans))
         assert stats[0] > 0 and stats[1] == sum(1 for s in seqs if nt.long_plan(max(kl), 1008, len(s))[0] >= 2)

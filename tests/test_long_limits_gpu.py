@@ -10,6 +10,8 @@ import pytest
 
 import limits_model as lm
 import orc
+from gpu_support import count_long, nt, on_device, planned  # noqa: F401
+from support import assert_same_sketch, offsets_of
 
 pytestmark = pytest.mark.gpu
 
@@ -20,52 +22,13 @@ ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
 CUT_RUN = 16  # chunks of a piece one workgroup of cut_tiles_kernel moves (ntc_long.hip:13)
 
 
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
-
-
-def on_device(buf, offs, lead=3):
-    """the sequences [offs[i], offs[i + 1]) of buf behind `lead` bytes in one device buffer (start offsets of any alignment) -> (tensor, host offsets)"""
-    host = np.concatenate([np.full(lead, ord("#"), dtype=np.uint8), buf, np.full(1, ord("#"), dtype=np.uint8)])
-    d = torch.from_numpy(host).cuda()
-    assert d.data_ptr() % 4 == 0
-    return d, (offs + np.uint64(lead)).astype(np.uint64)
-
-
-def offsets_of(lens):
-    offs = np.zeros(len(lens) + 1, dtype=np.uint64)
-    offs[1:] = np.cumsum(lens, dtype=np.uint64)
-    return offs
-
-
 def sketch(buf, offs, kl):
     counters = np.zeros((len(kl), 2, 1 << R), dtype=np.uint16)
     f1 = orc.sketch_update(counters, buf if buf.size else np.zeros(1, dtype=np.uint8), offs, list(kl), 0, R, S_BITS)
     return counters, f1
 
 
-def planned(nt, offs, kmax, pl):
-    m = [nt.long_plan(kmax, pl, int(n))[0] for n in np.diff(offs)]
-    return sum(m), sum(1 for x in m if x)
-
-
-def count_long(nt, buf, offs, kl, piece_len, lead=3, flags=0):
-    d, doffs = on_device(buf, offs, lead)
-    with nt.Engine(list(kl), r_bits=R, s_bits=S_BITS, flags=flags) as e:
-        e.submit_long_device(d.data_ptr(), doffs, piece_len)
-        tc, _, f1 = e.finish(counters=True)
-        return (tc, f1), e.long_stats()
-
-
-def same(got, want, what):
-    (tc, f1), (oc, of1) = got, want
-    print(what, "F1", f1.tolist(), "oracle", of1.tolist(), "counters off", int((tc != oc).sum()))
-    assert of1.all(), "the oracle counted nothing"
-    assert np.array_equal(f1, of1), (what, f1, of1)
-    assert np.array_equal(tc, oc), what
+same = functools.partial(assert_same_sketch, nonempty=True)  # (the oracle counted something in every plane)
 
 
 # ---- piece lengths of several runs ----
@@ -126,7 +89,7 @@ def assert_runs(nt, pl, offs):
         assert n_runs == 2 and n_chunks % CUT_RUN == 1  # a last run of one chunk (ntc_long.hip:42)
     else:
         assert n_runs > 1
-    pieces, with_piece = planned(nt, offs, K, pl)
+    pieces, with_piece = planned(nt, np.diff(offs), K, pl)
     assert with_piece > 1 and pieces > with_piece  # ntc_long.hip:50-72: a table of several entries, sequences of several pieces
     lens = np.diff(offs).astype(np.int64)
     S = pl - (K - 1)
@@ -138,8 +101,8 @@ def assert_runs(nt, pl, offs):
 def test_piece_lengths_of_several_runs(nt, pl, lead):
     buf, offs = piece_input(pl)
     assert_runs(nt, pl, offs)
-    got, stats = count_long(nt, buf, offs, (K,), pl, lead, flags=nt.FLAG_REQUIRE_TILED)
-    assert stats == planned(nt, offs, K, pl)
+    *got, stats = count_long(nt, *on_device(buf, offs, lead), (K,), pl, flags=nt.FLAG_REQUIRE_TILED)
+    assert stats == planned(nt, np.diff(offs), K, pl)
     same(got, piece_oracle(pl, (K,)), (pl, lead))
 
 
@@ -149,8 +112,8 @@ def test_piece_lengths_under_a_k_list(nt, pl):
     kl = (17, K)
     buf, offs = piece_input(pl)
     assert_runs(nt, pl, offs)
-    got, stats = count_long(nt, buf, offs, kl, pl, flags=nt.FLAG_REQUIRE_TILED)
-    assert stats == planned(nt, offs, K, pl)
+    *got, stats = count_long(nt, *on_device(buf, offs), kl, pl, flags=nt.FLAG_REQUIRE_TILED)
+    assert stats == planned(nt, np.diff(offs), K, pl)
     same(got, piece_oracle(pl, kl), (pl, kl))
 
 
@@ -181,7 +144,7 @@ def table_oracle(n_full, kl):
 
 
 def assert_depth(nt, n_full, offs):
-    pieces, with_piece = planned(nt, offs, K, PL)
+    pieces, with_piece = planned(nt, np.diff(offs), K, PL)
     assert with_piece == n_full and len(offs) - 1 == n_full + n_full // 2  # the table cut_tiles_kernel gets has exactly n_full entries
     assert n_full <= pieces <= 3 * n_full
     assert max(lm.cut_search_steps(n_full, t) for t in {0, 1, 63, 64, n_full // 2, n_full - 2, n_full - 1} if t < n_full) == DEPTHS[n_full]
@@ -192,7 +155,7 @@ def assert_depth(nt, n_full, offs):
 def test_table_search_depth(nt, n_full):
     buf, offs = table_input(n_full)
     want = assert_depth(nt, n_full, offs)
-    got, stats = count_long(nt, buf, offs, (K,), PL, flags=nt.FLAG_REQUIRE_TILED)
+    *got, stats = count_long(nt, *on_device(buf, offs), (K,), PL, flags=nt.FLAG_REQUIRE_TILED)
     assert stats == want
     same(got, table_oracle(n_full, (K,)), n_full)
 
@@ -200,7 +163,7 @@ def test_table_search_depth(nt, n_full):
 def test_table_search_depth_under_a_k_list(nt):
     buf, offs = table_input(4097)
     want = assert_depth(nt, 4097, offs)
-    got, stats = count_long(nt, buf, offs, (17, K), PL, flags=nt.FLAG_REQUIRE_TILED)
+    *got, stats = count_long(nt, *on_device(buf, offs), (17, K), PL, flags=nt.FLAG_REQUIRE_TILED)
     assert stats == want
     same(got, table_oracle(4097, (17, K)), "17,32")
 
@@ -211,7 +174,7 @@ def test_rounds_begin_in_the_middle_of_a_three_step_table(nt, monkeypatch):
     buf, offs = table_input(4097)
     want = assert_depth(nt, 4097, offs)
     assert want[0] > 3 * 2048  # four rounds or more
-    got, stats = count_long(nt, buf, offs, (K,), PL, flags=nt.FLAG_REQUIRE_TILED)
+    *got, stats = count_long(nt, *on_device(buf, offs), (K,), PL, flags=nt.FLAG_REQUIRE_TILED)
     assert stats == want
     same(got, table_oracle(4097, (K,)), "rounds")
 
@@ -241,8 +204,8 @@ def test_gather_of_more_slots_than_waves(nt, monkeypatch):
     monkeypatch.delenv("NTC_LONG_ROUND_BYTES", raising=False)  # (one round)
     buf, offs = slot_input(32, 47)
     assert_slots(offs, K)
-    assert planned(nt, offs, K, PL) == (0, 0)
-    got, stats = count_long(nt, buf, offs, (K,), PL)
+    assert planned(nt, np.diff(offs), K, PL) == (0, 0)
+    *got, stats = count_long(nt, *on_device(buf, offs), (K,), PL)
     assert stats == (0, 0)
     same(got, sketch(buf, offs, (K,)), "slots")
 
@@ -252,6 +215,6 @@ def test_gather_whole_of_more_slots_than_waves(nt, monkeypatch):
     monkeypatch.delenv("NTC_LONG_ROUND_BYTES", raising=False)
     buf, offs = slot_input(64, 100)
     assert_slots(offs, 64)
-    got, stats = count_long(nt, buf, offs, (64,), 0)
+    *got, stats = count_long(nt, *on_device(buf, offs), (64,), 0)
     assert stats == (0, 0)
     same(got, sketch(buf, offs, (64,)), "whole")

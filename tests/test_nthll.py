@@ -4,22 +4,13 @@ import gzip
 import json
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import orc
+from support import GOLD, NTHLL, ROOT, run_cli, small_reads
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
-NTHLL = os.path.join(ROOT, "ntcard_amd", "bin", "nthll")
-
-
-def small_reads():
-    with gzip.open(os.path.join(GOLD, "reads_small.fq.gz"), "rb") as f:
-        lines = f.read().split(b"\n")
-    return [lines[i] for i in range(1, len(lines) - 1, 4)], b"\n".join(lines)
 
 
 def goldens():
@@ -28,7 +19,7 @@ def goldens():
 
 
 def test_oracle_matches_reference_goldens():
-    reads, _ = small_reads()
+    reads = small_reads()
     for c in goldens()["cases"]:
         regs, est = orc.hll_reads(reads, c["k"], c["n_bits"])
         assert "%016x" % orc.fnv1a64(regs) == c["fnv1a64"] and int(regs.max()) == c["max"]
@@ -56,7 +47,7 @@ def test_oracle_live_against_reference():
 @pytest.mark.gpu
 def test_gpu_registers_match_oracle_and_goldens():
     import ntcard_amd as nt
-    reads, _ = small_reads()
+    reads = small_reads()
     for c in goldens()["cases"]:
         with nt.HllEngine(c["k"], c["n_bits"]) as e:
             e.submit_reads(reads)
@@ -123,19 +114,19 @@ def test_gpu_fullsize_matches_the_reference():
 
 @pytest.mark.gpu
 def test_nthll_cli_prints_the_reference_line(tmp_path):
-    _, fq = small_reads()
-    (tmp_path / "reads.fq").write_bytes(fq)
+    with gzip.open(os.path.join(GOLD, "reads_small.fq.gz"), "rb") as f:
+        (tmp_path / "reads.fq").write_bytes(f.read())
     g = goldens()
-    r = subprocess.run([NTHLL, "-k", "32", "reads.fq"], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    r = run_cli(NTHLL, ["-k", "32", "reads.fq"], cwd=tmp_path, timeout=300)
     assert r.returncode == 0 and r.stdout.decode() == g["cli_k32"], r.stderr
-    r = subprocess.run([NTHLL, "-k", "20", "-b", "12", "reads.fq"], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    r = run_cli(NTHLL, ["-k", "20", "-b", "12", "reads.fq"], cwd=tmp_path, timeout=300)
     assert r.returncode == 0 and r.stdout.decode() == g["cli_k20_b12"], r.stderr
 
 
 def test_nthll_cli_argument_errors():
-    r = subprocess.run([NTHLL], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    r = run_cli(NTHLL, [], timeout=None)
     assert r.returncode == 1 and b"nthll: missing arguments" in r.stderr
-    r = subprocess.run([NTHLL, "--version"], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    r = run_cli(NTHLL, ["--version"], timeout=None)
     assert r.returncode == 0 and b"nthll" in r.stderr
 
 
@@ -158,7 +149,7 @@ def test_nthll_live_differential_against_reference_binary(tmp_path):
         fq.append("@r%d\n%s\n+\n%s\n" % (i, s, "I" * len(s)))
     (tmp_path / "r.fq").write_text("".join(fq))
     for args in (["-k", "32", "c.fa"], ["-k", "21", "-b", "14", "r.fq"], ["-k", "48", "c.fa", "r.fq"]):
-        ours = subprocess.run([NTHLL] + args, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
-        ref = subprocess.run([REF_NTHLL] + args, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        ours = run_cli(NTHLL, args, cwd=tmp_path, timeout=300)
+        ref = run_cli(REF_NTHLL, args, cwd=tmp_path, timeout=300)
         assert ours.returncode == 0 and ref.returncode == 0, (ours.stderr, ref.stderr)
         assert ours.stdout == ref.stdout, (args, ours.stdout, ref.stdout)

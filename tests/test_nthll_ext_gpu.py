@@ -6,7 +6,6 @@ import gzip
 import json
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,34 +13,19 @@ import pytest
 import hll_model as hm
 import orc
 import strand_model as sm
+from gpu_support import nt, on_device  # noqa: F401
+from support import GOLD, NTHLL, rseq_acgt, run_cli, to_slots
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTHLL = os.path.join(ROOT, "ntcard_amd", "bin", "nthll")
-GOLD = os.path.join(ROOT, "tests", "golden")
 STRANDS = [("canonical", sm.CANONICAL), ("forward", sm.FORWARD), ("reverse", sm.REVERSE)]
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
 
 
 def goldens():
     with open(os.path.join(GOLD, "nthll_goldens.json")) as f:
         return json.load(f)
-
-
-def to_slots(reads, stride):
-    buf = np.full(len(reads) * stride + 16, ord("A"), dtype=np.uint8)
-    for i, r in enumerate(reads):
-        buf[i * stride: i * stride + len(r)] = np.frombuffer(r, dtype=np.uint8)
-    return buf
 
 
 def make(nt, masks, seeded, n_bits, strand):
@@ -133,15 +117,11 @@ K, PL = 32, 48  # (the shape of tests/test_long_gpu.py: mixed)
 STEP = PL - K + 1
 
 
-def rseq4(rng, n):
-    return bytes(rng.choice(b"ACGT") for _ in range(n))
-
-
 def mixed():
     """about 40 sequences: every boundary length of the plan, dirty bytes, a few of several thousand bases"""
     rng = random.Random(11)
     lens = [0, K - 1, K, PL - 1, PL, PL + STEP - 1, PL + STEP, 5 * STEP + K - 1, 3001, 5003, 7777, 2222] + [rng.randrange(1, 400) for _ in range(28)]
-    seqs = [bytearray(rseq4(rng, n)) for n in lens]
+    seqs = [bytearray(rseq_acgt(rng, n)) for n in lens]
     big = seqs[8]
     big[100] = ord("N")
     big[500:505] = b"acgtn"
@@ -159,11 +139,7 @@ def mixed():
 
 def test_long_sequences_count_like_submit_reads(nt):
     seqs = mixed()
-    lead = 3
-    offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
-    offs[0] = lead
-    offs[1:] = lead + np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    d = torch.from_numpy(np.frombuffer(b"#" * lead + b"".join(seqs) + b"#", dtype=np.uint8).copy()).cuda()
+    d, offs = on_device(seqs)
     with nt.HllEngine([20, 32], n_bits=10, strand="forward") as e:
         e.submit_reads(seqs)
         want = e.finish()
@@ -235,10 +211,6 @@ def test_reset_zeroes_every_plane(nt):
 
 
 # ---- 8. the command line ----
-def run_cli(args, cwd):
-    return subprocess.run([NTHLL] + args, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
-
-
 def write_reads(tmp_path):
     with gzip.open(os.path.join(GOLD, "reads_small.fq.gz"), "rb") as f:
         (tmp_path / "reads.fq").write_bytes(f.read())
@@ -254,11 +226,11 @@ def test_cli_prints_one_line_per_plane(nt, tmp_path):
     for args, masks, sname, labels in cases:
         regs, _ = hm.planes_of(hm.small_values(masks), sm.STRANDS[sname], 16)
         want = "".join("F0, Exp# of distnt kmers(%s): %d\n" % (lab, int(nt.hll_estimate(regs[i], 16, strand=sname))) for i, lab in enumerate(labels))
-        r = run_cli(args + [src], tmp_path)
+        r = run_cli(NTHLL, args + [src], cwd=tmp_path, timeout=300)
         assert r.returncode == 0 and r.stdout.decode() == want, (args, r.stdout, r.stderr)
 
 
 def test_cli_canonical_is_the_reference_line(tmp_path):
     src = write_reads(tmp_path)
-    r = run_cli(["--strand=canonical", "-k", "32", src], tmp_path)
+    r = run_cli(NTHLL, ["--strand=canonical", "-k", "32", src], cwd=tmp_path, timeout=300)
     assert r.returncode == 0 and r.stdout.decode() == goldens()["cli_k32"], r.stderr

@@ -2,8 +2,6 @@
 / --seed / -k K,K`): the model the GPU tests compare against (tests/hll_model.py) is pinned to the oracle, its inputs tell the strands and the masks
 apart, the strand estimate is the reference's with the alpha not halved, and every malformed argument is refused before a device is looked for."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,9 +10,8 @@ import hll_model as hm
 import orc
 import strand_model as sm
 from ntcard_amd import _abi
+from support import NTHLL, hll_create_ex, run_cli
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTHLL = os.path.join(ROOT, "ntcard_amd", "bin", "nthll")
 ERR_ARG = -1
 FWD, REV = 512, 1024
 
@@ -81,23 +78,8 @@ def test_estimate_strand(b):
 
 
 # ---- ntc_hll_create_ex: every argument error comes before the device (this test runs where there is none) ----
-def create_ex(k=None, seeds=None, n_bits=16, flags=0, n_k=None, n_seeds=None):
-    L = _abi.lib()
-    cfg = _abi.NtcHllConfig()
-    keep = []
-    if k is not None:
-        arr = (C.c_uint32 * max(1, len(k)))(*k)
-        keep.append(arr)
-        cfg.k = C.cast(arr, C.POINTER(C.c_uint32))
-    cfg.n_k = len(k) if n_k is None and k is not None else (n_k or 0)
-    if seeds is not None:
-        sarr = (C.c_char_p * max(1, len(seeds)))(*seeds)
-        keep.append(sarr)
-        cfg.seeds = C.cast(sarr, C.POINTER(C.c_char_p))
-    cfg.n_seeds = len(seeds) if n_seeds is None and seeds is not None else (n_seeds or 0)
-    cfg.n_bits, cfg.device, cfg.flags = n_bits, 0, flags
-    h = C.c_void_p()
-    rc = L.ntc_hll_create_ex(C.byref(cfg), C.byref(h))
+def create_ex(**kw):
+    rc, h, L = hll_create_ex(**kw)
     if h:
         L.ntc_destroy(h)
     return rc, L.ntc_last_error().decode()
@@ -160,6 +142,6 @@ def test_python_constructors_check_the_strand_first():
     (["--seed=1101,", "reads.fq"], b"--seed"),
 ])
 def test_cli_argument_errors(args, needle, tmp_path):
-    r = subprocess.run([NTHLL] + args, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)  # (reads.fq does not exist: never opened)
+    r = run_cli(NTHLL, args, cwd=tmp_path, timeout=60)  # (reads.fq does not exist: never opened)
     assert r.returncode == 1 and r.stdout == b"", (args, r.stdout, r.stderr)
     assert r.stderr.startswith(b"nthll: ") and needle in r.stderr, (args, r.stderr)

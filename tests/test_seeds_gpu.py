@@ -1,31 +1,19 @@
 """GPU tests of spaced seeds given as masks (include/ntcard_hip.h: ntc_create_seeded, ntc_hash_dump_seed_device; `ntcard --seed`):
 hashes against the oracle's stHashIterator / NTMSM64 restatement with the mask's don't-care positions, sketches against that
 restatement pushed through ntComp (ntcard.cpp:132-145), equivalences with plain k and with -g, every submit path, the CLI."""
-import ctypes as C
-import gzip
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import orc
+from gpu_support import nt  # noqa: F401
+from support import GOLD, NTCARD, mask_with, masks_for, rseq, run_cli, sketch_from_values, small_reads, to_slots
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTCARD = os.path.join(ROOT, "ntcard_amd", "bin", "ntcard")
-GOLD = os.path.join(ROOT, "tests", "golden")
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
 
 
 def seed_hash(seq, mask):
@@ -42,65 +30,7 @@ def seed_hash(seq, mask):
 
 def oracle_sketch(reads, masks, r_bits, s_bits):
     """t_Counter [n][2][1 << r_bits] (uint16, as the engine reports it) and F1 [n]: the oracle's hashes through ntComp"""
-    tc = np.zeros((len(masks), 2, 1 << r_bits), dtype=np.uint16)
-    f1 = np.zeros(len(masks), dtype=np.uint64)
-    s_mask = np.uint64((1 << (s_bits - 1)) - 1)
-    for mi, m in enumerate(masks):
-        hs = [seed_hash(r, m)[0] for r in reads]
-        h = np.concatenate(hs) if hs else np.zeros(0, dtype=np.uint64)
-        f1[mi] = h.size
-        s0 = (h >> np.uint64(63 - s_bits)) == np.uint64(1)
-        s1 = (h >> np.uint64(64 - s_bits)) == s_mask
-        sample = np.where(s1, 1, np.where(s0, 0, 2))
-        keep = sample < 2
-        np.add.at(tc[mi], (sample[keep], (h[keep] & np.uint64((1 << r_bits) - 1)).astype(np.int64)), np.uint16(1))
-    return tc, f1
-
-
-def rseq(rng, n, pn=0.0, plow=0.1):
-    out = []
-    for _ in range(n):
-        r = rng.random()
-        if r < pn:
-            out.append(rng.choice("NnRY-"))
-        elif r < pn + plow:
-            out.append(rng.choice("acgtu"))
-        else:
-            out.append(rng.choice("ACGTU"))
-    return "".join(out).encode()
-
-
-def to_slots(reads, L, stride):
-    buf = np.full(len(reads) * stride + 16, ord("A"), dtype=np.uint8)
-    for i, r in enumerate(reads):
-        buf[i * stride: i * stride + len(r)] = np.frombuffer(r, dtype=np.uint8)
-    return buf
-
-
-def small_reads():
-    with gzip.open(os.path.join(GOLD, "reads_small.fq.gz"), "rb") as f:
-        lines = f.read().split(b"\n")
-    return [lines[i] for i in range(1, len(lines) - 1, 4)]
-
-
-def mask_with(k, zeros):
-    m = ["1"] * k
-    for i in zeros:
-        m[i] = "0"
-    return "".join(m)
-
-
-# masks of every shape the kernel distinguishes, per span: one interior run, several runs, runs touching offset 0, offset k-1 and both,
-# a single '0', alternating 0101...1 (more toggle pairs than the rolling form takes), a single '1', and all '1' (plain k)
-def masks_for(k):
-    if k == 1:
-        return ["1"]
-    out = {"1" * k, mask_with(k, [k // 2]), "1" * (k - 1) + "0", "0" + "1" * (k - 1), ("01" * k)[:k - 1] + "1", "0" * (k - 1) + "1"}
-    if k >= 4:
-        out.add(mask_with(k, range(k // 4, k // 2)))                          # one interior run
-        out.add(mask_with(k, list(range(0, k // 4)) + [k - 1]))               # runs at both ends
-        out.add(mask_with(k, list(range(1, 2)) + list(range(k // 2, k // 2 + 2)) + [k - 2]))  # several runs
-    return sorted(out)
+    return sketch_from_values([np.concatenate([seed_hash(r, m)[0] for r in reads] or [np.zeros(0, dtype=np.uint64)]) for m in masks], r_bits, s_bits)
 
 
 SPANS = [1, 12, 31, 32, 33, 64, 97, 200]
@@ -114,7 +44,7 @@ def test_hash_dump_matches_oracle(nt, k):
         n = 64 * 3 + 37
         reads = [rseq(rng, L, pn=rng.choice([0.0, 0.0, 0.02])) for _ in range(n)]
         stride = (L + 3) & ~3
-        d = torch.from_numpy(to_slots(reads, L, stride)).cuda()
+        d = torch.from_numpy(to_slots(reads, stride)).cuda()
         maxw = max(L - k + 1, 1)
         for m in masks_for(k):
             dh = torch.zeros(n * maxw, dtype=torch.int64, device="cuda")
@@ -166,7 +96,7 @@ def test_sketch_matches_oracle_row_slots_and_tiles(nt):
     reads = [rseq(rng, L, pn=rng.choice([0.0, 0.0, 0.003])) for _ in range(n)]
     oc, of1 = oracle_sketch(reads, masks, r_bits, s_bits)
     stride = 152
-    d = torch.from_numpy(to_slots(reads, L, stride)).cuda()
+    d = torch.from_numpy(to_slots(reads, stride)).cuda()
     with nt.Engine.from_seeds(masks, r_bits=r_bits, s_bits=s_bits) as e:
         e.submit_device(d.data_ptr(), n, L, stride)
         tc, _, f1 = e.finish(counters=True)
@@ -258,7 +188,7 @@ def test_merge_devices_compares_seed_lists(nt):
 def test_cli_seed_reproduces_the_reference_gap_output(tmp_path):
     """the one check anchored directly on the reference binary: `ntcard -k 12 -g 2` (tests/golden/ref_k12_g2__out_k12.hist)"""
     src = os.path.join(GOLD, "reads_small.fq.gz")
-    r = subprocess.run([NTCARD, "--seed", "111110011111", "-p", "x", src], cwd=tmp_path, capture_output=True, timeout=600)
+    r = run_cli(NTCARD, ["--seed", "111110011111", "-p", "x", src], cwd=tmp_path, timeout=600)
     assert r.returncode == 0, r.stderr
     assert (tmp_path / "x_seed1_k12.hist").read_bytes() == open(os.path.join(GOLD, "ref_k12_g2__out_k12.hist"), "rb").read()
 
@@ -266,7 +196,7 @@ def test_cli_seed_reproduces_the_reference_gap_output(tmp_path):
 def test_cli_seed_compact_output_matches_the_oracle(tmp_path):
     masks = ["1110011100111", "0111111111111111111111111111110", "1" * 20]
     src = os.path.join(GOLD, "reads_small.fq.gz")
-    r = subprocess.run([NTCARD, "--seed=" + ",".join(masks), "-c", "50", "-o", "out.tsv", src], cwd=tmp_path, capture_output=True, timeout=600)
+    r = run_cli(NTCARD, ["--seed=" + ",".join(masks), "-c", "50", "-o", "out.tsv", src], cwd=tmp_path, timeout=600)
     assert r.returncode == 0, r.stderr
     rows = (tmp_path / "out.tsv").read_text().splitlines()
     assert rows[0] == "seed\tf\tn" and len(rows) == 1 + 3 * 50

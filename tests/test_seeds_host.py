@@ -1,26 +1,17 @@
 """CPU tests of the spaced-seed entry points (include/ntcard_hip.h: ntc_create_seeded, ntc_hash_dump_seed_device) and of
 `ntcard --seed`: the symbols exist, and every malformed argument is refused before a device is looked for."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import pytest
 
 from ntcard_amd import _abi
+from support import NTCARD, ROOT, abi_config, run_cli
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTCARD = os.path.join(ROOT, "ntcard_amd", "bin", "ntcard")
 ERR_ARG = -1
 
 
-def cfg(n_k=0, k=None, gap=0, flags=0):
-    c = _abi.NtcConfig(r_bits=20, s_bits=7, device=0, gap=gap, flags=flags)
-    c.n_k = n_k
-    if k is not None:
-        arr = (C.c_uint32 * len(k))(*k)
-        c.k = C.cast(arr, C.POINTER(C.c_uint32))
-        c._arr = arr
-    return c
+cfg = functools.partial(abi_config, k=None, r_bits=20)  # the seeded create: no k list
 
 
 def create_seeded(seeds, c=None):
@@ -54,7 +45,7 @@ def test_create_seeded_rejects_bad_masks_before_the_device(seeds):
     assert b"device" not in _abi.lib().ntc_last_error()
 
 
-@pytest.mark.parametrize("c", [cfg(n_k=1), cfg(k=[12]), cfg(gap=2), cfg(flags=1 << 20)])
+@pytest.mark.parametrize("c", [cfg(n_k=1), cfg(k=[12], n_k=0), cfg(gap=2), cfg(flags=1 << 20)])
 def test_create_seeded_rejects_a_k_list_or_gap_in_the_config(c):
     rc, h = create_seeded(["110011"], c)
     assert rc == ERR_ARG and not h.value
@@ -87,10 +78,6 @@ def test_hash_dump_seed_rejects_bad_masks_before_the_device(seed):
     assert rc == ERR_ARG
 
 
-def run_cli(args, cwd):
-    return subprocess.run([NTCARD] + args, cwd=cwd, capture_output=True, text=True, timeout=60)
-
-
 @pytest.mark.parametrize("args,msg", [
     (["--seed=111110011111", "-k", "12"], "cannot be combined with -k or -g"),
     (["--seed=111110011111", "-g", "2"], "cannot be combined with -k or -g"),
@@ -102,12 +89,12 @@ def run_cli(args, cwd):
 def test_cli_seed_argument_errors(tmp_path, args, msg):
     src = tmp_path / "r.fa"
     src.write_text(">r\nACGTACGTACGTACGTACGT\n")
-    r = run_cli(args + ["-p", "x", str(src)], tmp_path)
+    r = run_cli(NTCARD, args + ["-p", "x", str(src)], cwd=tmp_path, text=True)
     assert r.returncode == 1
     assert msg in r.stderr and "--help" in r.stderr
     assert not list(tmp_path.glob("x_*"))
 
 
 def test_cli_help_lists_seed():
-    r = run_cli(["--help"], ROOT)
+    r = run_cli(NTCARD, ["--help"], cwd=ROOT, text=True)
     assert r.returncode == 0 and "--seed=MASK" in r.stderr

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import sig_model
+from gpu_support import nt, submit_slots  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -14,13 +15,6 @@ torch = pytest.importorskip("torch")
 
 R = 14
 ERR_ARG, ERR_STATE = -1, -4
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
 
 
 def dev64(a):
@@ -31,21 +25,7 @@ def dev32(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32).copy()).cuda()
 
 
-@functools.lru_cache(maxsize=None)
-def device_slots(L=150, stride=152):
-    rs = list(sig_model.equal_reads())
-    a = np.full((len(rs), stride), ord("A"), dtype=np.uint8)
-    for i, r in enumerate(rs):
-        a[i, :L] = np.frombuffer(r, dtype=np.uint8)
-    return torch.from_numpy(np.concatenate([a.reshape(-1), np.full(16, ord("A"), np.uint8)])).cuda(), len(rs), L, stride
-
-
-def submit_slots(e):
-    d, n, L, stride = device_slots()
-    e.submit_device(d.data_ptr(), n, L, stride)
-
-
-def on_device(e, plane=0):
+def signature_on_device(e, plane=0):
     h, c, n = e.signature_device(plane)
     assert h.dtype == torch.int64 and c.dtype == torch.int32 and h.numel() == n and c.numel() == n and h.is_cuda and c.is_cuda
     return h.cpu().numpy().view(np.uint64), c.cpu().numpy().view(np.uint32)
@@ -65,8 +45,8 @@ def test_engine_signature_device(nt):
     extra_c = rng.integers(1, 1000, size=extra.size).astype(np.uint32)
     assert extra.size == 70000
     with nt.Engine([32], r_bits=R, s_bits=7, signature=True) as e, nt.Engine([32], r_bits=R, s_bits=7) as plain:
-        submit_slots(e)
-        assert same(on_device(e), want) and same(e.signature(), want)  # 593 pairs: the one-launch sort
+        submit_slots(e, sig_model.equal_reads())
+        assert same(signature_on_device(e), want) and same(e.signature(), want)  # 593 pairs: the one-launch sort
         # a short cap is refused with nothing written, *n included
         h, c = dev64(np.full(593, 7)), dev32(np.full(593, 7))
         n = C.c_uint64(12345)
@@ -81,7 +61,7 @@ def test_engine_signature_device(nt):
         e.signature_inject(extra, extra_c)
         order = np.argsort(np.concatenate([want[0], extra]), kind="stable")
         both = (np.concatenate([want[0], extra])[order], np.concatenate([want[1].astype(np.uint32), extra_c])[order])
-        assert same(on_device(e), both) and same(e.signature(), both)
+        assert same(signature_on_device(e), both) and same(e.signature(), both)
         assert e.signature_stats()[0] > 2**16
         with pytest.raises(nt.NtcError) as ei:
             plain.signature_device()
@@ -95,14 +75,14 @@ def test_engine_two_planes_and_sort_time(nt):
     with nt.Engine([21, 32], r_bits=R, s_bits=7, signature=True) as e:
         e.set_profiling(True)
         assert e.signature_sort_time() == 0.0
-        submit_slots(e)
+        submit_slots(e, sig_model.equal_reads())
         w21, w32 = sig_model.equal_model(21, "canonical", 7), sig_model.equal_model(32, "canonical", 7)
         assert not np.array_equal(w21[0], w32[0])
-        assert same(on_device(e, 0), w21) and same(on_device(e, 1), w32)
+        assert same(signature_on_device(e, 0), w21) and same(signature_on_device(e, 1), w32)
         assert e.signature_sort_time() > 0.0
         e.reset()
         assert e.signature_sort_time() == 0.0
-        assert on_device(e, 1)[0].size == 0
+        assert signature_on_device(e, 1)[0].size == 0
 
 
 # ---- compare ----

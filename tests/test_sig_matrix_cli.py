@@ -1,21 +1,18 @@
 """Host tests of `ntsig matrix` (ntcard_amd/csrc/ntsig_cli.cpp): what it checks before a device is looked for — its arguments, the files' headers, the
 reader's refusals.  The matrix itself is tests/test_sig_matrix_cli_gpu.py's."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import ntcard_amd as nt
+from support import NTSIG, run_cli
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTSIG = os.path.join(ROOT, "ntcard_amd", "bin", "ntsig")
 HEADER = dict(k=32, gap=0, strand=0, hpc=0, s_bits=7, mask="1" * 32)
 HASHES = np.arange(1, 11, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15 >> 8)
 
 
 def ntsig(*args):
-    return subprocess.run([NTSIG] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+    return run_cli(NTSIG, args, timeout=60)
 
 
 def test_matrix_without_a_file_is_a_usage_error():

@@ -1,22 +1,21 @@
 """`ntsig matrix` on the GPU (ntcard_amd/csrc/ntsig_cli.cpp): the TSV of all pairs, every off-diagonal value equal — as text — to what `ntsig compare` prints
 for that pair."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+from support import NTSIG, run_cli
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTSIG = os.path.join(ROOT, "ntcard_amd", "bin", "ntsig")
 HEADER = dict(k=32, gap=0, strand=0, hpc=0, s_bits=7, mask="1" * 32)
 
 
 def ntsig(*args):
-    return subprocess.run([NTSIG] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    return run_cli(NTSIG, args, timeout=120)
 
 
 @pytest.mark.parametrize("containment", [False, True])

@@ -16,6 +16,7 @@ import orc
 import sig_model
 from test_sig_device_gpu import dev32, dev64
 from test_sig_sort_gpu import KEY_SETS, check_sort
+from gpu_support import nt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -30,13 +31,6 @@ COMPARE_STRIDE = 8192 * 256  # sig_compare_kernel: entries of the shorter list p
 MAT_CHUNK, MAT_ITEMS = 4096, 2**18  # ntc_signature_matrix_device: entries per work item, work items per round
 SORT_TILE, SCAN_TILES = 4096, 256   # the sort: pairs per tile, tiles per turn of sort_scan_kernel
 DEFAULT_SLOTS = 2**16
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
 
 
 def frozen(*arrays):

@@ -5,6 +5,7 @@ import ctypes as C
 
 import numpy as np
 import pytest
+from gpu_support import nt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -14,13 +15,6 @@ ERR_ARG = -1
 ONE_LAUNCH = TILE = 4096
 SIZES = [0, 1, 2, 63, 64, 65, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 8191, 8192, 8193, 16383, 16384, 16385, 70001, 2**20 + 1]
 SET_SIZES = [ONE_LAUNCH - 1, ONE_LAUNCH, ONE_LAUNCH + 1, 70001]  # TILE +- 1 are the same three
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
 
 
 def u64(n, seed):

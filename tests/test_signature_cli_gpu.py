@@ -1,23 +1,19 @@
 """`ntcard --signature` and bin/ntsig (include/ntcard_hip.h: NTC_FLAG_SIGNATURE): the .sig file beside a .hist holds exactly the model's pairs
 (tests/sig_model.py), the .hist and the messages are those of a run without the option, and ntsig compares two runs."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import sig_model
-import strand_model as sm
 import ntcard_amd as nt
+from support import GOLD, NTCARD, NTSIG, run_cli, small_reads
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTCARD = os.path.join(ROOT, "ntcard_amd", "bin", "ntcard")
-NTSIG = os.path.join(ROOT, "ntcard_amd", "bin", "ntsig")
-FASTQ = os.path.join(sm.GOLD, "reads_small.fq.gz")
+FASTQ = os.path.join(GOLD, "reads_small.fq.gz")
 
 
 def run(cmd, cwd):
-    return subprocess.run([str(c) for c in cmd], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    return run_cli(cmd[0], cmd[1:], cwd=cwd, timeout=600)
 
 
 def without_runtime(text):
@@ -37,7 +33,7 @@ def test_the_option_needs_a_prefix(tmp_path):
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
     d = tmp_path_factory.mktemp("sig_cli")
-    reads = sm.small_reads()
+    reads = small_reads()
     assert len(reads) == 5000
     (d / "half.fq").write_bytes(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, s, b"I" * len(s)) for i, s in enumerate(reads[:2500])))
     out = {}

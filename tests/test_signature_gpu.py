@@ -8,11 +8,11 @@ import functools
 import numpy as np
 import pytest
 
-import hpc_model as hm
 import orc
 import sig_model
 import strand_model as sm
 from test_hpc_gpu import MASK
+from gpu_support import device_slots, nt, on_device, submit_slots  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,29 +22,8 @@ R = 14
 ERR_ARG, ERR_STATE = -1, -4
 
 
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
-
-
 def reads():
     return list(sig_model.equal_reads())
-
-
-@functools.lru_cache(maxsize=None)
-def device_slots(L=150, stride=152):
-    rs = reads()
-    a = np.full((len(rs), stride), ord("A"), dtype=np.uint8)
-    for i, r in enumerate(rs):
-        a[i, :L] = np.frombuffer(r, dtype=np.uint8)
-    return torch.from_numpy(np.concatenate([a.reshape(-1), np.full(16, ord("A"), np.uint8)])).cuda(), len(rs), L, stride
-
-
-def submit_slots(e):
-    d, n, L, stride = device_slots()
-    e.submit_device(d.data_ptr(), n, L, stride)
 
 
 @functools.lru_cache(maxsize=None)
@@ -62,8 +41,8 @@ def test_basic(nt):
     want = sig_model.equal_model(32, "canonical", 7)
     assert want[0].size == 593 and int(want[1].sum()) == 593
     with nt.Engine([32], r_bits=R, s_bits=7, signature=True) as e, nt.Engine([32], r_bits=R, s_bits=7) as plain:
-        submit_slots(e)
-        submit_slots(plain)
+        submit_slots(e, sig_model.equal_reads())
+        submit_slots(plain, sig_model.equal_reads())
         assert e.signature_size() == 593
         assert same_sig(e.signature(), want)
         tc, ph, f1 = e.finish(counters=True)
@@ -98,9 +77,9 @@ def test_growth_from_64_slots(nt, monkeypatch, log_entries):
         monkeypatch.setenv("NTC_SIG_LOG_ENTRIES", str(log_entries))
     with nt.Engine([32], r_bits=R, s_bits=2, signature=True) as e:
         assert e.signature_stats() == (64, 0)
-        submit_slots(e)
+        submit_slots(e, sig_model.equal_reads())
         assert same_sig(e.signature(), want)
-        submit_slots(e)
+        submit_slots(e, sig_model.equal_reads())
         h, c = e.signature()
         assert np.array_equal(h, want[0]) and np.all(c == 2)
         slots, grows = e.signature_stats()
@@ -154,7 +133,7 @@ def test_fused_k_list(nt):
     assert all(m[0].size > 10000 for m in models)
     assert all(not np.array_equal(models[i][0], models[j][0]) for i in range(4) for j in range(i))
     with nt.Engine(list(kl), r_bits=R, s_bits=2, signature=True) as e:
-        submit_slots(e)
+        submit_slots(e, sig_model.equal_reads())
         for pl in range(4):
             assert same_sig(e.signature(pl), models[pl]), kl[pl]
         tc, _, f1 = e.finish(counters=True)
@@ -167,7 +146,7 @@ def test_k12_counts_up_to_three(nt):
     want = sig_model.equal_model(12, "canonical", 2)
     assert (int(want[1].sum()), want[0].size, int(want[1].max())) == (22622, 22482, 3)
     with nt.Engine([12], r_bits=R, s_bits=2, signature=True) as e:
-        submit_slots(e)
+        submit_slots(e, sig_model.equal_reads())
         assert same_sig(e.signature(), want)
 
 
@@ -209,7 +188,7 @@ def test_forms(nt, name):
 def test_fused_k_list_of_one_strand(nt):
     """K1's row <true, 0, 10, false, false, true, true> (profiles/k1_variants.txt), which no other test dispatches: a fused k list on a forward engine, 130 reads in
     row slots (two full waves and a partial one) — every plane's pairs against the model, the counters against strand_model"""
-    d, _, L, stride = device_slots()
+    d, _, L, stride = device_slots(sig_model.equal_reads(), 150, 152)
     rs, klist = reads()[:130], [64, 96]
     with nt.Engine(klist, r_bits=R, s_bits=4, strand="forward", signature=True) as e:
         e.submit_device(d.data_ptr(), len(rs), L, stride)
@@ -294,10 +273,10 @@ def test_long_device_takes_the_gather_route(nt):
     _, seqs = long_set()
     want = sig_model.model(seqs, 32, "canonical", 3)
     assert int(want[1].sum()) > 800
-    d = torch.from_numpy(np.frombuffer(b"##" + b"".join(seqs) + b"#", dtype=np.uint8).copy()).cuda()
+    d, offs = on_device(seqs, lead=2)
     with nt.Engine([32], r_bits=R, s_bits=7, signature=True) as e7, nt.Engine([32], r_bits=R, s_bits=3, signature=True) as e:
         for eng in (e7, e):
-            eng.submit_long_device(d.data_ptr(), hm.offsets_of(list(seqs), 2))
+            eng.submit_long_device(d.data_ptr(), offs)
             assert eng.long_stats() == (0, 0)
         assert same_sig(e.signature(), want)
         assert same_sig(e7.signature(), sig_model.model(seqs, 32, "canonical", 7))
@@ -359,7 +338,7 @@ def test_inject_then_submit_adds_up(nt):
     extra = np.array([3, int(want[0][10]), int(want[0][10]), int(want[0][-1])], dtype=np.uint64)
     with nt.Engine([32], r_bits=R, s_bits=7, signature=True) as e:
         e.signature_inject(extra)
-        submit_slots(e)
+        submit_slots(e, sig_model.equal_reads())
         h, c = e.signature()
         wc = want[1].copy()
         wc[10] += 2
@@ -372,15 +351,15 @@ def test_reset_empties(nt, monkeypatch):
     monkeypatch.setenv("NTC_SIG_SLOTS", "128")
     want = sig_model.equal_model(32, "canonical", 7)
     with nt.Engine([32], r_bits=R, s_bits=7, signature=True) as e:
-        submit_slots(e)
+        submit_slots(e, sig_model.equal_reads())
         e.reset()  # (with the values still in the log)
         assert e.signature_size() == 0 and e.signature_stats() == (128, 0)
-        submit_slots(e)
+        submit_slots(e, sig_model.equal_reads())
         assert same_sig(e.signature(), want)
         assert e.signature_stats()[1] >= 4
         e.reset()
         assert e.signature()[0].size == 0 and e.signature_stats() == (128, 0)
-        submit_slots(e)
+        submit_slots(e, sig_model.equal_reads())
         assert same_sig(e.signature(), want)
 
 

@@ -1,8 +1,6 @@
 """Host tests of signatures (include/ntcard_hip.h: NTC_FLAG_SIGNATURE): the flag's validation before a device is looked for, ntc_signature_compare against
 np.intersect1d, the signature file's write / read round trip, bin/ntsig, and the model of tests/sig_model.py against the real reference's hashes."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,31 +10,10 @@ import sig_model
 import strand_model as sm
 from ntcard_amd import _abi
 import ntcard_amd as nt
+from support import NTSIG, abi_config, created, run_cli, sampled
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTSIG = os.path.join(ROOT, "ntcard_amd", "bin", "ntsig")
-ERR_ARG, ERR_DEVICE = -1, -2
+ERR_ARG = -1
 SIG, FWD, REV, STRAND_TILED, HPC = 16384, 512, 1024, 4096, 8192
-
-
-def cfg(flags, k=(32,)):
-    arr = (C.c_uint32 * len(k))(*k)
-    c = _abi.NtcConfig(n_k=len(k), k=C.cast(arr, C.POINTER(C.c_uint32)), gap=0, r_bits=14, s_bits=7, device=0, flags=flags)
-    c._keep = arr
-    return c
-
-
-def no_gpu():
-    import torch
-    return not torch.cuda.is_available()
-
-
-def created(rc, h, L):
-    """the call got past its argument checks: on a machine without a GPU it fails at the device probe, with one it makes an engine"""
-    if h:
-        L.ntc_destroy(h)
-    assert rc == (ERR_DEVICE if no_gpu() else 0), (rc, L.ntc_last_error())
-    return True
 
 
 # ---- the flag ----
@@ -50,7 +27,7 @@ def test_the_constant():
 def test_create_takes_the_flag_beside_every_compatible_one(beside):
     L = _abi.lib()
     h = C.c_void_p()
-    assert created(L.ntc_create(C.byref(cfg(SIG | beside)), C.byref(h)), h, L)
+    assert created(L.ntc_create(C.byref(abi_config(flags=SIG | beside)), C.byref(h)), h, L)
 
 
 def test_create_seeded_takes_the_flag():
@@ -64,7 +41,7 @@ def test_create_seeded_takes_the_flag():
 def test_the_simple_kernel_is_refused_beside_the_flag():
     L = _abi.lib()
     h = C.c_void_p()
-    assert L.ntc_create(C.byref(cfg(SIG | 1)), C.byref(h)) == ERR_ARG and not h
+    assert L.ntc_create(C.byref(abi_config(flags=SIG | 1)), C.byref(h)) == ERR_ARG and not h
     assert b"NTC_FLAG_SIGNATURE" in L.ntc_last_error()
     c = _abi.NtcConfig(n_k=0, k=None, gap=0, r_bits=14, s_bits=7, device=0, flags=SIG | 1)
     seeds = (C.c_char_p * 1)(b"1111111")
@@ -75,9 +52,9 @@ def test_the_retired_bits_stay_refused_beside_the_flag():
     L = _abi.lib()
     h = C.c_void_p()
     for bit in (4, 256, 2048, 1 << 20):
-        assert L.ntc_create(C.byref(cfg(SIG | bit)), C.byref(h)) == ERR_ARG and b"unknown flag" in L.ntc_last_error()
-    assert L.ntc_create(C.byref(cfg(SIG | FWD | REV)), C.byref(h)) == ERR_ARG
-    assert L.ntc_create(C.byref(cfg(SIG | STRAND_TILED)), C.byref(h)) == ERR_ARG
+        assert L.ntc_create(C.byref(abi_config(flags=SIG | bit)), C.byref(h)) == ERR_ARG and b"unknown flag" in L.ntc_last_error()
+    assert L.ntc_create(C.byref(abi_config(flags=SIG | FWD | REV)), C.byref(h)) == ERR_ARG
+    assert L.ntc_create(C.byref(abi_config(flags=SIG | STRAND_TILED)), C.byref(h)) == ERR_ARG
 
 
 @pytest.mark.parametrize("flags", [SIG, SIG | FWD, SIG | HPC])
@@ -218,7 +195,7 @@ def test_file_errors(tmp_path):
 
 
 def ntsig(*args):
-    return subprocess.run([NTSIG] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+    return run_cli(NTSIG, args, timeout=60)
 
 
 def test_ntsig_info_and_compare(tmp_path):
@@ -258,13 +235,13 @@ def test_ntsig_usage_and_bad_files(tmp_path):
 # ---- the model ----
 def test_sampled_is_ntcomp():
     s = 7
-    yes0, yes1 = np.uint64(1) << np.uint64(63 - s), np.uint64((1 << (s - 1)) - 1) << np.uint64(64 - s)
+    yes0, yes1 = np.uint64(1 << 56), np.uint64(63 << 57)  # s = 7: the top bits 0000 0001 and 0111 111
     h = u64([int(yes0), int(yes0) | 12345, int(yes1), int(yes1) | 99, 0, 1, 2**64 - 1, int(yes0) << 1, int(yes0) >> 1])
-    assert sig_model.sampled(h, s).tolist() == [True, True, True, True, False, False, False, False, False]
+    assert sampled(h, s).tolist() == [True, True, True, True, False, False, False, False, False]
     # against ntComp as the oracle runs it: a value is sampled iff it lands in t_Counter
     v = sig_model.values(list(sig_model.equal_reads())[:40], 32)
     tc, f1 = sm.sketch_of([(v, v)], sm.FORWARD, 14, s)
-    assert int(tc.sum()) == int(sig_model.sampled(v, s).sum()) > 0 and f1[0] == v.size
+    assert int(tc.sum()) == int(sampled(v, s).sum()) > 0 and f1[0] == v.size
 
 
 def test_the_tables_of_the_issue():

@@ -4,36 +4,20 @@ inputs tell the strands apart), through every submit path and update mode, plus 
 import functools
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import orc
 import strand_model as sm
+from gpu_support import nt  # noqa: F401
+from support import GOLD, NTCARD, run_cli, to_slots
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTCARD = os.path.join(ROOT, "ntcard_amd", "bin", "ntcard")
-GOLD = os.path.join(ROOT, "tests", "golden")
 ONE = [("forward", sm.FORWARD), ("reverse", sm.REVERSE)]
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
-
-
-def to_slots(reads, stride):
-    buf = np.full(len(reads) * stride + 16, ord("A"), dtype=np.uint8)
-    for i, r in enumerate(reads):
-        buf[i * stride: i * stride + len(r)] = np.frombuffer(r, dtype=np.uint8)
-    return buf
 
 
 def make(nt, masks, gap, **kw):
@@ -269,10 +253,6 @@ def test_merges_and_log_round_trips(nt):
         assert sum(counts) == int(want[0].astype(np.int64).sum()) and np.array_equal(tc, want[0])
 
 
-def run_cli(args, cwd):
-    return subprocess.run([NTCARD] + args, cwd=cwd, capture_output=True, timeout=600)
-
-
 def test_cli_strand_outputs_match_the_model(tmp_path):
     src = os.path.join(GOLD, "reads_small.fq.gz")
     reads = sm.small_reads()
@@ -283,7 +263,7 @@ def test_cli_strand_outputs_match_the_model(tmp_path):
         for sname, strand in ONE:
             for f in tmp_path.glob("x_*"):
                 f.unlink()
-            r = run_cli(args + ["--strand=" + sname, "-p", "x", src], tmp_path)
+            r = run_cli(NTCARD, args + ["--strand=" + sname, "-p", "x", src], cwd=tmp_path, timeout=600)
             assert r.returncode == 0, r.stderr
             tc, f1 = sm.sketch_of(vals, strand, 27, 7)
             for mi, fn in enumerate(files):
@@ -294,7 +274,7 @@ def test_cli_strand_canonical_is_the_committed_reference_output(tmp_path):
     src = os.path.join(GOLD, "reads_small.fq.gz")
     for args, gold in ((["-k", "12", "-g", "2"], {"out_k12.hist": "ref_k12_g2__out_k12.hist"}), (["-k", "32"], {"out_k32.hist": "ref_k32__out_k32.hist"}),
                        (["-k", "16,24,32,48"], {"out_k%d.hist" % k: "ref_multi__out_k%d.hist" % k for k in (16, 24, 32, 48)})):
-        r = run_cli(args + ["--strand=canonical", "-p", "out", src], tmp_path)
+        r = run_cli(NTCARD, args + ["--strand=canonical", "-p", "out", src], cwd=tmp_path, timeout=600)
         assert r.returncode == 0, r.stderr
         for fn, g in gold.items():
             assert (tmp_path / fn).read_bytes() == open(os.path.join(GOLD, g), "rb").read(), (args, fn)

@@ -5,7 +5,6 @@ import ctypes as C
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,9 +12,7 @@ import pytest
 import orc
 import strand_model as sm
 from ntcard_amd import _abi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTCARD = os.path.join(ROOT, "ntcard_amd", "bin", "ntcard")
+from support import NTCARD, ROOT, abi_config, run_cli
 HEADER = os.path.join(ROOT, "include", "ntcard_hip.h")
 ERR_ARG = -1
 FWD, REV = 512, 1024
@@ -88,15 +85,6 @@ def test_the_gpu_tests_inputs_tell_the_strands_apart(name, masks, gap, s_bits):
 
 
 # ---- ABI ----
-def cfg(k=(32,), gap=0, flags=0):
-    c = _abi.NtcConfig(r_bits=20, s_bits=7, device=0, gap=gap, flags=flags)
-    arr = (C.c_uint32 * len(k))(*k)
-    c.n_k = len(k)
-    c.k = C.cast(arr, C.POINTER(C.c_uint32))
-    c._arr = arr
-    return c
-
-
 def test_header_and_library_carry_the_strand_additions():
     text = open(HEADER).read()
     assert re.search(r"#define\s+NTC_FLAG_STRAND_FORWARD\s+512u", text) and re.search(r"#define\s+NTC_FLAG_STRAND_REVERSE\s+1024u", text)
@@ -118,7 +106,7 @@ def test_both_strand_flags_are_refused_before_the_device(seeded):
         arr = (C.c_char_p * 1)(b"110011")
         rc = L.ntc_create_seeded(C.byref(c), 1, arr, C.byref(h))
     else:
-        rc = L.ntc_create(C.byref(cfg(flags=FWD | REV)), C.byref(h))
+        rc = L.ntc_create(C.byref(abi_config(r_bits=20, flags=FWD | REV)), C.byref(h))
     assert rc == ERR_ARG and not h.value
     assert b"device" not in L.ntc_last_error() and b"STRAND" in L.ntc_last_error()
 
@@ -141,7 +129,7 @@ def test_a_single_strand_flag_reaches_the_device_probe(flags, k, gap):
         pytest.skip("a device is present (the GPU tests create strand engines)")
     L = _abi.lib()
     h = C.c_void_p()
-    assert L.ntc_create(C.byref(cfg(k=k, gap=gap, flags=flags)), C.byref(h)) == -2 and not h.value
+    assert L.ntc_create(C.byref(abi_config(r_bits=20, k=k, gap=gap, flags=flags)), C.byref(h)) == -2 and not h.value
     c = _abi.NtcConfig(r_bits=20, s_bits=7, device=0, flags=flags & ~1)
     arr = (C.c_char_p * 2)(b"110011", b"1111")
     assert L.ntc_create_seeded(C.byref(c), 2, arr, C.byref(h)) == -2 and not h.value
@@ -151,7 +139,7 @@ def test_the_retired_flag_bits_stay_refused():
     L = _abi.lib()
     h = C.c_void_p()
     for bit in (4, 256, 1 << 20, 2048):
-        assert L.ntc_create(C.byref(cfg(flags=FWD | bit)), C.byref(h)) == ERR_ARG and b"unknown flag" in L.ntc_last_error()
+        assert L.ntc_create(C.byref(abi_config(r_bits=20, flags=FWD | bit)), C.byref(h)) == ERR_ARG and b"unknown flag" in L.ntc_last_error()
 
 
 def test_python_strand_keyword_is_checked_before_the_library():
@@ -167,19 +155,15 @@ def test_python_strand_keyword_is_checked_before_the_library():
 
 
 # ---- CLI ----
-def run_cli(args, cwd):
-    return subprocess.run([NTCARD] + args, cwd=cwd, capture_output=True, text=True, timeout=60)
-
-
 @pytest.mark.parametrize("args", [["--strand=sideways", "-k", "32"], ["--strand=", "-k", "32"], ["--strand=Forward", "--seed=1101"],
                                   ["-k", "12", "-g", "2", "--strand", "both"]])
 def test_cli_strand_argument_errors(tmp_path, args):
-    r = run_cli(args + ["-p", "x", "x.fq"], tmp_path)  # (x.fq does not exist: the usage error comes before any file is opened)
+    r = run_cli(NTCARD, args + ["-p", "x", "x.fq"], cwd=tmp_path, text=True)  # (x.fq does not exist: the usage error comes before any file is opened)
     assert r.returncode == 1
     assert "--strand" in r.stderr and "--help" in r.stderr
     assert not list(tmp_path.glob("x_*"))
 
 
 def test_cli_help_lists_strand():
-    r = run_cli(["--help"], ROOT)
+    r = run_cli(NTCARD, ["--help"], cwd=ROOT, text=True)
     assert r.returncode == 0 and "--strand=canonical|forward|reverse" in r.stderr

@@ -4,36 +4,23 @@ that is meant to run on the tiled pair is created with NTC_FLAG_REQUIRE_TILED, s
 import functools
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import k1f_cases as kc
 import strand_model as sm
+from gpu_support import nt, on_device  # noqa: F401
+from support import GOLD, NTCARD, assert_same_sketch, gap_mask, run_cli
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NTCARD = os.path.join(ROOT, "ntcard_amd", "bin", "ntcard")
-GOLD = os.path.join(ROOT, "tests", "golden")
 ONE = [("forward", sm.FORWARD), ("reverse", sm.REVERSE)]
 BOTH = pytest.mark.parametrize("sname,strand", ONE, ids=[s for s, _ in ONE])
 R_BITS = sm.R_BITS
 KS = [12, 17, 25, 32]
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
-
-
-def seed_mask(k, gap):
-    return "1" * ((k - gap) // 2) + "0" * gap + "1" * (k - gap - (k - gap) // 2)
 
 
 # ---- read sets (fixed seeds) and the model's per-read values, computed once per (set, mask) ----
@@ -68,12 +55,6 @@ def flags_of(nt, sname, extra=0, require=True):
     return (nt.FLAG_STRAND_FORWARD if sname == "forward" else nt.FLAG_STRAND_REVERSE) | nt.FLAG_STRAND_TILED | (nt.FLAG_REQUIRE_TILED if require else 0) | extra
 
 
-def same(got, exp, what):
-    tc, _, f1 = got
-    assert np.array_equal(f1, exp[1]), (what, f1, exp[1])
-    assert np.array_equal(tc, exp[0]), (what, int((tc != exp[0]).sum()))
-
-
 def tiled(e, reads, L, keep):
     t = torch.from_numpy(__import__("ntcard_amd").tile_reads(list(reads), L)).cuda()
     keep.append(t)
@@ -89,7 +70,7 @@ def test_require_tiled_accepts_a_strand_engine_with_the_flag(nt):
         sflag = nt.FLAG_STRAND_FORWARD if sname == "forward" else nt.FLAG_STRAND_REVERSE
         with nt.Engine([32], r_bits=18, s_bits=7, flags=nt.FLAG_REQUIRE_TILED | sflag | nt.FLAG_STRAND_TILED) as e:
             e.submit_tiled_device(t.data_ptr(), len(reads), 150)
-            same(e.finish(counters=True), want(reads, ["1" * 32], strand, r_bits=18), sname)
+            assert_same_sketch(e.finish(counters=True), want(reads, ["1" * 32], strand, r_bits=18), sname)
         with nt.Engine([32], r_bits=18, s_bits=7, flags=nt.FLAG_REQUIRE_TILED | sflag) as e:  # without the flag: as before
             with pytest.raises(nt.NtcError, match="REQUIRE_TILED") as ei:
                 e.submit_tiled_device(t.data_ptr(), len(reads), 150)
@@ -107,7 +88,7 @@ def test_equal_length_batches(nt, k, sname, strand):
         keep = []
         with nt.Engine([k], r_bits=R_BITS, s_bits=7, flags=flags_of(nt, sname)) as e:
             tiled(e, reads, L, keep)
-            same(e.finish(counters=True), want(reads, ["1" * k], strand), (k, L, sname))
+            assert_same_sketch(e.finish(counters=True), want(reads, ["1" * k], strand), (k, L, sname))
 
 
 @BOTH
@@ -117,7 +98,7 @@ def test_batch_sizes(nt, n, sname, strand):
     keep = []
     with nt.Engine([32], r_bits=R_BITS, s_bits=7, flags=flags_of(nt, sname)) as e:
         tiled(e, reads, 47, keep)
-        same(e.finish(counters=True), want(equal_reads(47, 4100), ["1" * 32], strand, upto=n), (n, sname))
+        assert_same_sketch(e.finish(counters=True), want(equal_reads(47, 4100), ["1" * 32], strand, upto=n), (n, sname))
 
 
 def all_routes(nt, e, equal, ragged, keep):
@@ -145,7 +126,7 @@ def test_every_tiled_route_and_update_mode(nt, mode, k, sname, strand):
     keep = []
     with nt.Engine([k], r_bits=R_BITS, s_bits=7, flags=flags_of(nt, sname, extra)) as e:
         all_routes(nt, e, equal, ragged, keep)
-        same(e.finish(counters=True), (3 * we[0] + 3 * wr[0], 3 * we[1] + 3 * wr[1]), (mode, k, sname))
+        assert_same_sketch(e.finish(counters=True), (3 * we[0] + 3 * wr[0], 3 * we[1] + 3 * wr[1]), (mode, k, sname))
 
 
 # ---- 3: sBits and gaps ----
@@ -156,19 +137,19 @@ def test_larger_s_bits(nt, s_bits, sname, strand):
     keep = []
     with nt.Engine([32], r_bits=12, s_bits=s_bits, flags=flags_of(nt, sname)) as e:
         tiled(e, reads, 150, keep)
-        same(e.finish(counters=True), want(reads, ["1" * 32], strand, s_bits=s_bits, r_bits=12), (s_bits, sname))
+        assert_same_sketch(e.finish(counters=True), want(reads, ["1" * 32], strand, s_bits=s_bits, r_bits=12), (s_bits, sname))
 
 
 @BOTH
 @pytest.mark.parametrize("k,gap", [(12, 2), (32, 8)])
 def test_gap_seeds(nt, k, gap, sname, strand):
     equal, ragged = equal_reads(150), ragged_reads()
-    m = seed_mask(k, gap)
+    m = gap_mask(k, gap)
     we, wr = want(equal, [m], strand), want(ragged, [m], strand)
     keep = []
     with nt.Engine([k], gap=gap, r_bits=R_BITS, s_bits=7, flags=flags_of(nt, sname)) as e:
         all_routes(nt, e, equal, ragged, keep)
-        same(e.finish(counters=True), (3 * we[0] + 3 * wr[0], 3 * we[1] + 3 * wr[1]), (k, gap, sname))
+        assert_same_sketch(e.finish(counters=True), (3 * we[0] + 3 * wr[0], 3 * we[1] + 3 * wr[1]), (k, gap, sname))
 
 
 # ---- 4: K1f's slow path ----
@@ -180,7 +161,7 @@ def test_slow_path_by_a_table_slot_byte(nt, v, sname, strand):
     t = torch.from_numpy(kc.tile(case.reads, case.read_len)).cuda()
     with nt.Engine([case.k], r_bits=R_BITS, s_bits=case.s_bits, flags=flags_of(nt, sname)) as e:
         e.submit_tiled_device(t.data_ptr(), len(case.reads), case.read_len)
-        same(e.finish(counters=True), exp, (v, sname))
+        assert_same_sketch(e.finish(counters=True), exp, (v, sname))
 
 
 @BOTH
@@ -196,7 +177,7 @@ def test_dense_suspects(nt, monkeypatch, sus_cap, sname, strand):
     for log_entries in (0, 1 << 18):
         with nt.Engine([case.k], r_bits=R_BITS, s_bits=case.s_bits, flags=flags_of(nt, sname), log_entries=log_entries) as e:
             e.submit_tiled_device(t.data_ptr(), len(case.reads), case.read_len)
-            same(e.finish(counters=True), exp, (sus_cap, log_entries, sname))
+            assert_same_sketch(e.finish(counters=True), exp, (sus_cap, log_entries, sname))
 
 
 # ---- 5: identities ----
@@ -237,7 +218,7 @@ def test_merge_devices_ignores_the_flag(nt):
         es[0].submit_reads(list(reads[0::2]))
         es[1].submit_reads(list(reads[1::2]))
         nt.merge_devices(es)
-        same(es[0].finish(counters=True), exp, "merge")
+        assert_same_sketch(es[0].finish(counters=True), exp, "merge")
     finally:
         for e in es:
             e.close()
@@ -251,7 +232,7 @@ def test_partly_qualifying_list_stays_on_the_general_kernel(nt, sname, strand):
     keep = []
     with nt.Engine([32, 64], r_bits=R_BITS, s_bits=7, flags=flags_of(nt, sname, require=False)) as e:
         tiled(e, reads, 150, keep)
-        same(e.finish(counters=True), exp, sname)
+        assert_same_sketch(e.finish(counters=True), exp, sname)
     with nt.Engine([32, 64], r_bits=R_BITS, s_bits=7, flags=flags_of(nt, sname)) as e:
         with pytest.raises(nt.NtcError, match="REQUIRE_TILED"):
             tiled(e, reads, 150, keep)
@@ -277,18 +258,15 @@ def long_seqs():
 def test_long_sequences_are_cut_for_a_strand_engine_with_the_flag(nt, kl):
     seqs = long_seqs()
     PL = 48 + 16
-    offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
-    offs[0] = 3
-    offs[1:] = 3 + np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    d = torch.from_numpy(np.frombuffer(b"###" + b"".join(seqs) + b"#", dtype=np.uint8).copy()).cuda()
+    d, offs = on_device(seqs)
     exp = want(seqs, ["1" * k for k in kl], sm.FORWARD)
     with nt.Engine(list(kl), r_bits=R_BITS, s_bits=7, flags=flags_of(nt, "forward")) as e:
         e.submit_long_device(d.data_ptr(), offs, PL)
-        same(e.finish(counters=True), exp, kl)
+        assert_same_sketch(e.finish(counters=True), exp, kl)
         assert e.long_stats() == (sum(nt.long_plan(max(kl), PL, len(s))[0] for s in seqs), len(seqs))
     with nt.Engine(list(kl), r_bits=R_BITS, s_bits=7, strand="forward") as e:  # without the flag: gathered whole, as before
         e.submit_long_device(d.data_ptr(), offs, PL)
-        same(e.finish(counters=True), exp, kl)
+        assert_same_sketch(e.finish(counters=True), exp, kl)
         assert e.long_stats() == (0, 0)
 
 
@@ -297,11 +275,11 @@ def test_cli_strand_kernels_write_the_same_bytes(tmp_path):
     src = os.path.join(GOLD, "reads_small.fq.gz")
     out = {}
     for kern in ("tiled", "general"):
-        r = subprocess.run([NTCARD, "-k", "32", "--strand=forward", "--strand-kernel=" + kern, "-p", kern, src], cwd=tmp_path, capture_output=True, timeout=600)
+        r = run_cli(NTCARD, ["-k", "32", "--strand=forward", "--strand-kernel=" + kern, "-p", kern, src], cwd=tmp_path, timeout=600)
         assert r.returncode == 0, r.stderr
         out[kern] = (tmp_path / (kern + "_k32.hist")).read_bytes()
     assert out["tiled"] == out["general"] and len(out["tiled"]) > 1000
-    r = subprocess.run([NTCARD, "-k", "32", "--strand=forward", "-p", "dflt", src], cwd=tmp_path, capture_output=True, timeout=600)  # the default is tiled
+    r = run_cli(NTCARD, ["-k", "32", "--strand=forward", "-p", "dflt", src], cwd=tmp_path, timeout=600)  # the default is tiled
     assert r.returncode == 0 and (tmp_path / "dflt_k32.hist").read_bytes() == out["tiled"]
-    r = subprocess.run([NTCARD, "-k", "32", "--strand-kernel=sideways", "-p", "x", src], cwd=tmp_path, capture_output=True, timeout=60)
+    r = run_cli(NTCARD, ["-k", "32", "--strand-kernel=sideways", "-p", "x", src], cwd=tmp_path, timeout=60)
     assert r.returncode == 1 and b"--strand-kernel" in r.stderr

@@ -14,19 +14,14 @@ import pytest
 
 import orc
 from devview import DevArray as _DevArray
+from gpu_support import nt  # noqa: F401
+from support import assert_same_sketch, oracle_counts, random_reads, tile_array
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fullsize")
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
 
 
 def gen_host(n, L, dist, genome_len=200_000, seed=1):
@@ -53,11 +48,8 @@ def run_tiled(nt, reads, L, k=32, r_bits=18, s_bits=7, flags=0, pieces=1, log_en
 
 
 def check(nt, reads, L, **kw):
-    tc, ph, f1 = run_tiled(nt, reads, L, **kw)
-    oc, of1 = orc.sketch_reads(reads, [kw.get("k", 32)], 0, kw.get("r_bits", 18), kw.get("s_bits", 7))
-    assert np.array_equal(f1, of1), (f1, of1)
-    assert np.array_equal(tc, oc)
-    assert np.array_equal(ph[0], orc.value_hist(oc[0], kw.get("r_bits", 18)))
+    want = orc.sketch_reads(reads, [kw.get("k", 32)], 0, kw.get("r_bits", 18), kw.get("s_bits", 7))
+    assert_same_sketch(run_tiled(nt, reads, L, **kw), want, (len(reads), L, kw), hist_r_bits=kw.get("r_bits", 18))
 
 
 def test_tiled_generator_matches_oracle(nt):
@@ -81,9 +73,7 @@ def test_tiled_kernel_non_acgt_bytes(nt, n, L, p_bad):
     """N / IUPAC / punctuation anywhere, lower case and U as bases, all-N and poly-A reads: F1 and every counter"""
     rng = np.random.default_rng(int(p_bad * 1000) + L)
     alpha = np.frombuffer(b"ACGTacgtUuNnRYKMBDHVSW.-*@`bf", dtype=np.uint8)  # '@', '`', 'B', 'b', 'F', 'f' differ from a base letter in one bit
-    arr = alpha[rng.integers(0, 4, size=(n, L))]
-    bad = rng.random((n, L)) < p_bad
-    arr = np.where(bad, alpha[rng.integers(4, len(alpha), size=(n, L))], arr).astype(np.uint8)
+    arr = random_reads(rng, n, L, p_bad, alpha)
     reads = [arr[i].tobytes() for i in range(n)]
     reads[0] = b"A" * L
     reads[1] = b"N" * L
@@ -126,8 +116,7 @@ def test_first_apply_writes_and_later_ones_add(nt):
     rng = np.random.default_rng(6)
     alpha = np.frombuffer(b"ACGTacgtNn", dtype=np.uint8)
     n, L = 40_000, 150
-    arr = alpha[rng.integers(0, 4, size=(n, L))]
-    arr = np.where(rng.random((n, L)) < 0.004, alpha[rng.integers(4, len(alpha), size=(n, L))], arr).astype(np.uint8)
+    arr = random_reads(rng, n, L, 0.004, alpha)
     reads = [arr[i].tobytes() for i in range(n)]
     parts = [reads[:15_000], reads[15_000:22_000], reads[22_000:]]
     tiles = [torch.from_numpy(nt.tile_reads(p, L)).cuda() for p in parts]
@@ -171,11 +160,8 @@ def test_tiled_kernel_every_k(nt, k):
     """K1h is generated for k = 12 .. 32 (one assembly body per k): reads of
     exactly k and k + 1 bases, 97 and 150 bp, non-ACGTU bytes, sBits 7 / 8 / 11"""
     rng = np.random.default_rng(k)
-    alpha = np.frombuffer(b"ACGTacgtUuNnRYKM.-*", dtype=np.uint8)
     for n, L, s_bits, p_bad in ((3000, 150, 7, 0.002), (2100, k, 7, 0.0), (2500, k + 1, 8, 0.01), (2049, 97, 11, 0.0)):
-        arr = alpha[rng.integers(0, 4, size=(n, L))]
-        if p_bad:
-            arr = np.where(rng.random((n, L)) < p_bad, alpha[rng.integers(4, len(alpha), size=(n, L))], arr).astype(np.uint8)
+        arr = random_reads(rng, n, L, p_bad)
         check(nt, [arr[i].tobytes() for i in range(n)], L, k=k, s_bits=s_bits)
 
 
@@ -189,10 +175,7 @@ def test_tiled_kernel_random_shapes(nt, seed):
     n = int(rng.choice([1, 63, 2047, 2048, 2049, 5000, 9000]))
     s_bits = int(rng.choice([7, 8, 9, 12]))
     p_bad = float(rng.choice([0.0, 0.001, 0.02]))
-    alpha = np.frombuffer(b"ACGTacgtUuNnRYKM.-*", dtype=np.uint8)
-    arr = alpha[rng.integers(0, 4, size=(n, L))]
-    if p_bad:
-        arr = np.where(rng.random((n, L)) < p_bad, alpha[rng.integers(4, len(alpha), size=(n, L))], arr).astype(np.uint8)
+    arr = random_reads(rng, n, L, p_bad)
     check(nt, [arr[i].tobytes() for i in range(n)], L, k=k, s_bits=s_bits)
 
 
@@ -210,34 +193,18 @@ def test_tiled_kernel_k_lists(nt):
         assert np.array_equal(f1, of1) and np.array_equal(tc, oc), klist
 
 
-def tile_array(arr):
-    """(n, L) uint8 array of reads -> tiled layout (numpy only: millions of reads)"""
-    n, L = arr.shape
-    C16, ntl = (L + 15) // 16, (n + 2047) // 2048
-    a = np.full((ntl * 2048, C16 * 16), ord("A"), dtype=np.uint8)
-    a[:n, :L] = arr
-    return np.ascontiguousarray(a.reshape(ntl, 2048, C16, 16).transpose(0, 2, 1, 3)).reshape(-1)
-
-
 @pytest.mark.parametrize("L,k", [(12, 12), (14, 12), (16, 16), (16, 12), (20, 16), (33, 16), (47, 12), (32, 32), (40, 25)])
 def test_tiled_many_tiles_per_team_short_reads(nt, L, k):
     """3.2 M reads of 1 .. 3 chunks with 1.5 % non-ACGTU bytes: every team of waves walks >= 3 tiles whose blocks are (nearly) whole
     tiles, so the packer runs several TILES ahead of the resolvers — the dirty-piece queue's tile tags, the suspects' tile tags
     and the ring-slot phase (seq * C) % 5 all wrap within one launch.  F1 and every counter vs the oracle."""
     n = 3_200_000
-    rng = np.random.default_rng(L * 100 + k)
-    alpha = np.frombuffer(b"ACGTacgtUuNnRYKM.-*", dtype=np.uint8)
-    arr = alpha[rng.integers(0, 4, size=(n, L))]
-    arr = np.where(rng.random((n, L)) < 0.015, alpha[rng.integers(4, len(alpha), size=(n, L))], arr).astype(np.uint8)
+    arr = random_reads(np.random.default_rng(L * 100 + k), n, L, 0.015)
     t = torch.from_numpy(tile_array(arr)).cuda()
     with nt.Engine([k], r_bits=20, s_bits=7, flags=nt.FLAG_REQUIRE_TILED | VARIANT_FLAGS) as e:
         e.submit_tiled_device(t.data_ptr(), n, L)
         tc, ph, f1 = e.finish(counters=True)
-    counters = np.zeros((1, 2, 1 << 20), dtype=np.uint16)
-    offs = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
-    of1 = orc.sketch_update(counters, np.ascontiguousarray(arr).reshape(-1), offs, [k], 0, 20, 7)
-    assert np.array_equal(f1, of1), (f1, of1)
-    assert np.array_equal(tc, counters)
+    assert_same_sketch((tc, f1), oracle_counts(arr, [k], 0, 20, 7), (L, k))
 
 
 def test_tiled_layout_falls_back_for_other_configurations(nt):
@@ -380,12 +347,10 @@ def test_tiled_deferred_fixups(nt):
     all of them (blockIdx.y = the launch).  Eleven batches of different sizes and read lengths with non-ACGTU bytes: the ninth forces a K1f in
     mid-run; one batch holds reference-table slot bytes (its launch alone takes K1f's slow path); a flush in between; more batches behind it"""
     rng = np.random.default_rng(77)
-    alpha = np.frombuffer(b"ACGTacgtUuNnRYKM.-*", dtype=np.uint8)
     parts, bufs = [], []
     for i in range(11):
         n, L = 30_000 + 4000 * i, (150, 97, 64)[i % 3]
-        arr = alpha[rng.integers(0, 4, size=(n, L))]
-        arr = np.where(rng.random((n, L)) < 0.003, alpha[rng.integers(4, len(alpha), size=(n, L))], arr).astype(np.uint8)
+        arr = random_reads(rng, n, L, 0.003)
         if i == 4:
             arr[rng.integers(0, n, size=50), rng.integers(0, L, size=50)] = np.array([1, 3, 4, 5, 7], dtype=np.uint8)[rng.integers(0, 5, size=50)]
         parts.append(arr)
@@ -419,9 +384,7 @@ def test_tiled_reference_table_slot_bytes_and_suspect_overflow(nt):
         check(nt, [arr[i].tobytes() for i in range(n)], L)
     dense = np.frombuffer(b"ACGTN", dtype=np.uint8)[rng.integers(0, 5, size=(400_000, 64))].astype(np.uint8)
     t = torch.from_numpy(tile_array(dense)).cuda()
-    counters = np.zeros((1, 2, 1 << 20), dtype=np.uint16)
-    offs = np.arange(dense.shape[0] + 1, dtype=np.uint64) * np.uint64(64)
-    of1 = orc.sketch_update(counters, np.ascontiguousarray(dense).reshape(-1), offs, [32], 0, 20, 7)
+    counters, of1 = oracle_counts(dense, [32], 0, 20, 7)
     for cap in ("", "64"):  # the engine's own list (sized for every candidate: fast path), then a short one: the launch overflows -> slow path
         if cap:
             os.environ["NTC_K1H_SUS_CAP"] = cap
@@ -438,20 +401,12 @@ def test_tiled_reference_table_slot_bytes_and_suspect_overflow(nt):
 def test_tiled_spaced_seed_k12_gap2(nt, n, L, p_bad, s_bits):
     """stRead with ntcard's -g seed (ntcard.cpp:160-171,407-413) through the tiled layout: K1h's (k = 12, gap = 2) variant, K1f with the
     spaced closed form (the last case overflows the suspect list: slow path)"""
-    rng = np.random.default_rng(n + L)
-    alpha = np.frombuffer(b"ACGTacgtUuNnRYKM.-*", dtype=np.uint8)
-    arr = alpha[rng.integers(0, 4, size=(n, L))]
-    if p_bad:
-        arr = np.where(rng.random((n, L)) < p_bad, alpha[rng.integers(4, len(alpha), size=(n, L))], arr).astype(np.uint8)
+    arr = random_reads(np.random.default_rng(n + L), n, L, p_bad)
     t = torch.from_numpy(tile_array(arr)).cuda()
     with nt.Engine([12], gap=2, r_bits=18, s_bits=s_bits, flags=nt.FLAG_REQUIRE_TILED) as e:
         e.submit_tiled_device(t.data_ptr(), n, L)
         tc, ph, f1 = e.finish(counters=True)
-    counters = np.zeros((1, 2, 1 << 18), dtype=np.uint16)
-    offs = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
-    of1 = orc.sketch_update(counters, np.ascontiguousarray(arr).reshape(-1), offs, [12], 2, 18, s_bits)
-    assert np.array_equal(f1, of1), (f1, of1)
-    assert np.array_equal(tc, counters)
+    assert_same_sketch((tc, f1), oracle_counts(arr, [12], 2, 18, s_bits), (n, L, s_bits))
 
 
 def _ragged_reads(rng, n, lo, hi, p_bad=0.0):

@@ -9,11 +9,15 @@ plan_k1h.  Every test asserts that its input is beyond the threshold it is there
 
 Every batch of 70 or more reads begins with the nine directed reads of limits_model.DIRECTED; the slot byte among them sends the launch down K1f's
 slow path, so the *_fast_path tests run the same batches without it."""
+import functools
+
 import numpy as np
 import pytest
 
 import limits_model as lm
 import orc
+from gpu_support import nt  # noqa: F401
+from support import assert_same_sketch, oracle_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -21,13 +25,6 @@ torch = pytest.importorskip("torch")
 
 LENGTHS = (1009, 4097, 32769, 65520, 65535)
 OLD_MAX = 1008  # the longest tiled read of the rest of the suite (the default piece of test_long_gpu.py)
-
-
-@pytest.fixture(scope="module")
-def nt():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device (run on the MI355X box)"
-    import ntcard_amd
-    return ntcard_amd
 
 
 @pytest.fixture(scope="module")
@@ -44,19 +41,7 @@ def upload(buf, tiles):
     return buf.data_ptr()
 
 
-def oracle(arr, klist, gap=0, r_bits=16, s_bits=7):
-    n, L = arr.shape
-    counters = np.zeros((len(klist), 2, 1 << r_bits), dtype=np.uint16)
-    f1 = orc.sketch_update(counters, np.ascontiguousarray(arr).reshape(-1), np.arange(n + 1, dtype=np.uint64) * np.uint64(L), list(klist), gap, r_bits, s_bits)
-    return counters, f1
-
-
-def same(got, want, what):
-    (tc, f1), (oc, of1) = got, want
-    print(what, "F1", f1.tolist(), "oracle", of1.tolist(), "counters off", int((tc != oc).sum()))
-    assert of1.all(), "the oracle counted nothing"
-    assert np.array_equal(f1, of1), (what, f1, of1)
-    assert np.array_equal(tc, oc), what
+same = functools.partial(assert_same_sketch, nonempty=True)  # (the oracle counted something in every plane)
 
 
 def count_equal(nt, buf, arr, klist, gap=0, r_bits=16, s_bits=7, **kw):
@@ -109,7 +94,7 @@ def test_equal_length(nt, tile_buf, L, n, k):
         assert L <= 4097 and (n + 2047) // 2048 == 2 and n % 2048 == 1
     arr = batch(n, L, k)
     r_bits = 14 if k == 12 else 16
-    same(count_equal(nt, tile_buf, arr, [k], r_bits=r_bits), oracle(arr, [k], r_bits=r_bits), (L, n, k))
+    same(count_equal(nt, tile_buf, arr, [k], r_bits=r_bits), oracle_counts(arr, [k], r_bits=r_bits), (L, n, k))
 
 
 @pytest.mark.parametrize("L,k", [(L, k) for L in (4097, 65520, 65535) for k in (12, 32)])
@@ -118,7 +103,7 @@ def test_equal_length_fast_path(nt, tile_buf, L, k):
     window starts, their dirty marks in three chunks — decide the counts"""
     assert_reaches(L, k)
     arr = batch(70, L, k, slot_byte=False)
-    same(count_equal(nt, tile_buf, arr, [k], r_bits=15), oracle(arr, [k], r_bits=15), (L, k))
+    same(count_equal(nt, tile_buf, arr, [k], r_bits=15), oracle_counts(arr, [k], r_bits=15), (L, k))
 
 
 @pytest.mark.parametrize("L,k,gap", [(L, k, g) for L in (4097, 65535) for k, g in ((12, 2), (32, 8))])
@@ -126,7 +111,7 @@ def test_tiled_gap_seeds(nt, tile_buf, L, k, gap):
     """ntcard's -g seeds that have a tiled kernel (stRead, ntcard.cpp:160-171)"""
     assert_reaches(L, k)
     arr = batch(70, L, k, seed=1)
-    same(count_equal(nt, tile_buf, arr, [k], gap=gap, r_bits=14), oracle(arr, [k], gap=gap, r_bits=14), (L, k, gap))
+    same(count_equal(nt, tile_buf, arr, [k], gap=gap, r_bits=14), oracle_counts(arr, [k], gap=gap, r_bits=14), (L, k, gap))
 
 
 @pytest.mark.parametrize("L", [4097, 65520])
@@ -136,7 +121,7 @@ def test_k_list(nt, tile_buf, L):
     for k in kl:
         assert_reaches(L, k)
     arr = batch(70, L, max(kl), seed=2)
-    same(count_equal(nt, tile_buf, arr, kl, r_bits=15), oracle(arr, kl, r_bits=15), (L, kl))
+    same(count_equal(nt, tile_buf, arr, kl, r_bits=15), oracle_counts(arr, kl, r_bits=15), (L, kl))
 
 
 def test_larger_s_bits_at_65520(nt, tile_buf):
@@ -144,7 +129,7 @@ def test_larger_s_bits_at_65520(nt, tile_buf):
     L, k = 65520, 32
     assert_reaches(L, k)
     arr = batch(70, L, k, seed=3)
-    same(count_equal(nt, tile_buf, arr, [k], r_bits=16, s_bits=11), oracle(arr, [k], r_bits=16, s_bits=11), "sBits 11")
+    same(count_equal(nt, tile_buf, arr, [k], r_bits=16, s_bits=11), oracle_counts(arr, [k], r_bits=16, s_bits=11), "sBits 11")
 
 
 def test_forward_strand_at_65535(nt, tile_buf):
@@ -155,13 +140,13 @@ def test_forward_strand_at_65535(nt, tile_buf):
     got = count_equal(nt, tile_buf, arr, [k], r_bits=14, strand="forward", strand_tiled=True)
     want = lm.forward_sketch(arr, k, 14, 7)
     same(got, want, "forward")
-    assert not np.array_equal(want[0], oracle(arr, [k], r_bits=14)[0])  # (the input tells the strands apart)
+    assert not np.array_equal(want[0], oracle_counts(arr, [k], r_bits=14)[0])  # (the input tells the strands apart)
 
 
 def ragged_reads(rng, n, C, k, slot_byte):
     """n reads of C chunks whose tails cycle through 1 .. 16, a few non-base bytes, an N on the last base, on the first base of the last window and on the
     first byte of the last chunk of three of them; slot_byte: a byte 1 (a base to the reference) in the last chunk of a fourth"""
-    arr = lm.random_reads(rng, n, 16 * C)
+    arr = lm.random_reads(rng, n, 16 * C, lm.P_BAD)
     lens = 16 * (C - 1) + 1 + (np.arange(n) % 16)
     arr[0, lens[0] - 1] = lm.N
     arr[1, lens[1] - k] = lm.N
