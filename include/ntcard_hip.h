@@ -360,6 +360,27 @@ int ntc_signature_sort_device(int32_t device, void *stream, void *d_keys_u64, vo
 int ntc_signature_compare_device(int32_t device, void *stream, const void *d_a_u64, const void *d_ca_u32, uint64_t na, const void *d_b_u64,
                                  const void *d_cb_u32, uint64_t nb, uint64_t *n_common, uint64_t *min_sum);
 int ntc_signature_matrix_device(int32_t device, void *stream, uint32_t n_sigs, const void *const *d_hashes_u64, const uint64_t *n, uint64_t *common_out);
+/* Gather, another engine-less device tool (synchronous, frees its scratch): which references are in a query, and how much of it does each explain on its
+ * own — the greedy minimum-set-cover decomposition of FracMinHash tools.  The query: nq strictly ascending DEVICE hashes with optional uint32 counts
+ * (NULL: 1 each); d_refs_u64: a HOST array of n_refs DEVICE lists (1 <= n_refs <= 1024; list i has n[i] strictly ascending hashes, NULL allowed where
+ * n[i] == 0).  Every query entry starts live.  A round counts, for every reference, the live query entries it holds (unique); the reference with the most
+ * wins, the lowest index among equals; the run stops, with nothing more reported, when that count is below `threshold` (a number of hashes; 0 is taken as
+ * 1), when rows_cap rows are written or after n_refs rounds; else the round writes rows[r] = {ref, common = |Q n R_ref| on the whole query, unique,
+ * unique_weight = the sum of the query's counts over those live entries} and the entries stop being live.  *n_rows = the rows written, *unassigned = the
+ * query entries still live after the last reported row, *unassigned_weight = the sum of their counts (both may be NULL).  So a reference given twice is
+ * reported once, one inside an earlier pick never, the rows' unique values do not increase and they add up, with *unassigned, to nq.  All results are
+ * integer sums: exact and the same on every run.
+ * NTC_ERR_ARG before the device is touched: n_refs outside 1 .. 1024, nq or an n[i] >= 2^32, NULL n_rows, NULL rows with rows_cap != 0, a NULL list with a
+ * length.  Ascent of the query and of every reference is checked once on the device: NTC_ERR_ARG names the list ("the query", or the reference's index)
+ * and an offending entry.  NTC_ERR_MEMORY when the scratch cannot be had (a byte per query entry, 4 B per common hash of every reference with the
+ * query).  On any error every output is left alone.  rows_cap == 0 is legal: *n_rows = 0 and the whole query is unassigned. */
+typedef struct {
+    uint32_t ref, reserved;     /* index into d_refs_u64; 0 */
+    uint64_t common, unique, unique_weight;
+} ntc_gather_row;
+int ntc_signature_gather_device(int32_t device, void *stream, const void *d_query_u64, const void *d_query_counts_u32, uint64_t nq, uint32_t n_refs,
+                                const void *const *d_refs_u64, const uint64_t *n, uint64_t threshold, ntc_gather_row *rows, uint32_t rows_cap,
+                                uint32_t *n_rows, uint64_t *unassigned, uint64_t *unassigned_weight);
 /* A signature FILE (`ntcard --signature`, bin/ntsig): little-endian; the 8 bytes "NTCSIG1\0", uint32 k, gap, strand, hpc, s_bits, mask_len, uint64 n, the mask
  * (mask_len bytes '0' / '1', all '1' for plain k; zero-padded to a multiple of 8), uint64 hashes[n], uint32 counts[n].  The header says how the file was
  * counted: two files compare only when they agree in everything but n.  Pure host functions.

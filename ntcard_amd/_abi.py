@@ -24,7 +24,19 @@ ABI_SYMBOLS = [
     "ntc_signature_size", "ntc_signature", "ntc_signature_inject", "ntc_signature_inject_device", "ntc_signature_compare", "ntc_signature_stats",
     "ntc_signature_time", "ntc_signature_header", "ntc_signature_write", "ntc_signature_read",
     "ntc_signature_device", "ntc_signature_sort_time", "ntc_signature_sort_device", "ntc_signature_compare_device", "ntc_signature_matrix_device",
+    "ntc_signature_gather_device",
 ]
+
+
+class NtcGatherRow(C.Structure):
+    """ntc_gather_row"""
+    _fields_ = [
+        ("ref", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("common", C.c_uint64),
+        ("unique", C.c_uint64),
+        ("unique_weight", C.c_uint64),
+    ]
 
 
 class NtcSigHeader(C.Structure):
@@ -136,6 +148,8 @@ def lib():
     L.ntc_signature_sort_device.argtypes = [i32, p, p, p, u64]
     L.ntc_signature_compare_device.argtypes = [i32, p, p, p, u64, p, p, u64, C.POINTER(u64), C.POINTER(u64)]
     L.ntc_signature_matrix_device.argtypes = [i32, p, u32, C.POINTER(p), C.POINTER(u64), p]
+    L.ntc_signature_gather_device.argtypes = [i32, p, p, p, u64, u32, C.POINTER(p), C.POINTER(u64), u64, C.POINTER(NtcGatherRow), u32, C.POINTER(u32),
+                                              C.POINTER(u64), C.POINTER(u64)]
     L.ntc_sync.argtypes = [p]
     L.ntc_finish.argtypes = [p, p, p, p]
     L.ntc_merge_counters.argtypes = [p, p, p]

@@ -2,6 +2,8 @@
 //   ntsig info F.sig            the header: how the file was counted, and how many values it holds
 //   ntsig compare A.sig B.sig   |A n B|, Jaccard and both containments — refused when the headers differ in anything but n
 //   ntsig matrix [--containment] A.sig B.sig ...   all pairs at once, as a TSV: Jaccard, or the containment of the row's file in the column's
+//   ntsig gather [--threshold N] QUERY.sig REF.sig ...   which references are in the query and what each explains on its own, as a TSV in pick order
+//                               (ntc_signature_gather_device; headers are checked like matrix's, before a device is looked for)
 // info and compare are host code over the library's reader and ntc_signature_compare and need no GPU; matrix reads every header first (files counted
 // differently are refused before a device is looked for), then uploads the hash lists and calls ntc_signature_matrix_device.
 #include <hip/hip_runtime_api.h>
@@ -124,9 +126,71 @@ int matrix(int n_files, char** files, bool containment)
 	return EXIT_SUCCESS;
 }
 
+// hipMalloc + copy of n values of `bytes` bytes each from a file (n == 0: nothing, *out stays null)
+bool to_device(void** out, const void* host, uint64_t n, size_t bytes, const char* file)
+{
+	if (n == 0) return true;
+	hipError_t rc = hipMalloc(out, n * bytes);
+	if (rc == hipSuccess) rc = hipMemcpy(*out, host, n * bytes, hipMemcpyHostToDevice);
+	if (rc == hipSuccess) return true;
+	std::fprintf(stderr, "ntsig: cannot bring the %llu values of %s to the device: %s\n", (unsigned long long)n, file, hipGetErrorString(rc));
+	return false;
+}
+
+double ratio(uint64_t num, uint64_t den) { return den ? (double)num / (double)den : 0.0; }
+
+int gather(const char* query_file, int n_refs, char** ref_files, uint64_t threshold)
+{
+	Sig query;
+	std::vector<Sig> refs(n_refs);
+	if (!load(query_file, query, false)) return EXIT_FAILURE;
+	for (int i = 0; i < n_refs; ++i)
+		if (!load(ref_files[i], refs[i], false)) return EXIT_FAILURE;
+	for (int i = 0; i < n_refs; ++i)
+		if (const char* d = differs_in(query.h, refs[i].h)) return refuse(query_file, ref_files[i], d);
+	if (!load(query_file, query, true)) return EXIT_FAILURE;
+	for (int i = 0; i < n_refs; ++i)
+		if (!load(ref_files[i], refs[i], true)) return EXIT_FAILURE;
+	// the library says whether a device can be used (as matrix asks it)
+	uint64_t none = 0, probe = 0;
+	const void* null_list = nullptr;
+	if (ntc_signature_matrix_device(0, nullptr, 1, &null_list, &none, &probe) != 0) {
+		std::fprintf(stderr, "ntsig: %s\n", ntc_last_error());
+		return EXIT_FAILURE;
+	}
+	DeviceLists d; // [references][query hashes][query counts]
+	d.p.assign(n_refs + 2, nullptr);
+	std::vector<uint64_t> n(n_refs);
+	const uint64_t nq = query.h.n;
+	if (!to_device(&d.p[n_refs], query.hashes.data(), nq, 8, query_file) || !to_device(&d.p[n_refs + 1], query.counts.data(), nq, 4, query_file)) return EXIT_FAILURE;
+	for (int i = 0; i < n_refs; ++i) {
+		n[i] = refs[i].h.n;
+		if (!to_device(&d.p[i], refs[i].hashes.data(), n[i], 8, ref_files[i])) return EXIT_FAILURE;
+	}
+	std::vector<ntc_gather_row> rows(n_refs);
+	uint32_t n_rows = 0;
+	uint64_t rest = 0, rest_weight = 0, total_weight = 0;
+	if (ntc_signature_gather_device(0, nullptr, d.p[n_refs], d.p[n_refs + 1], nq, (uint32_t)n_refs, d.p.data(), n.data(), threshold, rows.data(), (uint32_t)n_refs, &n_rows,
+	                                &rest, &rest_weight) != 0) {
+		std::fprintf(stderr, "ntsig: %s\n", ntc_last_error());
+		return EXIT_FAILURE;
+	}
+	for (uint32_t c : query.counts)
+		total_weight += c;
+	std::printf("rank\treference\tcommon\tunique\tf_orig_query\tf_unique_query\tf_unique_weighted\tf_match\tavg_abund\n");
+	for (uint32_t r = 0; r < n_rows; ++r) {
+		const ntc_gather_row& g = rows[r];
+		std::printf("%u\t%s\t%llu\t%llu\t%.6f\t%.6f\t%.6f\t%.6f\t%.6f\n", r + 1, ref_files[g.ref], (unsigned long long)g.common, (unsigned long long)g.unique, ratio(g.common, nq),
+		            ratio(g.unique, nq), ratio(g.unique_weight, total_weight), ratio(g.unique, n[g.ref]), ratio(g.unique_weight, g.unique));
+	}
+	std::printf("unassigned\t-\t-\t%llu\t-\t%.6f\t%.6f\t-\t%.6f\n", (unsigned long long)rest, ratio(rest, nq), ratio(rest_weight, total_weight), ratio(rest_weight, rest));
+	return EXIT_SUCCESS;
+}
+
 int usage()
 {
-	std::fprintf(stderr, "Usage: ntsig info F.sig\n       ntsig compare A.sig B.sig\n       ntsig matrix [--containment] A.sig B.sig ...\n");
+	std::fprintf(stderr, "Usage: ntsig info F.sig\n       ntsig compare A.sig B.sig\n       ntsig matrix [--containment] A.sig B.sig ...\n"
+	                     "       ntsig gather [--threshold N] QUERY.sig REF.sig ...\n");
 	return EXIT_FAILURE;
 }
 
@@ -162,6 +226,20 @@ int main(int argc, char** argv)
 		const int first = containment ? 3 : 2;
 		if (argc - first < 1 || argc - first > 1024) return usage();
 		return matrix(argc - first, argv + first, containment);
+	}
+	if (cmd == "gather") {
+		int first = 2;
+		uint64_t threshold = 1;
+		if (argc > 2 && std::strcmp(argv[2], "--threshold") == 0) {
+			char* end = nullptr;
+			if (argc < 4 || argv[3][0] < '0' || argv[3][0] > '9') return usage();
+			threshold = std::strtoull(argv[3], &end, 10);
+			if (*end) return usage();
+			first = 4;
+		}
+		const int n_refs = argc - first - 1; // behind the query
+		if (n_refs < 1 || n_refs > 1024) return usage();
+		return gather(argv[first], n_refs, argv + first + 1, threshold);
 	}
 	return usage();
 }

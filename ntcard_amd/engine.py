@@ -459,6 +459,29 @@ def signature_matrix_device(ptrs, ns, device=0, stream=None):
     return out
 
 
+# ntc_gather_row as a structured array
+GATHER_ROW_DTYPE = np.dtype([("ref", np.uint32), ("reserved", np.uint32), ("common", np.uint64), ("unique", np.uint64), ("unique_weight", np.uint64)])
+
+
+def signature_gather_device(ptr_q, ptr_counts_q, nq, ptrs, ns, threshold=1, max_rows=None, device=0, stream=None):
+    """gather: the greedy decomposition of a device query (nq strictly ascending uint64 hashes; counts uint32, or None / 0: 1 each) over the device lists
+    ptrs[i] of ns[i] strictly ascending uint64 each -> (rows, unassigned, unassigned_weight).  rows: a structured array (GATHER_ROW_DTYPE) in pick order,
+    at most max_rows of them (None: as many as there are references); a round's pick is the reference with the most query entries no earlier pick took,
+    the lowest index among equals, and the run ends when that count falls below `threshold` hashes; synchronous (ntc_signature_gather_device)"""
+    assert len(ptrs) == len(ns)
+    k = len(ptrs)
+    cap = k if max_rows is None else int(max_rows)
+    arr = (C.c_void_p * max(k, 1))(*[C.c_void_p(int(p)) if p else None for p in ptrs])
+    n = (C.c_uint64 * max(k, 1))(*[int(x) for x in ns])
+    rows = np.zeros(max(cap, 1), dtype=GATHER_ROW_DTYPE)
+    n_rows, rest, rest_w = C.c_uint32(), C.c_uint64(), C.c_uint64()
+    check(_abi.lib().ntc_signature_gather_device(device, C.c_void_p(stream) if stream else None, C.c_void_p(ptr_q) if ptr_q else None,
+                                                 C.c_void_p(ptr_counts_q) if ptr_counts_q else None, int(nq), k, arr, n, int(threshold),
+                                                 rows.ctypes.data_as(C.POINTER(_abi.NtcGatherRow)) if cap else None, cap, C.byref(n_rows), C.byref(rest),
+                                                 C.byref(rest_w)))
+    return rows[:n_rows.value].copy(), rest.value, rest_w.value
+
+
 def signature_write(path, header, hashes, counts):
     """a signature file; header: dict(k, gap, strand, hpc, s_bits, mask) as Engine.signature_header() gives it (ntc_signature_write)"""
     hs = np.ascontiguousarray(hashes, dtype=np.uint64)
