@@ -1,8 +1,10 @@
 // ntc_engine.hpp — the engine behind the C ABI (include/ntcard_hip.h): its state, the owners of its device resources and the functions its
 // translation units share.  ntc_plan.hip: launch geometry and policy (no HIP calls); ntc_launch.hip: everything that enters the engine's stream;
 // ntc_submit.hip: host packing, length bins, the staging pool; ntc_lifecycle.hip: create .. finish and the queries; ntc_merge.hip: multi-GPU merge
-// and log exchange; ntc_device_tools.hip: the entry points that need no engine (those of signatures — sort, compare, matrix — sit with their kernels in
-// ntc_sig_sort.hip).
+// and log exchange; ntc_device_tools.hip: the entry points that need no engine.  Signatures: ntc_signature.hip: the container's kernels, the engine's
+// glue and the entry points that take an engine; those that need none sit with their kernels — ntc_sig_sort.hip: sort; ntc_sig_lists.hip: SigLists (lists on the
+// device, their ascent check), compare, matrix; ntc_sig_gather.hip: gather; ntc_sig_device.hpp is what these four share; ntc_sig_file.cpp: the signature file
+// format and the host compare, plain host C++ like ntc_estimator.cpp.
 //
 // Host-side mirror of the reference seam B2: ntc_create = the allocation/zeroing main() does (ntcard.cpp:433-439),
 // ntc_submit = a batch of ntRead/stRead calls (ntcard.cpp:147-171), ntc_finish = the state compEst reads (ntcard.cpp:237-247) + F1
@@ -23,7 +25,7 @@
 #include "../../include/ntcard_hip.h"
 #include "ntc_kernels.hpp"
 
-// sets ntc_last_error() and returns `code`: for the translation units outside ntc_eng (ntc_estimator.cpp)
+// sets ntc_last_error() and returns `code`: for the translation units outside ntc_eng (ntc_estimator.cpp, ntc_sig_file.cpp)
 int ntc_internal_fail(int code, const char* fmt, ...);
 
 namespace ntc_eng {

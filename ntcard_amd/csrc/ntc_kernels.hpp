@@ -260,7 +260,7 @@ struct SigTable {
 hipError_t launch_sig_insert(const SigTable& t, const unsigned long long* in_keys, const uint32_t* in_counts, uint64_t n, hipStream_t st);
 // the live pairs of a table, in slot order of arrival, to out_keys / out_counts (room for *live entries); *cursor (zeroed by the caller) counts them
 hipError_t launch_sig_compact(const SigTable& t, unsigned long long* out_keys, uint32_t* out_counts, unsigned long long* cursor, hipStream_t st);
-// ---- sort and compare of (u64 key, u32 value) pairs (ntc_sig_sort.hip) ----
+// ---- sort of (u64 key, u32 value) pairs (ntc_sig_sort.hip) ----
 // A stable LSD radix sort, ascending by key, n < 2^32; vals (and alt_vals) may be nullptr.  n <= sig_sort_one_launch(): one launch, in place, alt_* and aux
 // unused.  Otherwise the passes alternate between (keys, vals) and (alt_keys, alt_vals) — room for n each — with sig_sort_aux_bytes(n) bytes of aux, and
 // *in_alt says where the sorted pairs lie; the call waits for the stream once (it reads the digit histograms to skip the digits that do not tell any keys

@@ -17,7 +17,7 @@
 //            Each of them reads `done` first and leaves when it is set, so the host enqueues kGatherBatch rounds at a time and waits once per batch.
 //   rest     what is still live after the last reported row, and the sum of its counts.
 // No kernel waits on another workgroup; a launch reads what an earlier launch of the stream wrote.  Vector stores and plain C++ only.
-#include "ntc_engine.hpp"
+#include "ntc_sig_device.hpp"
 
 namespace ntc {
 
@@ -28,10 +28,8 @@ constexpr uint32_t kGatherLaneItems = kGatherChunk / 256u; // of them per lane
 constexpr uint32_t kGatherSearchItems = 1u << 18;  // search work items per launch
 constexpr uint32_t kGatherCountBlocks = 1024;      // grid cap of gather_count_kernel (it walks the rest of the items in a grid-stride loop)
 constexpr uint32_t kGatherClearBlocks = 1024;      // ... of gather_clear_kernel and gather_rest_kernel
-constexpr uint32_t kGatherAscentBlocks = 1024;     // ... of gather_ascent_kernel (per list)
 constexpr uint32_t kGatherBatch = 32;              // rounds enqueued between two waits of the host
 constexpr uint32_t kGatherMaxRefs = 1024;
-constexpr unsigned long long kGatherNoBad = ~0ull;
 
 // the words the round kernels share
 struct GatherState {
@@ -40,34 +38,6 @@ struct GatherState {
 	uint32_t n_rows; // rows written (= rounds that did not stop)
 	uint32_t pad;
 };
-
-__device__ __forceinline__ uint32_t gather_lanes_below(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
-
-// the first index >= x of the ascending list l[0 .. n) (any list: the search stays inside [0, n])
-__device__ __forceinline__ uint64_t gather_lower_bound(const unsigned long long* __restrict__ l, uint64_t n, unsigned long long x)
-{
-	uint64_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint64_t mid = lo + (hi - lo) / 2;
-		if (l[mid] < x)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-__device__ __forceinline__ unsigned long long gather_wave_sum(unsigned long long x)
-{
-	uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) {
-		const unsigned long long y = ((unsigned long long)(uint32_t)__shfl_xor((int)hi, o) << 32) | (uint32_t)__shfl_xor((int)lo, o);
-		x += y;
-		lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
-	}
-	return x;
-}
 
 // the list whose range of work items holds `item`: base[0 .. n_lists] ascending, base[0] = 0, item < base[n_lists] (lists without items are stepped over)
 __device__ __forceinline__ uint32_t gather_list_of(const unsigned long long* __restrict__ base, uint32_t n_lists, unsigned long long item)
@@ -81,17 +51,6 @@ __device__ __forceinline__ uint32_t gather_list_of(const unsigned long long* __r
 			hi = mid;
 	}
 	return lo;
-}
-
-// bad[list] = the smallest i >= 1 with a[i - 1] >= a[i] (kGatherNoBad: strictly ascending); blockIdx.y = the list.  (ntc_sig_sort.hip's sig_ascent_kernel is
-// local to that file: this is the same walk)
-__global__ __launch_bounds__(256) void gather_ascent_kernel(const unsigned long long* const* __restrict__ lists, const uint64_t* __restrict__ ns, unsigned long long* __restrict__ bad)
-{
-	const uint32_t li = blockIdx.y;
-	const unsigned long long* a = lists[li];
-	const uint64_t n = ns[li];
-	for (uint64_t i = 1 + (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
-		if (a[i - 1] >= a[i]) atomicMin(bad + li, (unsigned long long)i);
 }
 
 // a workgroup per work item first_item + blockIdx.x: kGatherChunk entries of the shorter of (reference, query) searched in the longer.  lists[n_refs] is the
@@ -121,7 +80,7 @@ __global__ __launch_bounds__(256) void gather_search_kernel(const unsigned long 
 		pos[t] = 0;
 		if (i < n_s) {
 			const unsigned long long x = s[i];
-			const uint64_t at = gather_lower_bound(l, n_l, x);
+			const uint64_t at = list_lower_bound(l, n_l, x);
 			if (at < n_l && l[at] == x) {
 				hit |= 1u << t;
 				pos[t] = (uint32_t)(by_query ? i : at); // (< nq < 2^32)
@@ -129,7 +88,7 @@ __global__ __launch_bounds__(256) void gather_search_kernel(const unsigned long 
 		}
 	}
 	const uint32_t lane = threadIdx.x & 63u;
-	const uint32_t wave_hits = (uint32_t)gather_wave_sum((unsigned long long)__popc(hit));
+	const uint32_t wave_hits = (uint32_t)wave_sum((unsigned long long)__popc(hit));
 	if (!kWrite) {
 		if (lane == 0u && wave_hits) atomicAdd(common + ref, (unsigned long long)wave_hits);
 		return;
@@ -144,7 +103,7 @@ __global__ __launch_bounds__(256) void gather_search_kernel(const unsigned long 
 	for (uint32_t t = 0; t < kGatherLaneItems; ++t) {
 		const bool mine = ((hit >> t) & 1u) != 0u;
 		const uint64_t m = __builtin_amdgcn_ballot_w64(mine);
-		if (mine && at + gather_lanes_below(m) < room) out[at + gather_lanes_below(m)] = pos[t];
+		if (mine && at + lanes_below(m) < room) out[at + lanes_below(m)] = pos[t];
 		at += (uint32_t)__popcll(m);
 	}
 }
@@ -171,8 +130,8 @@ __global__ __launch_bounds__(256) void gather_count_kernel(const GatherState* __
 			u += alive;
 			w += counts ? (unsigned long long)alive * counts[p] : (unsigned long long)alive;
 		}
-		u = (uint32_t)gather_wave_sum(u);
-		w = gather_wave_sum(w);
+		u = (uint32_t)wave_sum(u);
+		w = wave_sum(w);
 		if ((threadIdx.x & 63u) == 0u && u) {
 			atomicAdd(unique + ref, u);
 			atomicAdd(weight + ref, w);
@@ -245,15 +204,13 @@ __global__ __launch_bounds__(256) void gather_rest_kernel(const unsigned char* _
 		u += alive;
 		w += counts ? alive * counts[i] : alive;
 	}
-	u = gather_wave_sum(u);
-	w = gather_wave_sum(w);
+	u = wave_sum(u);
+	w = wave_sum(w);
 	if ((threadIdx.x & 63u) == 0u && u) {
 		atomicAdd(out, u);
 		atomicAdd(out + 1, w);
 	}
 }
-
-unsigned capped_blocks(uint64_t n, uint32_t cap) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cap)); }
 
 } // namespace
 
@@ -281,98 +238,91 @@ int ntc_signature_gather_device(int32_t device, void* stream, const void* d_quer
 	const size_t nr = n_refs, nl = nr + 1; // the lists: the references, then the query
 	const uint32_t row_limit = std::min(rows_cap, n_refs);
 	if (threshold == 0) threshold = 1;
-	// device words (8 B each): [lists nl][lengths nl][first bad entry nl][search item base nl][common nr][count item base nl][start nr][weight nr][rest 2]
-	const size_t o_len = nl, o_bad = 2 * nl, o_sbase = 3 * nl, o_common = 4 * nl, o_cbase = o_common + nr, o_start = o_cbase + nl, o_weight = o_start + nr,
-	             o_rest = o_weight + nr, n_words = o_rest + 2;
-	// device words (4 B each): [cursor nr][unique nr]
-	DevBuf<unsigned long long> d_w;
-	DevBuf<uint32_t> d_u;
+	// the lists' extra words (8 B each): [common nr][search item base nl][count item base nl][start nr][weight nr][rest 2]
+	const size_t x_common = 0, x_sbase = nr, x_cbase = x_sbase + nl, x_start = x_cbase + nl, x_weight = x_start + nr, x_rest = x_weight + nr, n_extra = x_rest + 2;
+	SigLists lists;
+	DevBuf<uint32_t> d_u; // device words (4 B each): [cursor nr][unique nr]
 	DevBuf<GatherState> d_state;
 	DevBuf<ntc_gather_row> d_rows;
 	DevBuf<unsigned char> d_live;
 	DevBuf<uint32_t> d_hits;
-	const size_t fixed = n_words * 8 + 2 * nr * 4 + sizeof(GatherState) + (size_t)std::max(row_limit, 1u) * sizeof(ntc_gather_row) + (size_t)std::max<uint64_t>(nq, 1);
-	if (!d_w.reserve(n_words * 8) || !d_u.reserve(2 * nr * 4) || !d_state.reserve(sizeof(GatherState)) ||
+	if (!lists.reserve(nl, n_extra, n_extra) || !d_u.reserve(2 * nr * 4) || !d_state.reserve(sizeof(GatherState)) ||
 	    !d_rows.reserve((size_t)std::max(row_limit, 1u) * sizeof(ntc_gather_row)) || !d_live.reserve((size_t)std::max<uint64_t>(nq, 1))) {
 		(void)hipGetLastError();
-		return fail(NTC_ERR_MEMORY, "ntc_signature_gather_device: cannot allocate %zu B of scratch on device; nothing was written", fixed);
+		return fail(NTC_ERR_MEMORY, "ntc_signature_gather_device: cannot allocate %zu B of scratch on device; nothing was written",
+		            lists.bytes() + 2 * nr * 4 + sizeof(GatherState) + (size_t)std::max(row_limit, 1u) * sizeof(ntc_gather_row) + (size_t)std::max<uint64_t>(nq, 1));
 	}
-	std::vector<unsigned long long> w(n_words, 0ull);
-	uint64_t longest = nq;
+	unsigned long long* const x = lists.extra();
 	unsigned long long search_items = 0;
 	for (size_t i = 0; i < nl; ++i) {
 		const uint64_t len = i < nr ? n[i] : nq;
-		w[i] = (unsigned long long)(uintptr_t)(i < nr ? d_refs_u64[i] : d_query_u64);
-		w[o_len + i] = len;
-		w[o_bad + i] = kGatherNoBad;
-		w[o_sbase + i] = search_items;
+		lists.set(i, i < nr ? d_refs_u64[i] : d_query_u64, len);
+		x[x_sbase + i] = search_items;
 		if (i < nr) search_items += (std::min(len, nq) + kGatherChunk - 1) / kGatherChunk;
-		longest = std::max(longest, len);
 	}
-	HIP_TRY(hipMemcpyAsync(d_w, w.data(), n_words * 8, hipMemcpyHostToDevice, st));
+	HIP_TRY(lists.start(st));
 	HIP_TRY(hipMemsetAsync(d_u, 0, 2 * nr * 4, st));
 	HIP_TRY(hipMemsetAsync(d_state, 0, sizeof(GatherState), st));
 	if (nq) HIP_TRY(hipMemsetAsync(d_live, 1, nq, st));
-	const unsigned long long* const* d_lists = (const unsigned long long* const*)d_w.get();
-	const uint64_t* d_ns = (const uint64_t*)(d_w.get() + o_len);
+	unsigned long long* const d_common = lists.d_extra() + x_common;
+	unsigned long long* const d_start = lists.d_extra() + x_start;
+	unsigned long long* const d_weight = lists.d_extra() + x_weight;
 	uint32_t* d_cursor = d_u.get();
 	uint32_t* d_unique = d_u.get() + nr;
 	const uint32_t* d_counts = (const uint32_t*)d_query_counts_u32;
-	if (longest > 1) hipLaunchKernelGGL(gather_ascent_kernel, dim3(capped_blocks(longest, kGatherAscentBlocks), (unsigned)nl), dim3(256), 0, st, d_lists, d_ns, d_w.get() + o_bad);
 	// pass 1 of the search.  An unsorted list makes its searches miss or hit at random but keeps them inside the list, and its result is thrown away below
 	auto search = [&](bool write) {
 		for (unsigned long long first = 0; first < search_items; first += kGatherSearchItems) {
 			const unsigned grid = (unsigned)std::min<unsigned long long>(kGatherSearchItems, search_items - first);
 			if (write)
-				hipLaunchKernelGGL(gather_search_kernel<true>, dim3(grid), dim3(256), 0, st, d_lists, d_ns, n_refs, d_w.get() + o_sbase, first, d_w.get() + o_common,
-				                   d_w.get() + o_start, d_cursor, d_hits.get());
+				hipLaunchKernelGGL(gather_search_kernel<true>, dim3(grid), dim3(256), 0, st, lists.d_ptrs(), lists.d_lens(), n_refs, lists.d_extra() + x_sbase, first, d_common, d_start,
+				                   d_cursor, d_hits.get());
 			else
-				hipLaunchKernelGGL(gather_search_kernel<false>, dim3(grid), dim3(256), 0, st, d_lists, d_ns, n_refs, d_w.get() + o_sbase, first, d_w.get() + o_common,
-				                   d_w.get() + o_start, d_cursor, (uint32_t*)nullptr);
+				hipLaunchKernelGGL(gather_search_kernel<false>, dim3(grid), dim3(256), 0, st, lists.d_ptrs(), lists.d_lens(), n_refs, lists.d_extra() + x_sbase, first, d_common, d_start,
+				                   d_cursor, (uint32_t*)nullptr);
 		}
 	};
 	search(false);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(w.data() + o_bad, d_w.get() + o_bad, nl * 8, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(w.data() + o_common, d_w.get() + o_common, nr * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(lists.read_back(st, nr)); // the bad entries and common[]
 	HIP_TRY(hipStreamSynchronize(st)); // the one wait of the search: every list is checked and every reference's hits are counted
-	if (w[o_bad + nr] != kGatherNoBad) return fail(NTC_ERR_ARG, "ntc_signature_gather_device: the query is not strictly ascending at entry %llu", w[o_bad + nr]);
+	if (lists.bad(nr) != kNoBad) return fail(NTC_ERR_ARG, "ntc_signature_gather_device: the query is not strictly ascending at entry %llu", lists.bad(nr));
 	for (size_t i = 0; i < nr; ++i)
-		if (w[o_bad + i] != kGatherNoBad) return fail(NTC_ERR_ARG, "ntc_signature_gather_device: reference %zu is not strictly ascending at entry %llu", i, w[o_bad + i]);
+		if (lists.bad(i) != kNoBad) return fail(NTC_ERR_ARG, "ntc_signature_gather_device: reference %zu is not strictly ascending at entry %llu", i, lists.bad(i));
 	unsigned long long total_hits = 0, count_items = 0, most_hits = 0;
 	for (size_t i = 0; i < nr; ++i) {
-		const unsigned long long c = w[o_common + i];
-		w[o_start + i] = total_hits;
-		w[o_cbase + i] = count_items;
+		const unsigned long long c = x[x_common + i];
+		x[x_start + i] = total_hits;
+		x[x_cbase + i] = count_items;
 		total_hits += c;
 		count_items += (c + kGatherChunk - 1) / kGatherChunk;
 		most_hits = std::max(most_hits, c);
 	}
-	w[o_cbase + nr] = count_items;
+	x[x_cbase + nr] = count_items;
 	if (!d_hits.reserve((size_t)std::max<unsigned long long>(total_hits, 1) * 4)) {
 		(void)hipGetLastError();
 		return fail(NTC_ERR_MEMORY, "ntc_signature_gather_device: cannot allocate %llu B for the hit lists on device; nothing was written", total_hits * 4);
 	}
-	HIP_TRY(hipMemcpyAsync(d_w.get() + o_cbase, w.data() + o_cbase, (nl + nr) * 8, hipMemcpyHostToDevice, st)); // the count items' base and the starts
+	HIP_TRY(hipMemcpyAsync(lists.d_extra() + x_cbase, x + x_cbase, (nl + nr) * 8, hipMemcpyHostToDevice, st)); // the count items' base and the starts
 	if (total_hits) HIP_TRY(hipMemsetAsync(d_hits, 0, (size_t)total_hits * 4, st)); // (pass 2 writes every entry; a list changed under the call leaves valid positions)
 	search(true);
 	HIP_TRY(hipGetLastError());
 	// the rounds: at most row_limit of them write a row and one more stops the run
 	GatherState state{};
 	const unsigned count_grid = (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>(count_items, kGatherCountBlocks));
-	const unsigned clear_grid = capped_blocks(most_hits, kGatherClearBlocks);
+	const unsigned clear_grid = capped_grid(most_hits, kGatherClearBlocks);
 	for (uint64_t enqueued = 0; !state.done;) {
 		const uint64_t batch = std::min<uint64_t>(kGatherBatch, (uint64_t)row_limit + 1 - enqueued);
 		if (batch == 0) return fail(NTC_ERR_DEVICE, "ntc_signature_gather_device: the rounds did not stop after %llu of them", (unsigned long long)enqueued);
 		for (uint64_t r = 0; r < batch; ++r) {
 			if (count_items)
-				hipLaunchKernelGGL(gather_count_kernel, dim3(count_grid), dim3(256), 0, st, (const GatherState*)d_state.get(), d_w.get() + o_cbase, n_refs, count_items,
-				                   d_w.get() + o_common, d_w.get() + o_start, (const uint32_t*)d_hits.get(), (const unsigned char*)d_live.get(), d_counts, d_unique,
-				                   d_w.get() + o_weight);
-			hipLaunchKernelGGL(gather_pick_kernel, dim3(1), dim3(256), 0, st, d_state.get(), n_refs, (unsigned long long)threshold, row_limit, d_w.get() + o_common, d_unique,
-			                   d_w.get() + o_weight, d_rows.get());
+				hipLaunchKernelGGL(gather_count_kernel, dim3(count_grid), dim3(256), 0, st, (const GatherState*)d_state.get(), lists.d_extra() + x_cbase, n_refs, count_items,
+				                   d_common, d_start, (const uint32_t*)d_hits.get(), (const unsigned char*)d_live.get(), d_counts, d_unique,
+				                   d_weight);
+			hipLaunchKernelGGL(gather_pick_kernel, dim3(1), dim3(256), 0, st, d_state.get(), n_refs, (unsigned long long)threshold, row_limit, d_common, d_unique,
+			                   d_weight, d_rows.get());
 			if (most_hits)
-				hipLaunchKernelGGL(gather_clear_kernel, dim3(clear_grid), dim3(256), 0, st, (const GatherState*)d_state.get(), d_w.get() + o_common, d_w.get() + o_start,
+				hipLaunchKernelGGL(gather_clear_kernel, dim3(clear_grid), dim3(256), 0, st, (const GatherState*)d_state.get(), d_common, d_start,
 				                   (const uint32_t*)d_hits.get(), d_live.get());
 		}
 		HIP_TRY(hipGetLastError());
@@ -380,12 +330,12 @@ int ntc_signature_gather_device(int32_t device, void* stream, const void* d_quer
 		HIP_TRY(hipMemcpyAsync(&state, d_state, sizeof state, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));
 	}
-	if (nq) hipLaunchKernelGGL(gather_rest_kernel, dim3(capped_blocks(nq, kGatherClearBlocks)), dim3(256), 0, st, (const unsigned char*)d_live.get(), d_counts, nq, d_w.get() + o_rest);
+	if (nq) hipLaunchKernelGGL(gather_rest_kernel, dim3(capped_grid(nq, kGatherClearBlocks)), dim3(256), 0, st, (const unsigned char*)d_live.get(), d_counts, nq, lists.d_extra() + x_rest);
 	HIP_TRY(hipGetLastError());
 	std::vector<ntc_gather_row> got(state.n_rows);
 	unsigned long long rest[2] = {0, 0};
 	if (state.n_rows) HIP_TRY(hipMemcpyAsync(got.data(), d_rows, got.size() * sizeof(ntc_gather_row), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(rest, d_w.get() + o_rest, sizeof rest, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(rest, lists.d_extra() + x_rest, sizeof rest, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	std::copy(got.begin(), got.end(), rows);
 	*n_rows = state.n_rows;

@@ -1,6 +1,6 @@
-// ntc_sig_sort.hip — signatures on the device behind the container: a stable radix sort of (u64 key, u32 value) pairs, the intersection of two sorted lists
-// and of all pairs of many (include/ntcard_hip.h: ntc_signature_sort_device, ntc_signature_compare_device, ntc_signature_matrix_device; DESIGN.md §4
-// "Signatures", "Sort and compare").  ntc_signature / ntc_signature_device sort their compaction with sig_sort() below.
+// ntc_sig_sort.hip — signatures on the device behind the container: a stable radix sort of (u64 key, u32 value) pairs (include/ntcard_hip.h:
+// ntc_signature_sort_device; DESIGN.md §4 "Signatures", "Sort and compare").  ntc_signature / ntc_signature_device sort their compaction with sig_sort()
+// below; the intersections of sorted lists are in ntc_sig_lists.hip.
 //
 // The sort is LSD, 8 bits per digit, eight digits.  A workgroup of four waves takes a TILE of 4096 pairs, wave w the 1024 pairs [1024 w, 1024 w + 1024) of it in
 // 16 rounds of 64 (a lane and round = one pair, a wave's load = 512 contiguous bytes), so the order of the pairs is (tile, wave, round, lane).
@@ -17,7 +17,7 @@
 // n <= 4096: ONE launch of one workgroup — the pairs stay in registers, the same ranking runs digit by digit (a digit all keys agree in is skipped there as
 // well), and LDS holds the counters and one copy of the pairs to permute them through.
 // No kernel waits on another workgroup; a launch reads what an earlier launch wrote.  Vector stores and plain C++ only.
-#include "ntc_engine.hpp"
+#include "ntc_sig_device.hpp"
 
 namespace ntc {
 
@@ -29,8 +29,6 @@ constexpr uint32_t kSortWaveItems = 64u * kSortRounds;          // 1024 pairs pe
 constexpr uint32_t kSortTile = kSortWaves * kSortWaveItems;     // 4096 pairs per workgroup
 constexpr uint32_t kSortSmall = kSortTile;                      // up to here: one launch
 static_assert(kSortThreads == kSortBins, "a thread per bin");
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
 
 __device__ __forceinline__ uint32_t digit_of(unsigned long long k, uint32_t shift) { return (uint32_t)(k >> shift) & (kSortBins - 1u); }
 
@@ -263,98 +261,6 @@ __global__ __launch_bounds__(kSortThreads) void sort_small_kernel(unsigned long 
 	}
 }
 
-// ---- intersections ----
-constexpr uint32_t kMatChunk = 4096;     // entries of a pair's shorter list per work item (a workgroup)
-constexpr uint32_t kMatItems = 1u << 18; // work items per launch: the scratch that holds them is 4 MiB whatever the number of pairs
-constexpr unsigned long long kNoBad = ~0ull;
-
-struct MatItem {
-	uint32_t i, j;  // the pair, i < j
-	uint64_t start; // first entry of the shorter list
-};
-
-// the first index >= x of the ascending list l[0 .. n) (any list: the search stays inside [0, n])
-__device__ __forceinline__ uint64_t lower_bound(const unsigned long long* __restrict__ l, uint64_t n, unsigned long long x)
-{
-	uint64_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint64_t mid = lo + (hi - lo) / 2;
-		if (l[mid] < x)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x)
-{
-	uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) {
-		const unsigned long long y = ((unsigned long long)(uint32_t)__shfl_xor((int)hi, o) << 32) | (uint32_t)__shfl_xor((int)lo, o);
-		x += y;
-		lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
-	}
-	return x;
-}
-
-// bad[list] = the smallest i >= 1 with a[i - 1] >= a[i] (kNoBad: strictly ascending); blockIdx.y = the list
-__global__ __launch_bounds__(256) void sig_ascent_kernel(const unsigned long long* const* __restrict__ lists, const uint64_t* __restrict__ ns, unsigned long long* __restrict__ bad)
-{
-	const uint32_t li = blockIdx.y;
-	const unsigned long long* a = lists[li];
-	const uint64_t n = ns[li];
-	for (uint64_t i = 1 + (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
-		if (a[i - 1] >= a[i]) atomicMin(bad + li, (unsigned long long)i);
-}
-
-// every lane an entry of the shorter list, searched in the longer one; out[0] += hits, out[1] += min(count, count) of the hits (cs != nullptr): one atomic
-// each per wave
-__global__ __launch_bounds__(256) void sig_compare_kernel(const unsigned long long* __restrict__ s, const uint32_t* __restrict__ cs, uint64_t ns,
-                                                          const unsigned long long* __restrict__ l, const uint32_t* __restrict__ cl, uint64_t nl,
-                                                          unsigned long long* __restrict__ out)
-{
-	unsigned long long hits = 0, sum = 0;
-	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < ns; i += (uint64_t)gridDim.x * 256u) {
-		const unsigned long long x = s[i];
-		const uint64_t at = lower_bound(l, nl, x);
-		if (at < nl && l[at] == x) {
-			++hits;
-			if (cs) sum += (unsigned long long)(cs[i] < cl[at] ? cs[i] : cl[at]);
-		}
-	}
-	hits = wave_sum(hits);
-	sum = wave_sum(sum);
-	if ((threadIdx.x & 63u) == 0u) {
-		if (hits) atomicAdd(out, hits);
-		if (sum) atomicAdd(out + 1, sum);
-	}
-}
-
-// a workgroup per work item: kMatChunk entries of the pair's shorter list against the longer one; counts[i * n_sigs + j] += hits, one atomic per wave
-__global__ __launch_bounds__(256) void sig_matrix_kernel(const unsigned long long* const* __restrict__ lists, const uint64_t* __restrict__ ns, const MatItem* __restrict__ items,
-                                                         uint32_t n_sigs, unsigned long long* __restrict__ counts)
-{
-	const MatItem it = items[blockIdx.x];
-	const uint64_t ni = ns[it.i], nj = ns[it.j];
-	const bool i_short = ni <= nj;
-	const unsigned long long* s = i_short ? lists[it.i] : lists[it.j];
-	const unsigned long long* l = i_short ? lists[it.j] : lists[it.i];
-	const uint64_t n_s = i_short ? ni : nj, n_l = i_short ? nj : ni;
-	const uint64_t end = it.start + kMatChunk < n_s ? it.start + kMatChunk : n_s;
-	unsigned long long hits = 0;
-	for (uint64_t q = it.start + threadIdx.x; q < end; q += 256u) {
-		const unsigned long long x = s[q];
-		const uint64_t at = lower_bound(l, n_l, x);
-		hits += (at < n_l && l[at] == x) ? 1u : 0u;
-	}
-	hits = wave_sum(hits);
-	if ((threadIdx.x & 63u) == 0u && hits) atomicAdd(counts + (uint64_t)it.i * n_sigs + it.j, hits);
-}
-
-unsigned ascent_blocks(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 1024)); }
-
 } // namespace
 
 uint64_t sig_sort_one_launch() { return kSortSmall; }
@@ -433,112 +339,6 @@ int ntc_signature_sort_device(int32_t device, void* stream, void* d_keys_u64, vo
 		if (vals) HIP_TRY(hipMemcpyAsync(vals, alt_v, n * 4, hipMemcpyDeviceToDevice, st));
 	}
 	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
-}
-
-int ntc_signature_compare_device(int32_t device, void* stream, const void* d_a_u64, const void* d_ca_u32, uint64_t na, const void* d_b_u64, const void* d_cb_u32,
-                                 uint64_t nb, uint64_t* n_common, uint64_t* min_sum)
-{
-	if (!n_common || (!d_a_u64 && na) || (!d_b_u64 && nb)) return fail(NTC_ERR_ARG, "ntc_signature_compare_device: null argument");
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
-	const bool weigh = d_ca_u32 && d_cb_u32 && min_sum;
-	// device words: the two lists, their lengths, the first bad entry of each, the hits, the sum
-	unsigned long long w[8] = {(unsigned long long)(uintptr_t)d_a_u64, (unsigned long long)(uintptr_t)d_b_u64, na, nb, ntc::kNoBad, ntc::kNoBad, 0ull, 0ull};
-	DevBuf<unsigned long long> d_w;
-	if (!d_w.reserve(sizeof w)) {
-		(void)hipGetLastError();
-		return fail(NTC_ERR_MEMORY, "ntc_signature_compare_device: cannot allocate %zu B on device", sizeof w);
-	}
-	HIP_TRY(hipMemcpyAsync(d_w, w, sizeof w, hipMemcpyHostToDevice, st));
-	if (na > 1 || nb > 1)
-		hipLaunchKernelGGL(ntc::sig_ascent_kernel, dim3(ntc::ascent_blocks(std::max(na, nb)), 2), dim3(256), 0, st, (const unsigned long long* const*)d_w.get(),
-		                   (const uint64_t*)(d_w.get() + 2), d_w.get() + 4);
-	if (na && nb) {
-		const bool a_short = na <= nb;
-		const uint64_t n_s = a_short ? na : nb;
-		const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_s + 255) / 256, 8192));
-		hipLaunchKernelGGL(ntc::sig_compare_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long*)(a_short ? d_a_u64 : d_b_u64),
-		                   weigh ? (const uint32_t*)(a_short ? d_ca_u32 : d_cb_u32) : nullptr, n_s, (const unsigned long long*)(a_short ? d_b_u64 : d_a_u64),
-		                   weigh ? (const uint32_t*)(a_short ? d_cb_u32 : d_ca_u32) : nullptr, a_short ? nb : na, d_w.get() + 6);
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(w, d_w, sizeof w, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	if (w[4] != ntc::kNoBad) return fail(NTC_ERR_ARG, "ntc_signature_compare_device: the first list is not strictly ascending at entry %llu", w[4]);
-	if (w[5] != ntc::kNoBad) return fail(NTC_ERR_ARG, "ntc_signature_compare_device: the second list is not strictly ascending at entry %llu", w[5]);
-	*n_common = w[6];
-	if (weigh) *min_sum = w[7];
-	return 0;
-}
-
-int ntc_signature_matrix_device(int32_t device, void* stream, uint32_t n_sigs, const void* const* d_hashes_u64, const uint64_t* n, uint64_t* common_out)
-{
-	if (n_sigs < 1 || n_sigs > 1024) return fail(NTC_ERR_ARG, "ntc_signature_matrix_device: %u lists (1 .. 1024 are taken)", n_sigs);
-	if (!d_hashes_u64 || !n || !common_out) return fail(NTC_ERR_ARG, "ntc_signature_matrix_device: null argument");
-	for (uint32_t i = 0; i < n_sigs; ++i)
-		if (!d_hashes_u64[i] && n[i]) return fail(NTC_ERR_ARG, "ntc_signature_matrix_device: list %u is null and has %llu entries", i, (unsigned long long)n[i]);
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
-	const size_t ns = n_sigs, cells = ns * ns;
-	// device words: [lists][lengths][first bad entry of each list][counts of the pairs, n_sigs x n_sigs], then the work items of a round
-	DevBuf<unsigned long long> d_w;
-	DevBuf<ntc::MatItem> d_items;
-	if (!d_w.reserve((3 * ns + cells) * 8) || !d_items.reserve((size_t)ntc::kMatItems * sizeof(ntc::MatItem))) {
-		(void)hipGetLastError();
-		return fail(NTC_ERR_MEMORY, "ntc_signature_matrix_device: cannot allocate %zu B of scratch on device", (3 * ns + cells) * 8 + (size_t)ntc::kMatItems * sizeof(ntc::MatItem));
-	}
-	std::vector<unsigned long long> w(3 * ns, ntc::kNoBad);
-	uint64_t longest = 0;
-	for (size_t i = 0; i < ns; ++i) {
-		w[i] = (unsigned long long)(uintptr_t)d_hashes_u64[i];
-		w[ns + i] = n[i];
-		longest = std::max<uint64_t>(longest, n[i]);
-	}
-	HIP_TRY(hipMemcpyAsync(d_w, w.data(), w.size() * 8, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemsetAsync(d_w.get() + 3 * ns, 0, cells * 8, st));
-	const unsigned long long* const* d_lists = (const unsigned long long* const*)d_w.get();
-	const uint64_t* d_ns = (const uint64_t*)(d_w.get() + ns);
-	if (longest > 1) {
-		hipLaunchKernelGGL(ntc::sig_ascent_kernel, dim3(ntc::ascent_blocks(longest), n_sigs), dim3(256), 0, st, d_lists, d_ns, d_w.get() + 2 * ns);
-		HIP_TRY(hipGetLastError());
-	}
-	HIP_TRY(hipMemcpyAsync(w.data() + 2 * ns, d_w.get() + 2 * ns, ns * 8, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st)); // every list is checked once, before any pair is looked at
-	for (size_t i = 0; i < ns; ++i)
-		if (w[2 * ns + i] != ntc::kNoBad)
-			return fail(NTC_ERR_ARG, "ntc_signature_matrix_device: list %zu is not strictly ascending at entry %llu", i, w[2 * ns + i]);
-	// rounds of at most kMatItems work items: the launches grow with the entries to search, not with the pairs
-	std::vector<ntc::MatItem> items;
-	items.reserve(ntc::kMatItems);
-	auto run_round = [&]() -> int {
-		if (items.empty()) return 0;
-		HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(ntc::MatItem), hipMemcpyHostToDevice, st));
-		hipLaunchKernelGGL(ntc::sig_matrix_kernel, dim3((unsigned)items.size()), dim3(256), 0, st, d_lists, d_ns, (const ntc::MatItem*)d_items.get(), n_sigs,
-		                   d_w.get() + 3 * ns);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(st)); // (the host items and d_items are reused by the next round)
-		items.clear();
-		return 0;
-	};
-	for (uint32_t i = 0; i < n_sigs; ++i)
-		for (uint32_t j = i + 1; j < n_sigs; ++j) {
-			const uint64_t n_s = std::min(n[i], n[j]);
-			for (uint64_t start = 0; start < n_s; start += ntc::kMatChunk) {
-				items.push_back(ntc::MatItem{i, j, start});
-				if (items.size() == ntc::kMatItems)
-					if (int rc = run_round()) return rc;
-			}
-		}
-	if (int rc = run_round()) return rc;
-	std::vector<unsigned long long> counts(cells);
-	HIP_TRY(hipMemcpyAsync(counts.data(), d_w.get() + 3 * ns, cells * 8, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	for (size_t i = 0; i < ns; ++i) {
-		common_out[i * ns + i] = n[i];
-		for (size_t j = i + 1; j < ns; ++j)
-			common_out[i * ns + j] = common_out[j * ns + i] = counts[i * ns + j];
-	}
 	return 0;
 }
 

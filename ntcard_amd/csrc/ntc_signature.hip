@@ -9,15 +9,15 @@
 // pairs (ntc_signature_inject*) and a peer's compacted pairs (ntc_merge_devices).  ntc_signature / ntc_signature_device compact a table and sort the compaction on
 // the device (ntc_sig_sort.hip).  Vector stores and plain C++ only; every launch is on the engine's stream.
 #include <cerrno>
-#include <cstdio>
 
-#include "ntc_engine.hpp"
+#include "ntc_sig_device.hpp"
 
 namespace ntc {
 
 namespace {
 
 constexpr unsigned long long kSigMul = 0x9E3779B97F4A7C15ull;
+constexpr uint32_t kSigBlocks = 4096; // grid cap of sig_insert_kernel and sig_compact_kernel
 
 // one pair into the table; kSat: the count may be anything (inject, rehash, merge) — a CAS loop that saturates; else add <= 64 and the launch adds fewer than
 // 2^31 in all (the log's capacity), so a counter below 2^31 cannot wrap under plain atomicAdd and only one at or above it takes the loop
@@ -69,11 +69,10 @@ __global__ __launch_bounds__(256) void sig_insert_kernel(const SigTable t, const
 		bool go = h != 0ull && add != 0u;
 		if constexpr (!kSat) {
 			// one hot value (a homopolymer, a repeat): the lanes that hold the first lane's value send ONE add instead of 64 to the same address
-			const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)h), hi = __builtin_amdgcn_readfirstlane((uint32_t)(h >> 32));
-			const unsigned long long first = ((unsigned long long)hi << 32) | lo;
+			const unsigned long long first = wave_first(h);
 			const uint64_t same = __builtin_amdgcn_ballot_w64(go && h == first);
 			if (go && h == first) {
-				go = (uint64_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same, 0u)) == 0u;
+				go = lanes_below(same) == 0u;
 				add = (uint32_t)__popcll(same);
 			}
 		}
@@ -91,22 +90,15 @@ __global__ __launch_bounds__(256) void sig_compact_kernel(const SigTable t, unsi
 		const unsigned long long h = i < t.slots ? t.keys[i] : 0ull;
 		const uint64_t m = __builtin_amdgcn_ballot_w64(h != 0ull);
 		if (m == 0) continue;
-		uint32_t b_lo = 0, b_hi = 0;
-		if (lane == 0) {
-			const unsigned long long b = atomicAdd(cursor, (unsigned long long)__popcll(m));
-			b_lo = (uint32_t)b;
-			b_hi = (uint32_t)(b >> 32);
-		}
-		const uint64_t at = (((uint64_t)__builtin_amdgcn_readfirstlane(b_hi) << 32) | __builtin_amdgcn_readfirstlane(b_lo)) +
-		                    __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+		unsigned long long b = 0;
+		if (lane == 0) b = atomicAdd(cursor, (unsigned long long)__popcll(m));
+		const uint64_t at = wave_first(b) + lanes_below(m);
 		if (h != 0ull) {
 			out_keys[at] = h;
 			out_counts[at] = t.counts[i];
 		}
 	}
 }
-
-unsigned sig_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 4096)); }
 
 } // namespace
 
@@ -118,15 +110,15 @@ hipError_t launch_sig_insert(const SigTable& t, const unsigned long long* in_key
 		++bits;
 	if ((1ull << bits) != t.slots || bits < 1) return hipErrorInvalidValue;
 	if (in_counts == nullptr) // the value log, or a list of single occurrences: fewer than 2^31 adds of 1
-		hipLaunchKernelGGL(sig_insert_kernel<false>, dim3(sig_grid(n)), dim3(256), 0, st, t, in_keys, in_counts, n, 64u - bits);
+		hipLaunchKernelGGL(sig_insert_kernel<false>, dim3(capped_grid(n, kSigBlocks)), dim3(256), 0, st, t, in_keys, in_counts, n, 64u - bits);
 	else
-		hipLaunchKernelGGL(sig_insert_kernel<true>, dim3(sig_grid(n)), dim3(256), 0, st, t, in_keys, in_counts, n, 64u - bits);
+		hipLaunchKernelGGL(sig_insert_kernel<true>, dim3(capped_grid(n, kSigBlocks)), dim3(256), 0, st, t, in_keys, in_counts, n, 64u - bits);
 	return hipGetLastError();
 }
 
 hipError_t launch_sig_compact(const SigTable& t, unsigned long long* out_keys, uint32_t* out_counts, unsigned long long* cursor, hipStream_t st)
 {
-	hipLaunchKernelGGL(sig_compact_kernel, dim3(sig_grid(t.slots)), dim3(256), 0, st, t, out_keys, out_counts, cursor);
+	hipLaunchKernelGGL(sig_compact_kernel, dim3(capped_grid(t.slots, kSigBlocks)), dim3(256), 0, st, t, out_keys, out_counts, cursor);
 	return hipGetLastError();
 }
 
@@ -274,6 +266,38 @@ int sig_sorted(ntc_engine* e, uint32_t plane, uint64_t cap, const char* who, uin
 	if (int rc = close_span(sp, e->stream, e->timers[T_SIG_SORT].spans)) return rc;
 	*k = in_alt ? e->d_sigalt_k.get() : e->d_sigtmp_k.get();
 	*c = in_alt ? e->d_sigalt_c.get() : e->d_sigtmp_c.get();
+	return 0;
+}
+
+// ntc_signature (kind = device to host) and ntc_signature_device (device to device): the plane's sorted pairs into the caller's arrays
+int sig_copy_out(ntc_engine* e, uint32_t plane, void* hashes, void* counts, uint64_t cap, uint64_t* n_out, hipMemcpyKind kind, const char* who)
+{
+	if (int rc = sig_check(e, plane, who)) return rc;
+	if (!n_out || (!hashes && cap)) return fail(NTC_ERR_ARG, "%s: null argument", who);
+	std::lock_guard<std::mutex> lk(e->mu);
+	HIP_TRY(hipSetDevice(e->device));
+	uint64_t got = 0;
+	const unsigned long long* k = nullptr;
+	const uint32_t* c = nullptr;
+	if (int rc = sig_sorted(e, plane, cap, who, &got, &k, &c)) return rc;
+	if (got) {
+		HIP_TRY(hipMemcpyAsync(hashes, k, got * 8, kind, e->stream));
+		if (counts) HIP_TRY(hipMemcpyAsync(counts, c, got * 4, kind, e->stream));
+	}
+	HIP_TRY(hipStreamSynchronize(e->stream)); // (the arrays are complete, and the engine's scratch is free again)
+	*n_out = got;
+	return drain_events(e);
+}
+
+// a query of timers: every span that has ended is read first
+int sig_times(ntc_engine* e, const char* who, Timer a, double* a_ms, Timer b = kTimers, double* b_ms = nullptr)
+{
+	if (int rc = sig_check(e, 0, who)) return rc;
+	std::lock_guard<std::mutex> lk(e->mu);
+	HIP_TRY(hipSetDevice(e->device));
+	if (int rc = drain_events(e)) return rc;
+	if (a_ms) *a_ms = e->timers[a].ms;
+	if (b_ms) *b_ms = e->timers[b].ms;
 	return 0;
 }
 
@@ -440,40 +464,12 @@ int ntc_signature_size(ntc_engine* e, uint32_t plane, uint64_t* n)
 
 int ntc_signature(ntc_engine* e, uint32_t plane, uint64_t* hashes, uint32_t* counts, uint64_t cap, uint64_t* n_out)
 {
-	if (int rc = sig_check(e, plane, "ntc_signature")) return rc;
-	if (!n_out || (!hashes && cap)) return fail(NTC_ERR_ARG, "ntc_signature: null argument");
-	std::lock_guard<std::mutex> lk(e->mu);
-	HIP_TRY(hipSetDevice(e->device));
-	uint64_t got = 0;
-	const unsigned long long* k = nullptr;
-	const uint32_t* c = nullptr;
-	if (int rc = sig_sorted(e, plane, cap, "ntc_signature", &got, &k, &c)) return rc;
-	if (got) {
-		HIP_TRY(hipMemcpyAsync(hashes, k, got * 8, hipMemcpyDeviceToHost, e->stream));
-		if (counts) HIP_TRY(hipMemcpyAsync(counts, c, got * 4, hipMemcpyDeviceToHost, e->stream));
-	}
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	*n_out = got;
-	return drain_events(e);
+	return sig_copy_out(e, plane, hashes, counts, cap, n_out, hipMemcpyDeviceToHost, "ntc_signature");
 }
 
 int ntc_signature_device(ntc_engine* e, uint32_t plane, void* d_hashes, void* d_counts, uint64_t cap, uint64_t* n_out)
 {
-	if (int rc = sig_check(e, plane, "ntc_signature_device")) return rc;
-	if (!n_out || (!d_hashes && cap)) return fail(NTC_ERR_ARG, "ntc_signature_device: null argument");
-	std::lock_guard<std::mutex> lk(e->mu);
-	HIP_TRY(hipSetDevice(e->device));
-	uint64_t got = 0;
-	const unsigned long long* k = nullptr;
-	const uint32_t* c = nullptr;
-	if (int rc = sig_sorted(e, plane, cap, "ntc_signature_device", &got, &k, &c)) return rc;
-	if (got) {
-		HIP_TRY(hipMemcpyAsync(d_hashes, k, got * 8, hipMemcpyDeviceToDevice, e->stream));
-		if (d_counts) HIP_TRY(hipMemcpyAsync(d_counts, c, got * 4, hipMemcpyDeviceToDevice, e->stream));
-	}
-	HIP_TRY(hipStreamSynchronize(e->stream)); // (the arrays are complete, and the engine's scratch is free again)
-	*n_out = got;
-	return drain_events(e);
+	return sig_copy_out(e, plane, d_hashes, d_counts, cap, n_out, hipMemcpyDeviceToDevice, "ntc_signature_device");
 }
 
 int ntc_signature_inject_device(ntc_engine* e, uint32_t plane, const void* d_hashes, const void* d_counts, uint64_t n)
@@ -502,26 +498,6 @@ int ntc_signature_inject(ntc_engine* e, uint32_t plane, const uint64_t* hashes, 
 	return rc;
 }
 
-int ntc_signature_compare(const uint64_t* a, uint64_t na, const uint64_t* b, uint64_t nb, uint64_t* n_common)
-{
-	if (!n_common || (!a && na) || (!b && nb)) return fail(NTC_ERR_ARG, "ntc_signature_compare: null argument");
-	for (uint64_t i = 1; i < na; ++i)
-		if (a[i - 1] >= a[i]) return fail(NTC_ERR_ARG, "ntc_signature_compare: the first list is not strictly ascending at entry %llu", (unsigned long long)i);
-	for (uint64_t i = 1; i < nb; ++i)
-		if (b[i - 1] >= b[i]) return fail(NTC_ERR_ARG, "ntc_signature_compare: the second list is not strictly ascending at entry %llu", (unsigned long long)i);
-	uint64_t i = 0, j = 0, c = 0;
-	while (i < na && j < nb) {
-		if (a[i] < b[j])
-			++i;
-		else if (b[j] < a[i])
-			++j;
-		else
-			++c, ++i, ++j;
-	}
-	*n_common = c;
-	return 0;
-}
-
 int ntc_signature_stats(ntc_engine* e, uint64_t* slots, uint64_t* grows)
 {
 	if (int rc = sig_check(e, 0, "ntc_signature_stats")) return rc;
@@ -534,26 +510,9 @@ int ntc_signature_stats(ntc_engine* e, uint64_t* slots, uint64_t* grows)
 	return 0;
 }
 
-int ntc_signature_time(ntc_engine* e, double* insert_ms, double* grow_ms)
-{
-	if (int rc = sig_check(e, 0, "ntc_signature_time")) return rc;
-	std::lock_guard<std::mutex> lk(e->mu);
-	HIP_TRY(hipSetDevice(e->device));
-	if (int rc = drain_events(e)) return rc;
-	if (insert_ms) *insert_ms = e->timers[T_SIG_INSERT].ms;
-	if (grow_ms) *grow_ms = e->timers[T_SIG_GROW].ms;
-	return 0;
-}
+int ntc_signature_time(ntc_engine* e, double* insert_ms, double* grow_ms) { return sig_times(e, "ntc_signature_time", T_SIG_INSERT, insert_ms, T_SIG_GROW, grow_ms); }
 
-int ntc_signature_sort_time(ntc_engine* e, double* ms)
-{
-	if (int rc = sig_check(e, 0, "ntc_signature_sort_time")) return rc;
-	std::lock_guard<std::mutex> lk(e->mu);
-	HIP_TRY(hipSetDevice(e->device));
-	if (int rc = drain_events(e)) return rc;
-	if (ms) *ms = e->timers[T_SIG_SORT].ms;
-	return 0;
-}
+int ntc_signature_sort_time(ntc_engine* e, double* ms) { return sig_times(e, "ntc_signature_sort_time", T_SIG_SORT, ms); }
 
 int ntc_signature_header(ntc_engine* e, uint32_t plane, ntc_sig_header* h)
 {
@@ -567,80 +526,6 @@ int ntc_signature_header(ntc_engine* e, uint32_t plane, ntc_sig_header* h)
 	h->s_bits = e->s_bits;
 	const std::string m = e->plain(plane) ? std::string(h->k, '1') : e->masks[plane];
 	std::memcpy(h->mask, m.data(), std::min<size_t>(m.size(), NTC_SIG_MASK_MAX - 1));
-	return 0;
-}
-
-// ---- signature files: pure host code ----
-namespace {
-const char kSigMagic[8] = {'N', 'T', 'C', 'S', 'I', 'G', '1', '\0'};
-struct FileCloser {
-	FILE* f;
-	~FileCloser()
-	{
-		if (f) std::fclose(f);
-	}
-};
-} // namespace
-
-int ntc_signature_write(const char* path, const ntc_sig_header* h, const uint64_t* hashes, const uint32_t* counts)
-{
-	if (!path || !h || ((!hashes || !counts) && h->n)) return fail(NTC_ERR_ARG, "ntc_signature_write: null argument");
-	const size_t ml = strnlen(h->mask, NTC_SIG_MASK_MAX);
-	if (ml == 0 || ml >= NTC_SIG_MASK_MAX || ml != h->k || h->strand > 2 || h->hpc > 1 || h->s_bits < 2 || h->s_bits > 24)
-		return fail(NTC_ERR_ARG, "ntc_signature_write: bad header (the mask has k characters, strand 0..2, hpc 0..1, s_bits 2..24)");
-	for (size_t i = 0; i < ml; ++i)
-		if (h->mask[i] != '0' && h->mask[i] != '1') return fail(NTC_ERR_ARG, "ntc_signature_write: the mask holds a character that is neither '0' nor '1'");
-	for (uint64_t i = 1; i < h->n; ++i)
-		if (hashes[i - 1] >= hashes[i]) return fail(NTC_ERR_ARG, "ntc_signature_write: the hashes are not strictly ascending at entry %llu", (unsigned long long)i);
-	FileCloser fc{std::fopen(path, "wb")};
-	if (!fc.f) return fail(NTC_ERR_ARG, "ntc_signature_write: cannot write %s", path);
-	const uint32_t head[6] = {h->k, h->gap, h->strand, h->hpc, h->s_bits, (uint32_t)ml};
-	char mask[NTC_SIG_MASK_MAX + 8] = {0};
-	std::memcpy(mask, h->mask, ml);
-	const size_t padded = (ml + 7) & ~(size_t)7;
-	bool ok = std::fwrite(kSigMagic, 1, 8, fc.f) == 8 && std::fwrite(head, 4, 6, fc.f) == 6 && std::fwrite(&h->n, 8, 1, fc.f) == 1 && std::fwrite(mask, 1, padded, fc.f) == padded;
-	ok = ok && (h->n == 0 || (std::fwrite(hashes, 8, h->n, fc.f) == h->n && std::fwrite(counts, 4, h->n, fc.f) == h->n));
-	FILE* f = fc.f;
-	fc.f = nullptr;
-	if (std::fclose(f) != 0 || !ok) return fail(NTC_ERR_ARG, "ntc_signature_write: cannot write %s", path);
-	return 0;
-}
-
-int ntc_signature_read(const char* path, ntc_sig_header* h, uint64_t* hashes, uint32_t* counts, uint64_t cap)
-{
-	if (!path || !h) return fail(NTC_ERR_ARG, "ntc_signature_read: null argument");
-	FileCloser fc{std::fopen(path, "rb")};
-	if (!fc.f) return fail(NTC_ERR_ARG, "ntc_signature_read: cannot read %s", path);
-	char magic[8];
-	uint32_t head[6];
-	uint64_t n = 0;
-	if (std::fseek(fc.f, 0, SEEK_END) != 0) return fail(NTC_ERR_ARG, "ntc_signature_read: cannot read %s", path);
-	const long file_len = std::ftell(fc.f);
-	if (file_len < 0 || std::fseek(fc.f, 0, SEEK_SET) != 0) return fail(NTC_ERR_ARG, "ntc_signature_read: cannot read %s", path);
-	if (std::fread(magic, 1, 8, fc.f) != 8 || std::memcmp(magic, kSigMagic, 8) != 0) return fail(NTC_ERR_ARG, "ntc_signature_read: %s is not a signature file", path);
-	if (std::fread(head, 4, 6, fc.f) != 6 || std::fread(&n, 8, 1, fc.f) != 1 || head[5] == 0 || head[5] >= NTC_SIG_MASK_MAX || head[5] != head[0] || head[2] > 2 || head[3] > 1)
-		return fail(NTC_ERR_ARG, "ntc_signature_read: %s: bad header", path);
-	const size_t padded = ((size_t)head[5] + 7) & ~(size_t)7;
-	const uint64_t body = (uint64_t)file_len - std::min<uint64_t>((uint64_t)file_len, 8 + 24 + 8 + padded);
-	if (n > body / 12 || n * 12 != body) // (n comes from the file: it is checked against the file's length before anything is sized or sought by it)
-		return fail(NTC_ERR_ARG, "ntc_signature_read: %s is cut short or holds more than its header says (%llu pairs, %llu bytes behind the header)", path, (unsigned long long)n, (unsigned long long)body);
-	std::memset(h, 0, sizeof *h);
-	h->k = head[0], h->gap = head[1], h->strand = head[2], h->hpc = head[3], h->s_bits = head[4], h->n = n;
-	char mask[NTC_SIG_MASK_MAX + 8];
-	if (std::fread(mask, 1, padded, fc.f) != padded) return fail(NTC_ERR_ARG, "ntc_signature_read: %s is cut short", path);
-	std::memcpy(h->mask, mask, head[5]);
-	for (uint32_t i = 0; i < head[5]; ++i)
-		if (h->mask[i] != '0' && h->mask[i] != '1') return fail(NTC_ERR_ARG, "ntc_signature_read: %s: bad mask", path);
-	if (!hashes && !counts) return 0;
-	if (cap < n) return fail(NTC_ERR_ARG, "ntc_signature_read: %s holds %llu pairs, the arrays have room for %llu", path, (unsigned long long)n, (unsigned long long)cap);
-	if (hashes) {
-		if (n && std::fread(hashes, 8, n, fc.f) != n) return fail(NTC_ERR_ARG, "ntc_signature_read: %s is cut short", path);
-		for (uint64_t i = 1; i < n; ++i)
-			if (hashes[i - 1] >= hashes[i]) return fail(NTC_ERR_ARG, "ntc_signature_read: %s: the hashes are not strictly ascending", path);
-	} else if (std::fseek(fc.f, (long)(n * 8), SEEK_CUR) != 0) {
-		return fail(NTC_ERR_ARG, "ntc_signature_read: %s is cut short", path);
-	}
-	if (counts && n && std::fread(counts, 4, n, fc.f) != n) return fail(NTC_ERR_ARG, "ntc_signature_read: %s is cut short", path);
 	return 0;
 }
 

@@ -3,9 +3,9 @@
 //   ntsig compare A.sig B.sig   |A n B|, Jaccard and both containments — refused when the headers differ in anything but n
 //   ntsig matrix [--containment] A.sig B.sig ...   all pairs at once, as a TSV: Jaccard, or the containment of the row's file in the column's
 //   ntsig gather [--threshold N] QUERY.sig REF.sig ...   which references are in the query and what each explains on its own, as a TSV in pick order
-//                               (ntc_signature_gather_device; headers are checked like matrix's, before a device is looked for)
-// info and compare are host code over the library's reader and ntc_signature_compare and need no GPU; matrix reads every header first (files counted
-// differently are refused before a device is looked for), then uploads the hash lists and calls ntc_signature_matrix_device.
+//                               (ntc_signature_gather_device)
+// info and compare are host code over the library's reader and ntc_signature_compare and need no GPU; matrix and gather read every header first (files counted
+// differently are refused before a device is looked for: load_all), then upload the hash lists and call ntc_signature_matrix_device / _gather_device.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
@@ -78,34 +78,48 @@ struct DeviceLists {
 	}
 };
 
-int matrix(int n_files, char** files, bool containment)
+// hipMalloc + copy of n values of `bytes` bytes each from a file (n == 0: nothing, *out stays null)
+bool to_device(void** out, const void* host, uint64_t n, size_t bytes, const char* file)
 {
-	std::vector<Sig> sigs(n_files);
+	if (n == 0) return true;
+	hipError_t rc = hipMalloc(out, n * bytes);
+	if (rc == hipSuccess) rc = hipMemcpy(*out, host, n * bytes, hipMemcpyHostToDevice);
+	if (rc == hipSuccess) return true;
+	std::fprintf(stderr, "ntsig: cannot bring the %llu values of %s to the device: %s\n", (unsigned long long)n, file, hipGetErrorString(rc));
+	return false;
+}
+
+// what matrix and gather do with their files before anything goes to the device, in this order: every header is read, files[1 ..] counted differently from
+// files[0] are refused, every file's pairs are read, and the library says whether a device can be used — the matrix of one empty list touches the device and
+// nothing else.  EXIT_SUCCESS: sigs holds the files
+int load_all(int n_files, char** files, std::vector<Sig>& sigs)
+{
+	sigs.resize(n_files);
 	for (int i = 0; i < n_files; ++i)
 		if (!load(files[i], sigs[i], false)) return EXIT_FAILURE;
 	for (int i = 1; i < n_files; ++i)
 		if (const char* d = differs_in(sigs[0].h, sigs[i].h)) return refuse(files[0], files[i], d);
 	for (int i = 0; i < n_files; ++i)
 		if (!load(files[i], sigs[i], true)) return EXIT_FAILURE;
-	// the library says whether a device can be used: the matrix of one empty list touches the device and nothing else
 	uint64_t none = 0, probe = 0;
 	const void* null_list = nullptr;
 	if (ntc_signature_matrix_device(0, nullptr, 1, &null_list, &none, &probe) != 0) {
 		std::fprintf(stderr, "ntsig: %s\n", ntc_last_error());
 		return EXIT_FAILURE;
 	}
+	return EXIT_SUCCESS;
+}
+
+int matrix(int n_files, char** files, bool containment)
+{
+	std::vector<Sig> sigs;
+	if (int rc = load_all(n_files, files, sigs)) return rc;
 	DeviceLists d;
 	d.p.assign(n_files, nullptr);
 	std::vector<uint64_t> n(n_files);
 	for (int i = 0; i < n_files; ++i) {
 		n[i] = sigs[i].h.n;
-		if (n[i] == 0) continue;
-		hipError_t rc = hipMalloc(&d.p[i], n[i] * 8);
-		if (rc == hipSuccess) rc = hipMemcpy(d.p[i], sigs[i].hashes.data(), n[i] * 8, hipMemcpyHostToDevice);
-		if (rc != hipSuccess) {
-			std::fprintf(stderr, "ntsig: cannot bring the %llu values of %s to the device: %s\n", (unsigned long long)n[i], files[i], hipGetErrorString(rc));
-			return EXIT_FAILURE;
-		}
+		if (!to_device(&d.p[i], sigs[i].hashes.data(), n[i], 8, files[i])) return EXIT_FAILURE;
 	}
 	std::vector<uint64_t> common((size_t)n_files * n_files);
 	if (ntc_signature_matrix_device(0, nullptr, (uint32_t)n_files, d.p.data(), n.data(), common.data()) != 0) {
@@ -126,46 +140,24 @@ int matrix(int n_files, char** files, bool containment)
 	return EXIT_SUCCESS;
 }
 
-// hipMalloc + copy of n values of `bytes` bytes each from a file (n == 0: nothing, *out stays null)
-bool to_device(void** out, const void* host, uint64_t n, size_t bytes, const char* file)
-{
-	if (n == 0) return true;
-	hipError_t rc = hipMalloc(out, n * bytes);
-	if (rc == hipSuccess) rc = hipMemcpy(*out, host, n * bytes, hipMemcpyHostToDevice);
-	if (rc == hipSuccess) return true;
-	std::fprintf(stderr, "ntsig: cannot bring the %llu values of %s to the device: %s\n", (unsigned long long)n, file, hipGetErrorString(rc));
-	return false;
-}
-
 double ratio(uint64_t num, uint64_t den) { return den ? (double)num / (double)den : 0.0; }
 
-int gather(const char* query_file, int n_refs, char** ref_files, uint64_t threshold)
+// files[0] is the query, the references follow
+int gather(int n_files, char** files, uint64_t threshold)
 {
-	Sig query;
-	std::vector<Sig> refs(n_refs);
-	if (!load(query_file, query, false)) return EXIT_FAILURE;
-	for (int i = 0; i < n_refs; ++i)
-		if (!load(ref_files[i], refs[i], false)) return EXIT_FAILURE;
-	for (int i = 0; i < n_refs; ++i)
-		if (const char* d = differs_in(query.h, refs[i].h)) return refuse(query_file, ref_files[i], d);
-	if (!load(query_file, query, true)) return EXIT_FAILURE;
-	for (int i = 0; i < n_refs; ++i)
-		if (!load(ref_files[i], refs[i], true)) return EXIT_FAILURE;
-	// the library says whether a device can be used (as matrix asks it)
-	uint64_t none = 0, probe = 0;
-	const void* null_list = nullptr;
-	if (ntc_signature_matrix_device(0, nullptr, 1, &null_list, &none, &probe) != 0) {
-		std::fprintf(stderr, "ntsig: %s\n", ntc_last_error());
-		return EXIT_FAILURE;
-	}
+	std::vector<Sig> sigs;
+	if (int rc = load_all(n_files, files, sigs)) return rc;
+	const Sig& query = sigs[0];
+	const int n_refs = n_files - 1;
+	char** ref_files = files + 1;
 	DeviceLists d; // [references][query hashes][query counts]
 	d.p.assign(n_refs + 2, nullptr);
 	std::vector<uint64_t> n(n_refs);
 	const uint64_t nq = query.h.n;
-	if (!to_device(&d.p[n_refs], query.hashes.data(), nq, 8, query_file) || !to_device(&d.p[n_refs + 1], query.counts.data(), nq, 4, query_file)) return EXIT_FAILURE;
+	if (!to_device(&d.p[n_refs], query.hashes.data(), nq, 8, files[0]) || !to_device(&d.p[n_refs + 1], query.counts.data(), nq, 4, files[0])) return EXIT_FAILURE;
 	for (int i = 0; i < n_refs; ++i) {
-		n[i] = refs[i].h.n;
-		if (!to_device(&d.p[i], refs[i].hashes.data(), n[i], 8, ref_files[i])) return EXIT_FAILURE;
+		n[i] = sigs[i + 1].h.n;
+		if (!to_device(&d.p[i], sigs[i + 1].hashes.data(), n[i], 8, ref_files[i])) return EXIT_FAILURE;
 	}
 	std::vector<ntc_gather_row> rows(n_refs);
 	uint32_t n_rows = 0;
@@ -239,7 +231,7 @@ int main(int argc, char** argv)
 		}
 		const int n_refs = argc - first - 1; // behind the query
 		if (n_refs < 1 || n_refs > 1024) return usage();
-		return gather(argv[first], n_refs, argv + first + 1, threshold);
+		return gather(n_refs + 1, argv + first, threshold);
 	}
 	return usage();
 }

@@ -447,13 +447,17 @@ def signature_compare_device(ptr_a, ptr_counts_a, na, ptr_b, ptr_counts_b, nb, d
     return c.value, (m.value if both else None)
 
 
+def _device_lists(ptrs, ns):
+    """-> (how many, void* array, uint64 array) of device lists for the C ABI (arrays of one element for no list)"""
+    assert len(ptrs) == len(ns)
+    k = len(ptrs)
+    return k, (C.c_void_p * max(k, 1))(*[C.c_void_p(int(p)) if p else None for p in ptrs]), (C.c_uint64 * max(k, 1))(*[int(x) for x in ns])
+
+
 def signature_matrix_device(ptrs, ns, device=0, stream=None):
     """device hash lists ptrs[i] of ns[i] strictly ascending uint64 each -> np.ndarray[uint64] (len, len): the size of every pair's intersection, the diagonal
     ns; synchronous (ntc_signature_matrix_device)"""
-    assert len(ptrs) == len(ns)
-    k = len(ptrs)
-    arr = (C.c_void_p * max(k, 1))(*[C.c_void_p(int(p)) if p else None for p in ptrs])
-    n = (C.c_uint64 * max(k, 1))(*[int(x) for x in ns])
+    k, arr, n = _device_lists(ptrs, ns)
     out = np.zeros((k, k), dtype=np.uint64)
     check(_abi.lib().ntc_signature_matrix_device(device, C.c_void_p(stream) if stream else None, k, arr, n, _np_ptr(out) if k else None))
     return out
@@ -468,11 +472,8 @@ def signature_gather_device(ptr_q, ptr_counts_q, nq, ptrs, ns, threshold=1, max_
     ptrs[i] of ns[i] strictly ascending uint64 each -> (rows, unassigned, unassigned_weight).  rows: a structured array (GATHER_ROW_DTYPE) in pick order,
     at most max_rows of them (None: as many as there are references); a round's pick is the reference with the most query entries no earlier pick took,
     the lowest index among equals, and the run ends when that count falls below `threshold` hashes; synchronous (ntc_signature_gather_device)"""
-    assert len(ptrs) == len(ns)
-    k = len(ptrs)
+    k, arr, n = _device_lists(ptrs, ns)
     cap = k if max_rows is None else int(max_rows)
-    arr = (C.c_void_p * max(k, 1))(*[C.c_void_p(int(p)) if p else None for p in ptrs])
-    n = (C.c_uint64 * max(k, 1))(*[int(x) for x in ns])
     rows = np.zeros(max(cap, 1), dtype=GATHER_ROW_DTYPE)
     n_rows, rest, rest_w = C.c_uint32(), C.c_uint64(), C.c_uint64()
     check(_abi.lib().ntc_signature_gather_device(device, C.c_void_p(stream) if stream else None, C.c_void_p(ptr_q) if ptr_q else None,

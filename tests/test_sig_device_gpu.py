@@ -176,6 +176,13 @@ def test_compare_refuses_lists_that_do_not_ascend(nt):
     with pytest.raises(nt.NtcError) as ei:
         nt.signature_compare_device(dd.data_ptr(), 0, dup.size, dg.data_ptr(), 0, good.size)
     assert ei.value.code == ERR_ARG and "first list" in str(ei.value) and "entry 40000" in str(ei.value)
+    # both lists are bad: the first list and its entry are named
+    two, five = p[:6].copy(), p[:8].copy()
+    two[2], five[5] = two[1], five[3]
+    dt, df = dev64(two), dev64(five)
+    with pytest.raises(nt.NtcError) as ei:
+        nt.signature_compare_device(dt.data_ptr(), 0, two.size, df.data_ptr(), 0, five.size)
+    assert ei.value.code == ERR_ARG and "first list" in str(ei.value) and "entry 2" in str(ei.value) and "second list" not in str(ei.value)
     c = C.c_uint64()
     assert L.ntc_signature_compare(step.ctypes.data_as(C.c_void_p), step.size, good.ctypes.data_as(C.c_void_p), good.size, C.byref(c)) == ERR_ARG
     assert b"first list" in L.ntc_last_error() and b"entry 69999" in L.ntc_last_error()  # the host function's words
@@ -227,6 +234,14 @@ def test_matrix_refuses_an_unsorted_list_and_bad_counts(nt):
     out = np.full((3, 3), 0x5a5a5a5a, dtype=np.uint64)
     assert L.ntc_signature_matrix_device(0, None, 3, ptrs, ns, out.ctypes.data_as(C.c_void_p)) == ERR_ARG
     assert b"list 1 " in L.ntc_last_error() and b"entry 5001" in L.ntc_last_error() and bool(np.all(out == 0x5a5a5a5a))
+    # lists 0 and 2 are bad: list 0 is named
+    small = [p[:6].copy(), p[2:9], p[:8].copy()]
+    small[0][3], small[2][5] = small[0][2], small[2][1]
+    ds = [dev64(x) for x in small]
+    sp = (C.c_void_p * 3)(*[d.data_ptr() for d in ds])
+    sn = (C.c_uint64 * 3)(*[x.size for x in small])
+    assert L.ntc_signature_matrix_device(0, None, 3, sp, sn, out.ctypes.data_as(C.c_void_p)) == ERR_ARG
+    assert b"list 0 is not strictly ascending at entry 3" in L.ntc_last_error() and bool(np.all(out == 0x5a5a5a5a))
     for bad in (0, 1025):
         assert L.ntc_signature_matrix_device(0, None, bad, ptrs, ns, out.ctypes.data_as(C.c_void_p)) == ERR_ARG and bool(np.all(out == 0x5a5a5a5a))
     assert L.ntc_signature_matrix_device(0, None, 3, None, ns, out.ctypes.data_as(C.c_void_p)) == ERR_ARG

@@ -227,6 +227,11 @@ def test_unsorted_lists_are_refused(nt):
     bad_r[[17, 18]] = bad_r[[18, 17]]  # a step back
     rc, msg, untouched = raw_call(nt, q, refs[:2] + [bad_r] + refs[3:])
     assert rc == ERR_ARG and "reference 2 is not strictly ascending at entry 18" in msg and untouched
+    # the query and reference 0 are both bad: the query is named
+    small_q, small_r = p[:8].copy(), p[2:8].copy()
+    small_q[6], small_r[2] = small_q[4], small_r[1]
+    rc, msg, untouched = raw_call(nt, small_q, [small_r, p[3:7]])
+    assert rc == ERR_ARG and "the query is not strictly ascending at entry 6" in msg and "reference" not in msg and untouched
     rc, msg, untouched = raw_call(nt, q, refs)
     assert rc == 0 and not untouched
 

@@ -1,4 +1,4 @@
-"""GPU tests of gather above its caps (ntcard_amd/csrc/ntc_sig_gather.hip; DESIGN.md §4, the table of grid caps).  The count, clear, rest and ascent kernels
+"""GPU tests of gather above its caps (ntcard_amd/csrc/ntc_sig_gather.hip, ntc_sig_lists.hip; DESIGN.md §4, the table of grid caps).  The count, clear, rest and ascent kernels
 cap their grids and walk the rest in a grid-stride loop, the search runs at most 2^18 work items per launch and the pick walks the references 256 at a
 time: each case here is the smallest that takes such a loop into a second turn, asserts the size that makes it do so before it touches the device, and is
 compared with tests/sig_gather_model.py."""
@@ -20,7 +20,7 @@ CHUNK = 4096                      # entries (search) or hits (count) per work it
 SEARCH_ITEMS = 2**18              # search work items per launch
 COUNT_BLOCKS = 1024               # gather_count_kernel: work items per turn
 CLEAR_STRIDE = 1024 * 256         # gather_clear_kernel, gather_rest_kernel: hits / query entries per turn
-ASCENT_STRIDE = 1024 * 256        # gather_ascent_kernel: the first turn covers the entries 1 .. ASCENT_STRIDE
+ASCENT_STRIDE = 1024 * 256        # sig_ascent_kernel (SigLists): the first turn covers the entries 1 .. ASCENT_STRIDE
 PICK_THREADS = 256                # gather_pick_kernel: references per turn
 MAX_REFS = 1024
 

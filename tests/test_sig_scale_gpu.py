@@ -1,4 +1,4 @@
-"""GPU tests of the signature kernels above their grid caps (ntcard_amd/csrc/ntc_signature.hip, ntc_sig_sort.hip; DESIGN.md §4 "Sort and compare", the table
+"""GPU tests of the signature kernels above their grid caps (ntcard_amd/csrc/ntc_signature.hip, ntc_sig_sort.hip, ntc_sig_lists.hip; DESIGN.md §4 "Sort and compare", the table
 of thresholds).  Every kernel there caps its grid and walks the rest of its input in a grid-stride loop, the matrix cuts its work into rounds of 2^18 items
 and the sort's scan walks its row 256 tiles at a time: each case here is the smallest that takes such a loop into a second turn, asserts the size that
 makes it do so before it touches the device, and compares with numpy or the oracle (np.unique, np.argsort(kind="stable"), np.intersect1d, a
