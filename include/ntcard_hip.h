@@ -564,6 +564,27 @@ int ntc_set_profiling(ntc_engine *e, int enable);
 /* how ntComp's increment is currently carried out on the device: 0 = hit log + partitioned apply, 1 = direct atomics
  * (NTC_FLAG_DIRECT_ATOMICS, or chosen by the engine after an apply found mostly repeated counters); waits for the stream */
 int ntc_update_mode(ntc_engine *e, uint32_t *mode_out);
+/* K1 (the general kernel) is one template with many instantiations; this says which of them the library has launched and in which regimes (additive to
+ * ABI 6; a diagnostic for the tests, like ntc_merge_allocations).  Process-wide, host only: it touches no device and needs none.  Row `row` of the table
+ * of instantiations: its template arguments, the launches since the library was loaded, how many of them were in regime i —
+ *   0 PREFETCH     ceil(64 stride / 1024) <= pref: the next wave-batch is prefetched into registers
+ *   1 BLOCKING     ceil(64 stride / 1024) >  pref: blocking loads
+ *   2 PARTIAL      n_slots % 64 != 0: the last wave-batch is staged by the byte loop
+ *   3 META         a slot table (reads of unequal length)
+ *   4 SMALL_BLOCK  waves per block % 4 != 0: the equal split of a workgroup's wave-batches
+ *   5 IDLE         fewer wave-batches than waves: ceil(n_slots / 64) < grid x waves per block
+ *   6 MULTI        at least two wave-batches per wave on average: ceil(n_slots / 64) >= 2 x grid x waves per block
+ *   7 LOG          the launch had hit-log regions
+ * — and the shape of the last launch.  Counts are exact under concurrent launches; the last_* words are each those of some recent launch.
+ * NTC_ERR_ARG for a NULL out or row >= the table's rows: that is how a caller counts them. */
+typedef struct {
+    uint8_t multi, mode, pref, dump, tiled, one, sig, reserved;
+    uint64_t launches;
+    uint64_t regime[8];
+    uint32_t last_grid, last_wpb, last_stride, reserved2;
+    uint64_t last_n_slots;
+} ntc_k1_variant_info;
+int ntc_k1_variant_stats(uint32_t row, ntc_k1_variant_info *out);
 
 #ifdef __cplusplus
 }

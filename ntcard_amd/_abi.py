@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "ntc_signature_time", "ntc_signature_header", "ntc_signature_write", "ntc_signature_read",
     "ntc_signature_device", "ntc_signature_sort_time", "ntc_signature_sort_device", "ntc_signature_compare_device", "ntc_signature_matrix_device",
     "ntc_signature_gather_device",
+    "ntc_k1_variant_stats",
 ]
 
 
@@ -36,6 +37,21 @@ class NtcGatherRow(C.Structure):
         ("common", C.c_uint64),
         ("unique", C.c_uint64),
         ("unique_weight", C.c_uint64),
+    ]
+
+
+class NtcK1VariantInfo(C.Structure):
+    """ntc_k1_variant_info"""
+    _fields_ = [
+        ("multi", C.c_uint8), ("mode", C.c_uint8), ("pref", C.c_uint8), ("dump", C.c_uint8), ("tiled", C.c_uint8), ("one", C.c_uint8), ("sig", C.c_uint8),
+        ("reserved", C.c_uint8),
+        ("launches", C.c_uint64),
+        ("regime", C.c_uint64 * 8),
+        ("last_grid", C.c_uint32),
+        ("last_wpb", C.c_uint32),
+        ("last_stride", C.c_uint32),
+        ("reserved2", C.c_uint32),
+        ("last_n_slots", C.c_uint64),
     ]
 
 
@@ -180,6 +196,7 @@ def lib():
     L.ntc_hll_estimate.argtypes = [p, u32, C.POINTER(C.c_double)]
     L.ntc_hll_create_ex.argtypes = [C.POINTER(NtcHllConfig), C.POINTER(p)]
     L.ntc_hll_estimate_strand.argtypes = [p, u32, u32, C.POINTER(C.c_double)]
+    L.ntc_k1_variant_stats.argtypes = [u32, C.POINTER(NtcK1VariantInfo)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("ntc_abi_version", "ntc_max_k", "ntc_last_error", "ntc_destroy", "ntc_tiled_bytes"):

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/ntcard_hip.h"
 #include "nthash_tables.hpp"
 
 namespace ntc {
@@ -274,6 +275,10 @@ hipError_t set_hash_smem_limit(size_t smem);
 hipError_t launch_sketch_hf(const HfArgs& a, unsigned grid, unsigned waves_per_block, size_t smem, hipStream_t st);
 hipError_t launch_compact_dump(const uint64_t* full, const uint32_t* valid, uint64_t n_reads, uint32_t n_win, uint32_t max_win, uint64_t* out, uint32_t* count, hipStream_t st);
 hipError_t set_sketch_hf_smem_limit(size_t smem);
+// what launch_sketch_hf has dispatched for row `row` of K1's variant table (ntc_k1_variant_stats); false: the table has no such row
+constexpr int kK1Regimes = 8;
+static_assert(sizeof(ntc_k1_variant_info::regime) == kK1Regimes * sizeof(uint64_t), "ntc_k1_variant_info::regime");
+bool k1_variant_stats(uint32_t row, ntc_k1_variant_info& out);
 bool sketch_hf_deep_prefetch(uint32_t stride);
 hipError_t launch_hll_threshold(const uint32_t* regs, uint32_t n_regs, uint32_t* thr, hipStream_t st);
 hipError_t launch_finalize(const uint32_t* sketch, uint64_t n_per_sample, uint32_t* p_hist,

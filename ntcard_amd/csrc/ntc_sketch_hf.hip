@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <cstring>
 #include <type_traits>
 
 #include "ntc_kernels.hpp"
@@ -1000,6 +1002,51 @@ struct HfVariant {
 #define HF_ROW(multi, mode, pref, dump, tiled, one, sig) { multi, mode, pref, dump, tiled, one, sig, &sketch_hf_kernel<multi, mode, pref, dump, tiled, one, sig> },
 static const HfVariant kHfVariants[] = { HF_VARIANTS(HF_ROW) };
 #undef HF_ROW
+constexpr uint32_t kHfRows = sizeof kHfVariants / sizeof kHfVariants[0];
+
+// What launch_sketch_hf has dispatched, per row of the table (k1_variant_stats; process-wide, host only): engines launch from several threads, hence
+// relaxed atomics — a reader sees every count, and the last_* words of SOME launch each
+struct HfRowStats {
+	std::atomic<uint64_t> launches{0}, regime[kK1Regimes]{}, last_n_slots{0};
+	std::atomic<uint32_t> last_grid{0}, last_wpb{0}, last_stride{0};
+};
+static HfRowStats g_hf_stats[kHfRows];
+
+// the regimes of a launch, from the same words the kernel derives them from (nchunk, can_prefetch, nvalid, wpb % 4, the wave-batch shares)
+static void note_hf_launch(uint32_t row, const HfArgs& a, unsigned grid, unsigned wpb, int pref)
+{
+	const uint32_t nchunk = (64u * a.stride + 1023u) >> 10;
+	const uint64_t n_wb = (a.n_slots + 63) / 64, waves = (uint64_t)grid * wpb;
+	const bool in[kK1Regimes] = { nchunk <= (uint32_t)pref, nchunk > (uint32_t)pref, a.n_slots % 64 != 0, a.meta != nullptr,
+	                              wpb % 4u != 0u,           n_wb < waves,            n_wb >= 2 * waves,    a.log_regions != 0 };
+	HfRowStats& s = g_hf_stats[row];
+	constexpr auto relaxed = std::memory_order_relaxed;
+	s.launches.fetch_add(1, relaxed);
+	for (int i = 0; i < kK1Regimes; ++i)
+		if (in[i]) s.regime[i].fetch_add(1, relaxed);
+	s.last_grid.store(grid, relaxed);
+	s.last_wpb.store(wpb, relaxed);
+	s.last_stride.store(a.stride, relaxed);
+	s.last_n_slots.store(a.n_slots, relaxed);
+}
+
+bool k1_variant_stats(uint32_t row, ntc_k1_variant_info& o)
+{
+	if (row >= kHfRows) return false;
+	const HfVariant& v = kHfVariants[row];
+	const HfRowStats& s = g_hf_stats[row];
+	constexpr auto relaxed = std::memory_order_relaxed;
+	std::memset(&o, 0, sizeof o);
+	o.multi = v.multi, o.mode = (uint8_t)v.mode, o.pref = (uint8_t)v.pref, o.dump = v.dump, o.tiled = v.tiled, o.one = v.one, o.sig = v.sig;
+	o.launches = s.launches.load(relaxed);
+	for (int i = 0; i < kK1Regimes; ++i)
+		o.regime[i] = s.regime[i].load(relaxed);
+	o.last_grid = s.last_grid.load(relaxed);
+	o.last_wpb = s.last_wpb.load(relaxed);
+	o.last_stride = s.last_stride.load(relaxed);
+	o.last_n_slots = s.last_n_slots.load(relaxed);
+	return true;
+}
 
 hipError_t launch_sketch_hf(const HfArgs& a, unsigned grid, unsigned waves_per_block, size_t smem, hipStream_t st)
 {
@@ -1016,6 +1063,7 @@ hipError_t launch_sketch_hf(const HfArgs& a, unsigned grid, unsigned waves_per_b
 	const int pref = (mode == 0 && !dump && !sig && sketch_hf_deep_prefetch(a.stride) && waves_per_block <= 12) ? 16 : 10;
 	for (const HfVariant& v : kHfVariants)
 		if (v.multi == multi && v.mode == mode && v.pref == pref && v.dump == dump && v.tiled == tiled && v.one == one && v.sig == sig) {
+			note_hf_launch((uint32_t)(&v - kHfVariants), a, grid, waves_per_block, pref);
 			hipLaunchKernelGGL(v.fn, dim3(grid), dim3(64u * waves_per_block), smem, st, a);
 			return hipGetLastError();
 		}
@@ -1057,3 +1105,12 @@ hipError_t set_sketch_hf_smem_limit(size_t smem)
 }
 
 } // namespace ntc
+
+int ntc_internal_fail(int code, const char* fmt, ...); // ntc_lifecycle.hip: sets ntc_last_error()
+
+extern "C" int ntc_k1_variant_stats(uint32_t row, ntc_k1_variant_info* out)
+{
+	if (!out) return ntc_internal_fail(NTC_ERR_ARG, "ntc_k1_variant_stats: null argument");
+	if (!ntc::k1_variant_stats(row, *out)) return ntc_internal_fail(NTC_ERR_ARG, "ntc_k1_variant_stats: row %u: the table has fewer rows", row);
+	return 0;
+}

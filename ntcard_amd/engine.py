@@ -554,6 +554,20 @@ def hpc_compress_device(d_in_ptr, offsets, d_out_ptr, device=0, stream=None):
     return out
 
 
+K1_REGIMES = ("PREFETCH", "BLOCKING", "PARTIAL", "META", "SMALL_BLOCK", "IDLE", "MULTI", "LOG")  # ntc_k1_variant_info::regime, in order
+
+
+def k1_variant_stats():
+    """what the general kernel K1 has launched in this process, one dict per row of its table of instantiations: row (multi, mode, pref, dump, tiled, one,
+    sig), launches, regime {name: launches in it, K1_REGIMES}, last_grid, last_wpb, last_stride, last_n_slots (ntc_k1_variant_stats; host only)"""
+    L, out, info = _abi.lib(), [], _abi.NtcK1VariantInfo()
+    while L.ntc_k1_variant_stats(len(out), C.byref(info)) == 0:
+        out.append(dict(row=(bool(info.multi), info.mode, info.pref, bool(info.dump), bool(info.tiled), bool(info.one), bool(info.sig)),
+                        launches=info.launches, regime=dict(zip(K1_REGIMES, info.regime)), last_grid=info.last_grid, last_wpb=info.last_wpb,
+                        last_stride=info.last_stride, last_n_slots=info.last_n_slots))
+    return out
+
+
 def tiled_bytes(n_reads, read_len):
     """size of a batch in the tiled layout"""
     return int(_abi.lib().ntc_tiled_bytes(n_reads, read_len))
