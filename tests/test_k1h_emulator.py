@@ -7,12 +7,14 @@ import numpy as np
 import pytest
 
 import k1h_model as km
+import k1h_variant_cases as vc
 import orc
 from support import ALPHA, random_reads, tile_array
 
 
-def run(n, L, k, p_bad=0.0, r_bits=14, n_waves=2, seed=1, s_bits=7, gap=0, **kw):
-    arr = random_reads(np.random.default_rng(seed), n, L, p_bad)
+def run(n, L, k, p_bad=0.0, r_bits=14, n_waves=2, seed=1, s_bits=7, gap=0, arr=None, **kw):
+    """arr: the reads [n, L] themselves (a case of tests/k1h_variant_cases.py) instead of random_reads under `seed`"""
+    arr = random_reads(np.random.default_rng(seed), n, L, p_bad) if arr is None else arr
     res = km.run_k1h(tile_array(arr), n, L, k, r_bits=r_bits, n_waves=n_waves, s_bits=s_bits, gap=gap, **kw)
     reads = [arr[i].tobytes() for i in range(n)]
     fk, f1_sub = km.k1f_model(reads, L, k, r_bits, s_bits, res["dirty"], res["tie"], res["sus"], res["sus_overflow"], gap=gap)
@@ -110,6 +112,19 @@ def test_k1h_emulated_spaced_seeds(k, gap, L, s_bits):
 def test_k1h_emulated_other_k(k):
     """the library is built with every k of 12 .. 32 (gen_k1h.VARIANTS): phases (k - 1) mod 16 and table sizes the cases above do not touch"""
     run(2100, k + 29, k, 0.01, n_waves=2, seed=k)
+
+
+@pytest.mark.parametrize("c", [c for c in vc.EMU_CASES + vc.PLANT_CASES if c.strand == 0], ids=vc.case_id)
+def test_k1h_emulated_every_canonical_body(c):
+    """one case per canonical body of the case table, both sBits classes of every (k, gap) the library is built with — K1H_ASM_K32_G8_S8 and the class-8
+    bodies below k = 32, which no case above runs, among them — and the planted windows of sBits 24 at r_bits 14, the widest table word; what fails on a GPU in
+    tests/test_k1h_variants_gpu.py can be reproduced here"""
+    res = run(c.n, c.L, c.k, c.p_bad, r_bits=c.r_bits, s_bits=c.s_bits, gap=c.gap, arr=vc.reads_of(c))
+    assert len(res["sus"]) > 0 and not res["sus_overflow"]
+    if c.kind == "plant":  # the windows planted beside an N are suspects: K1f's verdict on the extra hash bits decides them
+        sus = {(int(t) * 2048 + (int(rw) & 2047), int(rw) >> 11) for _, t, rw, _ in res["sus"]}
+        beside = [(r, w) for r, w, _, what in vc.planted_reads(c)[1] if what in ("n_before", "n_behind")]
+        assert len(beside) == 12 and all(p in sus for p in beside)
 
 
 def test_k1h_generator_budgets():

@@ -8,6 +8,7 @@ import re
 import pytest
 
 import k1h_strand_model as ksm
+import k1h_variant_cases as vc
 import strand_model as sm
 from ntcard_amd import _abi
 from support import abi_config
@@ -68,6 +69,19 @@ def test_strand_k1h_emulated_direct_atomics(strand):
 def test_strand_k1h_emulated_odd_k(strand, k):
     """phases (k - 1) mod 16 the cases above do not touch, and the parity of the bit that wraps around in a walk step"""
     ksm.run(strand, 2100, k + 29, k, 0.01, seed=k)
+
+
+@pytest.mark.parametrize("c", [c for c in vc.EMU_CASES + vc.PLANT_CASES if c.strand != sm.CANONICAL], ids=vc.case_id)
+def test_strand_k1h_emulated_every_body(c):
+    """every one-strand body the library is built with, both sBits classes (the case table of tests/k1h_variant_cases.py; tests/test_k1h_variant_cases_host.py
+    proves the coverage): what depends on k — start chunk, phase, table groups, the wrap bit's parity in the reverse walk — at each k it belongs to; and the planted windows of sBits 24 at r_bits 14 (17 extra hash bits in the table word)"""
+    arr = vc.reads_of(c)
+    res = ksm.check(c.strand, [arr[i].tobytes() for i in range(c.n)], arr, c.n, c.L, c.k, c.r_bits, c.s_bits, c.gap, 2)
+    assert len(res["sus"]) > 0 and not res["sus_overflow"]
+    if c.kind == "plant":  # the windows planted beside an N are suspects: K1f's verdict on the extra hash bits decides them
+        sus = {(int(t) * 2048 + (int(rw) & 2047), int(rw) >> 11) for _, t, rw, _ in res["sus"]}
+        beside = [(r, w) for r, w, _, what in vc.planted_reads(c)[1] if what in ("n_before", "n_behind")]
+        assert len(beside) == 12 and all(p in sus for p in beside)
 
 
 @pytest.mark.parametrize("k,sb,gap", [(32, 7, 0), (12, 8, 2), (21, 8, 0)])

@@ -12,7 +12,7 @@ import pytest
 import orc
 import strand_model as sm
 from ntcard_amd import _abi
-from support import NTCARD, ROOT, abi_config, run_cli
+from support import ALPHA, NTCARD, ROOT, abi_config, gap_mask, random_reads, run_cli
 HEADER = os.path.join(ROOT, "include", "ntcard_hip.h")
 ERR_ARG = -1
 FWD, REV = 512, 1024
@@ -82,6 +82,37 @@ def test_the_gpu_tests_inputs_tell_the_strands_apart(name, masks, gap, s_bits):
                 assert sk[s][0][mi, 0].any() and sk[s][0][mi, 1].any(), (name, mi, s)
             for a, b in ((sm.CANONICAL, sm.FORWARD), (sm.CANONICAL, sm.REVERSE), (sm.FORWARD, sm.REVERSE)):
                 assert not np.array_equal(sk[a][0][mi], sk[b][0][mi]), (name, mi, a, b)
+
+
+@pytest.mark.parametrize("k", list(range(12, 33)))
+def test_array_form_is_window_values_window_by_window(k):
+    """strand_model.window_blocks (table look-ups over arr[n, L]) against window_values (one oracle call per window): which windows exist, and fs and rs
+    of each, for plain k and both -g masks; reads with lower case, U / u, N and every other byte of support.ALPHA, and the reference's table-slot bytes"""
+    rng = np.random.default_rng(k)
+    masks = ["1" * k] + [gap_mask(kk, g) for kk, g in ((12, 2), (32, 8)) if kk == k]
+    other = np.concatenate([ALPHA[10:], np.array([0, 1, 3, 4, 5, 7, 255], dtype=np.uint8)])  # NnRYKM.-* and bytes that are no letters
+    for mask in masks:
+        for L, p_bad in ((k, 0.02), (k + 1, 0.0), (k + 29, 0.05), (97, 0.01)):
+            arr = ALPHA[rng.integers(0, 10, size=(40, L))]  # ACGTacgtUu
+            arr = np.where(rng.random(arr.shape) < p_bad, other[rng.integers(0, len(other), size=arr.shape)], arr).astype(np.uint8)
+            fs, rs, ok = sm.array_window_values(arr, mask)
+            assert fs.shape == rs.shape == ok.shape == (40, L - k + 1)
+            for i in range(arr.shape[0]):
+                wf, wr, pos = sm.window_values(arr[i].tobytes(), mask)
+                assert np.array_equal(np.flatnonzero(ok[i]), pos), (mask, L, i)
+                assert np.array_equal(fs[i][ok[i]], wf) and np.array_equal(rs[i][ok[i]], wr), (mask, L, i)
+            assert p_bad == 0.0 or not ok.all()
+    # row blocks, reads shorter than k, reads padded to one length, and the sketches of all three strands in one pass
+    arr = random_reads(rng, 300, k + 5, 0.02)
+    whole = sm.array_window_values(arr, "1" * k)
+    parts = list(sm.window_blocks(arr, "1" * k, rows=64))
+    assert len(parts) == 5 and all(np.array_equal(np.concatenate([p[j] for p in parts]), whole[j]) for j in range(3))
+    assert sm.array_window_values(arr[:, :k - 1], "1" * k)[0].shape == (300, 0)
+    reads = [arr[i, :k + 5 - (i % 9)].tobytes() for i in range(300)]
+    for strand in (sm.CANONICAL, sm.FORWARD, sm.REVERSE):
+        got = sm.array_sketches(sm.pad_reads(reads), "1" * k, [(strand, 10, 7)])[strand, 10, 7]
+        want = sm.model_sketch(reads, ["1" * k], strand, 10, 7)
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and want[0].any()
 
 
 # ---- ABI ----
