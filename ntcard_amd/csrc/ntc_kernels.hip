@@ -12,22 +12,14 @@
 #include <stdint.h>
 
 #include "ntc_kernels.hpp"
+#include "ntc_tile_bits.hpp"
 
 namespace ntc {
 
 // ---- small device helpers ---------------------------------------------------------------------
-__device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh)
-{
-	return __builtin_amdgcn_alignbit(hi, lo, sh); // ({hi,lo} >> sh)[31:0]
-}
-__device__ __forceinline__ uint32_t alignbyte(uint32_t hi, uint32_t lo, uint32_t sh)
-{
-	return __builtin_amdgcn_alignbyte(hi, lo, sh); // ({hi,lo} >> 8*sh)[31:0]
-}
-__device__ __forceinline__ uint32_t perm(uint32_t s0, uint32_t s1, uint32_t sel)
-{
-	return __builtin_amdgcn_perm(s0, s1, sel); // byte i = {s0,s1}.byte[sel.byte[i]], 0-3 -> s1
-}
+using tilebits::alignbit;
+using tilebits::alignbyte;
+using tilebits::perm;
 
 // v_perm tables indexed by (byte & 7): 1:A 3:C 7:G 4:T 5:U, 0/2/6: not a base.
 // (the same low-3-bit trick the reference uses for complements, nthash.hpp:16,32)

@@ -1,4 +1,5 @@
-// ntc_tile_bits.hpp — byte-level helpers shared by the kernels that read the TILED slot layout (ntc_sketch_ts.hip, ntc_sketch_k1h.hip):
+// ntc_tile_bits.hpp — the one-instruction wrappers every kernel file shares (funnel shifts, v_perm, ballot, a lane's rank in a ballot,
+// readfirstlane), and the byte-level helpers of the kernels that read the TILED slot layout (ntc_sketch_k1h.hip):
 // 16 raw bytes -> 2 bits per base, and the exact mask of the bytes that are no ACGTU letter (nthash.hpp:31-64 restricted to letters).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,12 +8,15 @@
 namespace ntc {
 namespace tilebits {
 
-__device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
-__device__ __forceinline__ uint32_t perm(uint32_t s0, uint32_t s1, uint32_t sel) { return __builtin_amdgcn_perm(s0, s1, sel); }
+__device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); } // ({hi,lo} >> sh)[31:0]
+__device__ __forceinline__ uint32_t alignbyte(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbyte(hi, lo, sh); } // ({hi,lo} >> 8*sh)[31:0]
+__device__ __forceinline__ uint32_t perm(uint32_t s0, uint32_t s1, uint32_t sel) { return __builtin_amdgcn_perm(s0, s1, sel); } // byte i = {s0,s1}.byte[sel.byte[i]], 0-3 -> s1
 __device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 __device__ __forceinline__ uint32_t bfi(uint32_t m, uint32_t x, uint32_t y) { return (x & m) | (y & ~m); } // v_bfi_b32
+// rank of this lane among the set bits of a ballot: the set bits below it
 __device__ __forceinline__ uint32_t mbcnt(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t rfl64(uint64_t v) { return rfl((uint32_t)v) | ((uint64_t)rfl((uint32_t)(v >> 32)) << 32); }
 
 typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
 

@@ -75,8 +75,8 @@ inline void build_tables(unsigned k, HashTables& t)
 	}
 }
 
-// Strand registers (device layout) of the hash of k consecutive 'A' bases — the state the tuned
-// kernel starts every read from (see ntc_sketch_fast.hip): {flo, fB, fHd, rlo, rB, rHd}.
+// Strand registers (device layout) of the hash of k consecutive 'A' bases — the state a rolling walk
+// starts every read from, with 'A' as the outgoing base of its first k steps: {flo, fB, fHd, rlo, rB, rHd}.
 inline void poly_a_state(unsigned k, uint32_t out[6])
 {
 	uint64_t fh = 0, rh = 0;
