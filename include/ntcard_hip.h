@@ -81,9 +81,11 @@ typedef struct {
                                       reads with non-ACGTU bytes are then shared by several batches instead of run per batch: the fix-up
                                       kernels K1f behind up to 8 launches of the one-wave-per-tile kernel K1h.  Since ABI 6 the HASH launches wait as
                                       well: up to 8 tiled batches (ntc_submit_tiled_device / _ragged_device) are hashed by one launch per k, started
-                                      when the eighth arrives or when ntc_flush / ntc_sync / ntc_finish / ntc_reset / a merge / ntc_device_state needs
-                                      the counters — work submitted under this flag is only guaranteed to have been ENQUEUED after one of those calls
-                                      (a small batch then costs its share of a large launch instead of a launch of its own).  Without the flag a
+                                      when the eighth arrives or when ntc_flush / ntc_sync / ntc_finish / ntc_reset / ntc_merge_devices / ntc_device_state /
+                                      the log calls need the counters — work submitted under this flag is only guaranteed to have been ENQUEUED after one of
+                                      those calls (a small batch then costs its share of a large launch instead of a launch of its own).  ntc_merge_counters
+                                      does NOT start them: it adds its image into the counters, the waiting batches are added behind it in stream order, and
+                                      the sums commute (tests/test_engine_seq_gpu.py pins the launch count across it and the result after it).  Without the flag a
                                       buffer may be reused as soon as the stream has passed the submit call. */
 #define NTC_FLAG_REQUIRE_TILED 64u  /* validation: a tiled batch must be served by the tiled kernels for EVERY k of the list, else ntc_submit_tiled_device fails */
 /* ONE STRAND instead of the canonical k-mer (additive to ABI 6: two flag bits and ntc_hash_dump_strand_device; ntc_config and NTC_ABI_VERSION are unchanged).

@@ -22,6 +22,19 @@ def dev(a):
     return torch.from_numpy(a).cuda()
 
 
+def upload(a, stream=None, into=None):
+    """numpy array (or a pinned host tensor) -> device tensor by a copy ON `stream` (a torch.cuda.Stream; None: the current one) that the host does not wait
+    for: whatever reads the tensor must be ordered behind that stream.  into: an existing device tensor to overwrite instead of a new one.
+    -> (tensor, the pinned host tensor the copy reads: keep it until the stream has passed).  tests/test_engine_seq_gpu.py (test_shared_helpers) pins it
+    and tests/devview.py's DevArray, which need a device."""
+    pinned = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
+    assert pinned.is_pinned()
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        t = into if into is not None else torch.empty(pinned.shape, dtype=pinned.dtype, device="cuda")
+        t.copy_(pinned, non_blocking=True)
+    return t, pinned
+
+
 def on_device(seqs_or_buf, offs=None, lead=3):
     """sequences (a list of bytes; or the sequences [offs[i], offs[i + 1]) of a uint8 array) behind one another in one device buffer, `lead` bytes in
     front (start offsets of any alignment) and one behind, all '#' -> (tensor, host offsets)"""

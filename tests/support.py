@@ -142,6 +142,29 @@ def tile(reads, read_len, unused=ord("A")):
     return tile_array(a)
 
 
+def tile_ragged(reads, n_chunks):
+    """one bin of a ragged read set (reads of 16 n_chunks - 15 .. 16 n_chunks bases) -> (tiles uint8, tails uint32 [n_tiles, 16]): every tile sorted longest
+    read first, tails[t, d] = the reads of tile t with more than d bases in their last piece (include/ntcard_hip.h: ntc_submit_tiled_ragged_device)"""
+    lens = np.array([len(r) for r in reads], dtype=np.int64)
+    assert lens.size and lens.min() > 16 * (n_chunks - 1) and lens.max() <= 16 * n_chunks
+    order = np.argsort(-lens, kind="stable")
+    tiles = tile([reads[i] for i in order], 16 * n_chunks)
+    last = np.full((len(reads) + TILE - 1) // TILE * TILE, 0, dtype=np.int64)
+    last[:lens.size] = lens[order] - 16 * (n_chunks - 1)
+    tails = (last.reshape(-1, TILE, 1) > np.arange(16).reshape(1, 1, 16)).sum(axis=1).astype(np.uint32)
+    return tiles, tails
+
+
+def spans_of(reads, lead=5, gap=3, fill=ord("#")):
+    """reads as spans of one host buffer, `gap` bytes of `fill` between them (ntc_submit_spans) -> (buf uint8, starts uint64, lens uint32)"""
+    lens = np.array([len(r) for r in reads], dtype=np.uint32)
+    starts = lead + np.concatenate([[0], np.cumsum(lens[:-1].astype(np.uint64) + np.uint64(gap))]).astype(np.uint64)
+    buf = np.full(int(starts[-1]) + int(lens[-1]) + gap, fill, dtype=np.uint8)
+    for s, r in zip(starts.tolist(), reads):
+        buf[s:s + len(r)] = np.frombuffer(r, dtype=np.uint8)
+    return buf, starts, lens
+
+
 def offsets_of(lens_or_seqs, lead=0):
     """uint64 offsets [n + 1] of sequences (or of their lengths) laid behind one another, the first one at `lead`"""
     lens = lens_or_seqs if isinstance(lens_or_seqs, np.ndarray) else [x if isinstance(x, (int, np.integer)) else len(x) for x in lens_or_seqs]

@@ -81,6 +81,26 @@ def test_tile_pads_a_shorter_read_with_a_base():
     assert np.all(t[0, :, 3:] == 0x23)
 
 
+@pytest.mark.parametrize("n,chunks", [(1, 1), (2047, 3), (2049, 7), (5000, 10)])
+def test_tile_ragged_is_tile_reads_ragged(n, chunks):
+    rng = np.random.default_rng(n + chunks)
+    full = support.random_reads(rng, n, 16 * chunks, 0.02)
+    lens = rng.integers(16 * chunks - 15, 16 * chunks + 1, size=n)
+    reads = [full[i, :lens[i]].tobytes() for i in range(n)]
+    tiles, tails = support.tile_ragged(reads, chunks)
+    want_tiles, want_tails, _ = nt.tile_reads_ragged(reads, chunks)
+    assert tails.dtype == np.uint32 and np.array_equal(tails, want_tails) and np.array_equal(tiles, want_tiles)
+    assert int(tails[:, 0].sum()) == n and np.all(np.diff(tails.astype(np.int64), axis=1) <= 0)
+
+
+def test_spans_round_trip():
+    reads = [b"ACGT", b"", b"N", b"ACGTACGTA"]
+    buf, starts, lens = support.spans_of(reads, lead=2, gap=1)
+    assert starts.dtype == np.uint64 and lens.dtype == np.uint32 and starts.tolist() == [2, 7, 8, 10] and lens.tolist() == [4, 0, 1, 9]
+    assert [buf[s:s + n].tobytes() for s, n in zip(starts.tolist(), lens.tolist())] == reads
+    assert buf.tobytes() == b"##ACGT##N#ACGTACGTA#"
+
+
 def test_row_slots_round_trip():
     rng = random.Random(4)
     reads = [support.rseq(rng, n, pn=0.1) for n in (0, 1, 7, 8, 150, 151, 152)]
