@@ -383,6 +383,46 @@ typedef struct {
 int ntc_signature_gather_device(int32_t device, void *stream, const void *d_query_u64, const void *d_query_counts_u32, uint64_t nq, uint32_t n_refs,
                                 const void *const *d_refs_u64, const uint64_t *n, uint64_t threshold, ntc_gather_row *rows, uint32_t rows_cap,
                                 uint32_t *n_rows, uint64_t *unassigned, uint64_t *unassigned_weight);
+/* SET ALGEBRA AND SPECTRUM (additive to ABI 6: three calls and three constants; NTC_ABI_VERSION and every other declaration are unchanged).  Engine-less
+ * device tools like the ones above: synchronous, on the caller's `stream`, and they free their scratch.  New signatures out of existing ones, and the
+ * abundance spectrum of one, without an engine.  Every result is an exact integer.
+ *   ntc_signature_union_device   1 <= n_lists <= 1024; d_hashes_u64 and n are HOST arrays, list i has n[i] strictly ascending DEVICE hashes (NULL allowed
+ *       where n[i] == 0); d_counts_u32 is NULL, or a HOST array whose entry i is NULL or a DEVICE array of n[i] counts — NULL means 1 each.  The result: the
+ *       distinct hashes of all lists, strictly ascending, each with min(the sum of its counts over the lists, 2^32 - 1).  A hash of 0 is a value like any
+ *       other here, as for compare.  The sum of the n[i] is below 2^32 (the sort's limit).  The lists are gathered into one pair buffer, sorted
+ *       (ntc_signature_sort_device's kernels), and every head of a run of equal hashes — at most n_lists long — adds up its run; n_lists == 1 is a checked
+ *       copy.  Scratch: 25 B per entry of the input (two pair buffers of 12 B — one up to 4096 entries —, a byte of flag), the sort's histograms and 4 B
+ *       per 2048 entries.  The host waits three times: for the sort's digit histograms (above 4096 entries), in front of the scatter, and at the end.
+ *   ntc_signature_select_device  an entry (h, c) of A (na strictly ascending DEVICE hashes; c = 1 when d_ca_u32 == NULL) is kept iff it passes the count
+ *       test — min_count <= c, and c <= max_count unless max_count == 0 (no upper bound) — and the membership test: the rule of `mode` over the n_refs
+ *       reference lists (0 <= n_refs <= 1024; d_refs_u64 and n as above, both may be NULL with 0 references; na and every n[i] below 2^32).  Kept entries
+ *       keep A's order, hashes and counts.  An empty reference holds nothing: under NTC_SIG_IN_ALL nothing is kept, under NTC_SIG_IN_NONE it excludes
+ *       nothing.  So intersect is IN_ALL, subtract IN_NONE, and the abundance filter is n_refs == 0 with bounds.  NTC_ERR_ARG for min_count > max_count != 0
+ *       or a mode above 2.  A lane per entry of A searches reference after reference and leaves at the first that decides.  Scratch: a byte per entry of A
+ *       and 4 B per 2048 entries.  The host waits twice: in front of the scatter, and at the end.
+ *   Output of both: d_out_u64 has room for cap hashes, d_out_counts_u32 (may be NULL: hashes only) for cap counts, *n_out = the size of the result.
+ *       d_out_u64 == NULL asks for the size alone and is legal only with cap == 0 and d_out_counts_u32 == NULL: NTC_OK, *n_out is set, nothing else is
+ *       written.  A cap smaller than the result: NTC_ERR_ARG, the message names the needed size, nothing is written; the sum of the n[i] (union) and na
+ *       (select) are always enough.  An output array that overlaps an input array: NTC_ERR_ARG, decided from the pointer ranges.  NTC_ERR_ARG before the
+ *       device is touched also for a NULL n_out, a NULL table or n with lists to read, a NULL list with a length, a length or a sum >= 2^32, n_lists
+ *       outside 1 .. 1024, n_refs > 1024.  Ascent of every input list is checked once on the device: NTC_ERR_ARG names the list ("A", "list i",
+ *       "reference i") and an offending entry.  NTC_ERR_MEMORY when the scratch cannot be had.  On ANY error every output is left alone: both arrays and
+ *       *n_out.
+ *   ntc_signature_hist_device    the abundance spectrum of a signature's n DEVICE counts (any n): hist_out, a HOST array [cov_max + 2], gets
+ *       hist_out[v] = the entries with count v for 0 <= v <= cov_max and hist_out[cov_max + 1] = the entries with a larger count; *weight_out (may be
+ *       NULL) = the sum of the counts.  The spectrum of the SAMPLED distinct k-mers, exact and free of collisions: what the estimator's f[] estimates,
+ *       scaled by the sampling rate.  1 <= cov_max <= 65535.  NTC_ERR_ARG for a NULL hist_out, a cov_max outside that range or a NULL d_counts_u32 with
+ *       n != 0, all before the device is touched; n == 0 touches no device.  One launch, one wait; scratch (cov_max + 3) x 8 B. */
+#define NTC_SIG_IN_ALL  0u   /* keep an entry of A iff every reference holds it (no references: every entry) */
+#define NTC_SIG_IN_NONE 1u   /* ... iff no reference holds it                                               */
+#define NTC_SIG_IN_ANY  2u   /* ... iff at least one reference holds it (no references: none)               */
+int ntc_signature_union_device(int32_t device, void *stream, uint32_t n_lists, const void *const *d_hashes_u64, const void *const *d_counts_u32,
+                               const uint64_t *n, void *d_out_u64, void *d_out_counts_u32, uint64_t cap, uint64_t *n_out);
+int ntc_signature_select_device(int32_t device, void *stream, const void *d_a_u64, const void *d_ca_u32, uint64_t na, uint32_t n_refs,
+                                const void *const *d_refs_u64, const uint64_t *n, uint32_t mode, uint32_t min_count, uint32_t max_count, void *d_out_u64,
+                                void *d_out_counts_u32, uint64_t cap, uint64_t *n_out);
+int ntc_signature_hist_device(int32_t device, void *stream, const void *d_counts_u32, uint64_t n, uint32_t cov_max, uint64_t *hist_out,
+                              uint64_t *weight_out);
 /* A signature FILE (`ntcard --signature`, bin/ntsig): little-endian; the 8 bytes "NTCSIG1\0", uint32 k, gap, strand, hpc, s_bits, mask_len, uint64 n, the mask
  * (mask_len bytes '0' / '1', all '1' for plain k; zero-padded to a multiple of 8), uint64 hashes[n], uint32 counts[n].  The header says how the file was
  * counted: two files compare only when they agree in everything but n.  Pure host functions.

@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "ntc_signature_time", "ntc_signature_header", "ntc_signature_write", "ntc_signature_read",
     "ntc_signature_device", "ntc_signature_sort_time", "ntc_signature_sort_device", "ntc_signature_compare_device", "ntc_signature_matrix_device",
     "ntc_signature_gather_device",
+    "ntc_signature_union_device", "ntc_signature_select_device", "ntc_signature_hist_device",
     "ntc_k1_variant_stats",
 ]
 
@@ -166,6 +167,9 @@ def lib():
     L.ntc_signature_matrix_device.argtypes = [i32, p, u32, C.POINTER(p), C.POINTER(u64), p]
     L.ntc_signature_gather_device.argtypes = [i32, p, p, p, u64, u32, C.POINTER(p), C.POINTER(u64), u64, C.POINTER(NtcGatherRow), u32, C.POINTER(u32),
                                               C.POINTER(u64), C.POINTER(u64)]
+    L.ntc_signature_union_device.argtypes = [i32, p, u32, C.POINTER(p), C.POINTER(p), C.POINTER(u64), p, p, u64, C.POINTER(u64)]
+    L.ntc_signature_select_device.argtypes = [i32, p, p, p, u64, u32, C.POINTER(p), C.POINTER(u64), u32, u32, u32, p, p, u64, C.POINTER(u64)]
+    L.ntc_signature_hist_device.argtypes = [i32, p, p, u64, u32, p, C.POINTER(u64)]
     L.ntc_sync.argtypes = [p]
     L.ntc_finish.argtypes = [p, p, p, p]
     L.ntc_merge_counters.argtypes = [p, p, p]

@@ -3,7 +3,7 @@
 // ntc_submit.hip: host packing, length bins, the staging pool; ntc_lifecycle.hip: create .. finish and the queries; ntc_merge.hip: multi-GPU merge
 // and log exchange; ntc_device_tools.hip: the entry points that need no engine.  Signatures: ntc_signature.hip: the container's kernels, the engine's
 // glue and the entry points that take an engine; those that need none sit with their kernels — ntc_sig_sort.hip: sort; ntc_sig_lists.hip: SigLists (lists on the
-// device, their ascent check), compare, matrix; ntc_sig_gather.hip: gather; ntc_sig_device.hpp is what these four share; ntc_sig_file.cpp: the signature file
+// device, their ascent check), compare, matrix; ntc_sig_gather.hip: gather; ntc_sig_algebra.hip: union, select, hist; ntc_sig_device.hpp is what these five share; ntc_sig_file.cpp: the signature file
 // format and the host compare, plain host C++ like ntc_estimator.cpp.
 //
 // Host-side mirror of the reference seam B2: ntc_create = the allocation/zeroing main() does (ntcard.cpp:433-439),

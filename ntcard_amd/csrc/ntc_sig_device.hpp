@@ -1,6 +1,6 @@
-// ntc_sig_device.hpp — what the signature translation units share (ntc_signature.hip, ntc_sig_sort.hip, ntc_sig_lists.hip, ntc_sig_gather.hip; DESIGN.md §4
-// "Signatures"): the wave helpers of their kernels, the clamp of their grids, and SigLists, the owner of "lists on the device" under compare, matrix and
-// gather.  Vector stores and plain C++ only.
+// ntc_sig_device.hpp — what the signature translation units share (ntc_signature.hip, ntc_sig_sort.hip, ntc_sig_lists.hip, ntc_sig_gather.hip, ntc_sig_algebra.hip; DESIGN.md §4
+// "Signatures"): the wave helpers of their kernels, the clamp of their grids, and SigLists, the owner of "lists on the device" under compare, matrix,
+// gather and the set algebra.  Vector stores and plain C++ only.
 #pragma once
 #include "ntc_engine.hpp"
 
@@ -41,6 +41,43 @@ __device__ __forceinline__ uint64_t list_lower_bound(const unsigned long long* _
 			hi = mid;
 	}
 	return lo;
+}
+
+// h[d] += 1 for every valid lane (whole waves call this).  The lanes that hold the first lane's d send one add: a value most lanes agree in — a signature's top
+// bits, a nearly full bin, the count 1 of a spectrum — is not 64 adds to one LDS address
+__device__ __forceinline__ void hist_add(uint32_t* h, uint32_t d, bool valid)
+{
+	const uint32_t first = __builtin_amdgcn_readfirstlane(d);
+	const uint64_t same = __builtin_amdgcn_ballot_w64(valid && d == first);
+	if (!valid) return;
+	if (d != first)
+		atomicAdd(h + d, 1u);
+	else if (lanes_below(same) == 0u)
+		atomicAdd(h + d, (uint32_t)__popcll(same));
+}
+
+// exclusive prefix sum of v over a workgroup of 256 threads; total = the sum.  wsum: 4 words of LDS, free again on return
+__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* wsum, uint32_t& total)
+{
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	uint32_t inc = v;
+#pragma unroll
+	for (uint32_t o = 1; o < 64u; o <<= 1) {
+		const uint32_t t = (uint32_t)__shfl_up((int)inc, o);
+		if (lane >= o) inc += t;
+	}
+	if (lane == 63u) wsum[wave] = inc;
+	__syncthreads();
+	uint32_t pre = 0;
+	total = 0;
+#pragma unroll
+	for (uint32_t w = 0; w < 4u; ++w) {
+		const uint32_t s = wsum[w];
+		pre += w < wave ? s : 0u;
+		total += s;
+	}
+	__syncthreads();
+	return pre + inc - v;
 }
 
 // workgroups of 256 threads for n entries, one at least and `cap` at most (the kernel walks the rest in a grid-stride loop)

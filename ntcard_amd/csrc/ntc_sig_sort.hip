@@ -32,18 +32,7 @@ static_assert(kSortThreads == kSortBins, "a thread per bin");
 
 __device__ __forceinline__ uint32_t digit_of(unsigned long long k, uint32_t shift) { return (uint32_t)(k >> shift) & (kSortBins - 1u); }
 
-// h[d] += 1 for every valid lane (whole waves call this).  The lanes that hold the first lane's digit send one add: a digit most keys agree in — a signature's top
-// bits, a nearly full bin — is not 64 adds to one LDS address
-__device__ __forceinline__ void hist_add(uint32_t* h, uint32_t d, bool valid)
-{
-	const uint32_t first = __builtin_amdgcn_readfirstlane(d);
-	const uint64_t same = __builtin_amdgcn_ballot_w64(valid && d == first);
-	if (!valid) return;
-	if (d != first)
-		atomicAdd(h + d, 1u);
-	else if (lanes_below(same) == 0u)
-		atomicAdd(h + d, (uint32_t)__popcll(same));
-}
+// (hist_add — one add for the lanes that hold the first lane's digit — and block_scan are in ntc_sig_device.hpp: the set algebra uses them too)
 
 // a key's position: the counter of its digit in its wave's row + the valid lanes below it with the same digit; the lowest of them moves the counter past all
 // of them.  Whole waves call this; the row is the calling wave's alone (its lanes read it in one instruction and one lane per digit writes it in a later one)
@@ -64,29 +53,7 @@ __device__ __forceinline__ uint32_t wave_rank(volatile uint32_t* row, uint32_t d
 	return old + below;
 }
 
-// exclusive prefix sum of v over the workgroup's 256 threads; total = the sum.  wsum: kSortWaves words of LDS, free again on return
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* wsum, uint32_t& total)
-{
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	uint32_t inc = v;
-#pragma unroll
-	for (uint32_t o = 1; o < 64u; o <<= 1) {
-		const uint32_t t = (uint32_t)__shfl_up((int)inc, o);
-		if (lane >= o) inc += t;
-	}
-	if (lane == 63u) wsum[wave] = inc;
-	__syncthreads();
-	uint32_t pre = 0;
-	total = 0;
-#pragma unroll
-	for (uint32_t w = 0; w < kSortWaves; ++w) {
-		const uint32_t s = wsum[w];
-		pre += w < wave ? s : 0u;
-		total += s;
-	}
-	__syncthreads();
-	return pre + inc - v;
-}
+static_assert(kSortWaves == 4 && kSortThreads == 256, "block_scan (ntc_sig_device.hpp) scans a workgroup of four waves");
 
 __global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(const unsigned long long* __restrict__ keys, uint64_t n, uint32_t* __restrict__ ghist)
 {

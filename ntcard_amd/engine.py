@@ -483,6 +483,60 @@ def signature_gather_device(ptr_q, ptr_counts_q, nq, ptrs, ns, threshold=1, max_
     return rows[:n_rows.value].copy(), rest.value, rest_w.value
 
 
+def _device_pairs_out(call, device):
+    """the output protocol of union and select: call(d_hashes, d_counts, cap, n_out) once for the size and once into fresh torch tensors
+    -> (hashes torch.int64[n] — the uint64 values' bits —, counts torch.int32[n] — uint32 likewise —, n)"""
+    import torch
+    n = C.c_uint64()
+    check(call(None, None, 0, C.byref(n)))
+    cap = n.value
+    dev = torch.device("cuda", device)
+    h = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+    c = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    check(call(C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), cap, C.byref(n)))
+    return h[:n.value], c[:n.value], n.value
+
+
+def signature_union_device(ptrs, count_ptrs, ns, device=0, stream=None):
+    """the union of the device lists ptrs[i] of ns[i] strictly ascending uint64 each; count_ptrs: None, or per list a device uint32 array or None / 0
+    (1 each) -> (hashes, counts, n) as Engine.signature_device gives them: the distinct hashes ascending, counts added and saturating at 2^32 - 1;
+    synchronous (ntc_signature_union_device)"""
+    k, arr, n = _device_lists(ptrs, ns)
+    carr = None
+    if count_ptrs is not None:
+        assert len(count_ptrs) == k
+        carr = (C.c_void_p * max(k, 1))(*[C.c_void_p(int(p)) if p else None for p in count_ptrs])
+    st = C.c_void_p(stream) if stream else None
+    return _device_pairs_out(lambda h, c, cap, n_out: _abi.lib().ntc_signature_union_device(device, st, k, arr, carr, n, h, c, cap, n_out), device)
+
+
+_SELECT_MODES = {"all": 0, "none": 1, "any": 2}  # NTC_SIG_IN_ALL, _NONE, _ANY
+
+
+def signature_select_device(ptr_a, ptr_ca, na, ptrs, ns, mode="all", min_count=0, max_count=0, device=0, stream=None):
+    """the entries of the device signature A (na strictly ascending uint64 hashes; counts uint32, or None / 0: 1 each) that pass the count test
+    (min_count <= c, and c <= max_count unless max_count is 0) and the membership rule over the device lists ptrs[i] of ns[i] strictly ascending uint64 each:
+    mode "all" — every list holds the hash (intersect) —, "none" — no list does (subtract) —, "any" — at least one does -> (hashes, counts, n) in A's
+    order; synchronous (ntc_signature_select_device)"""
+    k, arr, n = _device_lists(ptrs, ns)
+    st = C.c_void_p(stream) if stream else None
+    a, ca = (C.c_void_p(ptr_a) if ptr_a else None), (C.c_void_p(ptr_ca) if ptr_ca else None)
+    m = _SELECT_MODES[mode]
+    return _device_pairs_out(lambda h, c, cap, n_out: _abi.lib().ntc_signature_select_device(device, st, a, ca, int(na), k, arr if k else None, n if k else None, m,
+                                                                                               int(min_count), int(max_count), h, c, cap, n_out), device)
+
+
+def signature_hist_device(ptr_counts, n, cov_max=1000, device=0, stream=None):
+    """the abundance spectrum of n device counts (uint32) -> (hist np.uint64[cov_max + 2], weight np.uint64): hist[v] = the entries with count v,
+    hist[cov_max + 1] = those with a larger count, weight = the sum of the counts; synchronous (ntc_signature_hist_device)"""
+    cov_max = int(cov_max)
+    hist = np.zeros(max(cov_max, 0) + 2, dtype=np.uint64)
+    w = C.c_uint64()
+    check(_abi.lib().ntc_signature_hist_device(device, C.c_void_p(stream) if stream else None, C.c_void_p(ptr_counts) if ptr_counts else None, int(n), cov_max,
+                                               _np_ptr(hist), C.byref(w)))
+    return hist, np.uint64(w.value)
+
+
 def signature_write(path, header, hashes, counts):
     """a signature file; header: dict(k, gap, strand, hpc, s_bits, mask) as Engine.signature_header() gives it (ntc_signature_write)"""
     hs = np.ascontiguousarray(hashes, dtype=np.uint64)
