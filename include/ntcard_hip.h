@@ -442,6 +442,59 @@ int ntc_signature_read(const char *path, ntc_sig_header *h, uint64_t *hashes, ui
 /* the header of plane `plane` of a signature engine (k, gap, mask, strand, hpc, s_bits; n = 0): what ntc_signature_write needs beside the pairs */
 int ntc_signature_header(ntc_engine *e, uint32_t plane, ntc_sig_header *h);
 
+/* BLOOM FILTERS of EVERY k-mer (additive to ABI 6: nine calls, one constant, one struct; NTC_ABI_VERSION and every other declaration are unchanged).
+ * What ntCard's F0 is for: the filter a downstream tool sizes from the `.hist` file, built and queried by the same ntHash walk.  The layout is the
+ * reference's vendor/ntHash/lib/BloomFilter.hpp: position loc_i = h_i % m_bits, bit 7 - loc % 8 of byte loc / 8, h_0 the window's value and
+ * h_i = (t ^ t >> 27), t = h_0 * (i ^ k * multiSeed) for 1 <= i < n_hash (nthash.hpp:381-390).  Engine-less device tools like the signature tools above:
+ * synchronous, on the caller's `stream`, and they free their scratch.
+ *   The filter    caller-owned DEVICE memory: (m_bits + 7) / 8 bytes rounded up to a multiple of 4, 4-byte aligned, zeroed by the caller before the
+ *       first insert.  The bits from m_bits on (the padding) stay zero.  1 <= m_bits < 2^40, 1 <= n_hash <= 32, 1 <= k <= ntc_max_k().
+ *   The input     as for ntc_hpc_compress_device: d_bases DEVICE bytes of any alignment, offsets a HOST array of n_seqs + 1 non-decreasing values,
+ *       sequence i = d_bases[offsets[i], offsets[i + 1]); offsets[0] need not be 0, empty sequences are legal, n_seqs and the byte range need not fit
+ *       32 bits (at most 2^43 bytes in one call).  A window [p, p + k) counts iff it lies inside one sequence and every byte is one of A C G T U, either
+ *       case — the windows ntHashIterator yields on text (the control bytes 1, 3, 4, 5, 7 that the reference's seed table also maps are NOT bases
+ *       here).  A sequence shorter than k contributes nothing.  strand: 0 canonical min(fh, rh), 1 forward fh, 2 reverse rh (the numbers of
+ *       NTC_FLAG_STRAND_*).  Homopolymer compression is not a flag here: a caller who wants it runs ntc_hpc_compress_device first and passes its output.
+ *   ntc_bloom_size           pure host: m = ceil(-n_distinct * n_hash / ln(1 - fpr^(1 / n_hash))) rounded up to a multiple of 64.  NTC_ERR_ARG for
+ *       n_distinct == 0, n_hash outside 1 .. 32, fpr outside (0, 1), a NULL m_bits or a result of 2^40 or more.
+ *   ntc_bloom_insert_device  sets the n_hash bits of every window; *n_windows = the windows inserted (may be NULL).  The byte range is cut into blocks
+ *       of NTC_BLOOM_BLOCK window starts, counted from offsets[0]; a workgroup stages its block's bytes in LDS and a lane rolls over 16 consecutive
+ *       windows.  A bit that a plain load already finds set costs no atomic.  Scratch: the offsets (8 B per sequence) and 8 B.
+ *   ntc_bloom_query_device   d_windows_u32[i] = the windows of sequence i, d_hits_u32[i] = those whose n_hash bits are all set; both DEVICE arrays of
+ *       n_seqs uint32, zeroed by the call (a sequence of 2^32 windows or more wraps).  Exact integers: the same on every run.
+ *   ntc_bloom_insert_hashes_device / ntc_bloom_query_hashes_device  the same bit arithmetic on n GIVEN h_0 values (DEVICE uint64), without hashing:
+ *       a signature's hashes go in this way.  d_flags_u8[i] = 1 iff all n_hash bits of d_h0_u64[i] are set, else 0.  k enters h_i only.
+ *   ntc_bloom_popcount_device  *pop = the set bits among the first m_bits; NTC_ERR_STATE when a padding bit is set (then it is no filter of m_bits).
+ *   ntc_bloom_or_device      d_dst |= d_src, two filters of the same m_bits (shards of one input, peers' filters); the padding is OR-ed too.
+ * Before the device is touched, NTC_ERR_ARG for: a NULL pointer that is needed (the filter; offsets; d_bases with bytes to read; the outputs of a query;
+ * d_h0_u64 with n != 0; pop), a filter that is not 4-byte aligned, offsets that decrease, k, n_hash, m_bits or strand out of range.  NTC_ERR_MEMORY when
+ * the scratch cannot be had.  On any error nothing is written.
+ * A filter FILE (bin/ntbloom): the 8 bytes "NTCBF1\0\0", the header below little-endian, then the reference's byte image — (m_bits + 7) / 8 bytes, as
+ * BloomFilter::storeFilter writes them.  Pure host functions.
+ *   ntc_bloom_write  writes path + ".part" and renames it when it is whole, so a failure leaves nothing behind; NTC_ERR_ARG for a bad header
+ *                    (the ranges above, reserved == 0) or a file that cannot be written
+ *   ntc_bloom_read   fills *h; filter_bytes has room for cap_bytes — cap_bytes smaller than the image with a non-NULL array: NTC_ERR_ARG after *h is
+ *                    filled, so a first call with cap_bytes == 0 and a NULL array learns the header; NTC_ERR_ARG for a file that is no filter file, has a
+ *                    bad header, is cut short or holds more than its header says */
+#define NTC_BLOOM_BLOCK 4096u   /* window starts per workgroup: block b holds the starts [b * NTC_BLOOM_BLOCK, (b + 1) * NTC_BLOOM_BLOCK) behind offsets[0] */
+int ntc_bloom_size(uint64_t n_distinct, uint32_t n_hash, double fpr, uint64_t *m_bits);
+int ntc_bloom_insert_device(int32_t device, void *stream, void *d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k, uint32_t strand,
+                            const void *d_bases, const uint64_t *offsets, uint64_t n_seqs, uint64_t *n_windows);
+int ntc_bloom_query_device(int32_t device, void *stream, const void *d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k, uint32_t strand,
+                           const void *d_bases, const uint64_t *offsets, uint64_t n_seqs, void *d_windows_u32, void *d_hits_u32);
+int ntc_bloom_insert_hashes_device(int32_t device, void *stream, void *d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k, const void *d_h0_u64,
+                                   uint64_t n);
+int ntc_bloom_query_hashes_device(int32_t device, void *stream, const void *d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k,
+                                  const void *d_h0_u64, uint64_t n, void *d_flags_u8);
+int ntc_bloom_popcount_device(int32_t device, void *stream, const void *d_filter, uint64_t m_bits, uint64_t *pop);
+int ntc_bloom_or_device(int32_t device, void *stream, void *d_dst, const void *d_src, uint64_t m_bits);
+typedef struct {
+    uint32_t k, n_hash, strand, reserved;   /* strand: 0 canonical, 1 forward, 2 reverse; reserved: 0 */
+    uint64_t m_bits, n_inserted;            /* n_inserted: the windows inserted so far (a count of insertions, not of distinct k-mers) */
+} ntc_bloom_header;
+int ntc_bloom_write(const char *path, const ntc_bloom_header *h, const void *filter_bytes);
+int ntc_bloom_read(const char *path, ntc_bloom_header *h, void *filter_bytes, uint64_t cap_bytes);
+
 int ntc_sync(ntc_engine *e); /* wait for all submitted work */
 
 /* Apply the pending hit log to the device sketch (asynchronous on the engine's stream).  After it the

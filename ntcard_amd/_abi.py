@@ -27,7 +27,23 @@ ABI_SYMBOLS = [
     "ntc_signature_gather_device",
     "ntc_signature_union_device", "ntc_signature_select_device", "ntc_signature_hist_device",
     "ntc_k1_variant_stats",
+    "ntc_bloom_size", "ntc_bloom_insert_device", "ntc_bloom_query_device", "ntc_bloom_insert_hashes_device", "ntc_bloom_query_hashes_device",
+    "ntc_bloom_popcount_device", "ntc_bloom_or_device", "ntc_bloom_write", "ntc_bloom_read",
 ]
+
+BLOOM_BLOCK = 4096  # NTC_BLOOM_BLOCK
+
+
+class NtcBloomHeader(C.Structure):
+    """ntc_bloom_header"""
+    _fields_ = [
+        ("k", C.c_uint32),
+        ("n_hash", C.c_uint32),
+        ("strand", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("m_bits", C.c_uint64),
+        ("n_inserted", C.c_uint64),
+    ]
 
 
 class NtcGatherRow(C.Structure):
@@ -201,6 +217,15 @@ def lib():
     L.ntc_hll_create_ex.argtypes = [C.POINTER(NtcHllConfig), C.POINTER(p)]
     L.ntc_hll_estimate_strand.argtypes = [p, u32, u32, C.POINTER(C.c_double)]
     L.ntc_k1_variant_stats.argtypes = [u32, C.POINTER(NtcK1VariantInfo)]
+    L.ntc_bloom_size.argtypes = [u64, u32, C.c_double, C.POINTER(u64)]
+    L.ntc_bloom_insert_device.argtypes = [i32, p, p, u64, u32, u32, u32, p, p, u64, C.POINTER(u64)]
+    L.ntc_bloom_query_device.argtypes = [i32, p, p, u64, u32, u32, u32, p, p, u64, p, p]
+    L.ntc_bloom_insert_hashes_device.argtypes = [i32, p, p, u64, u32, u32, p, u64]
+    L.ntc_bloom_query_hashes_device.argtypes = [i32, p, p, u64, u32, u32, p, u64, p]
+    L.ntc_bloom_popcount_device.argtypes = [i32, p, p, u64, C.POINTER(u64)]
+    L.ntc_bloom_or_device.argtypes = [i32, p, p, p, u64]
+    L.ntc_bloom_write.argtypes = [C.c_char_p, C.POINTER(NtcBloomHeader), p]
+    L.ntc_bloom_read.argtypes = [C.c_char_p, C.POINTER(NtcBloomHeader), p, u64]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("ntc_abi_version", "ntc_max_k", "ntc_last_error", "ntc_destroy", "ntc_tiled_bytes"):

@@ -1,0 +1,162 @@
+"""Bloom filters of every k-mer on the device (include/ntcard_hip.h: ntc_bloom_*; DESIGN.md §4 "Bloom filters"): the step behind ntCard's F0.
+
+The layout is the reference's vendor/ntHash/lib/BloomFilter.hpp — position h_i % m, bit 7 - loc % 8 of byte loc / 8, h_i the multi-hash of
+nthash.hpp:381-390 — so `BloomFilter.bytes()` is what `storeFilter` writes.  torch is plumbing only: it owns the filter's device memory.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from ._abi import BLOOM_BLOCK, NtcBloomHeader, check  # noqa: F401  (BLOOM_BLOCK is re-exported)
+
+_STRANDS = {"canonical": 0, "forward": 1, "reverse": 2}
+_STRAND_NAMES = {v: s for s, v in _STRANDS.items()}
+
+
+def bloom_size(n_distinct, fpr, n_hash=3):
+    """ntc_bloom_size: the bits of a filter that holds n_distinct k-mers at false positive rate fpr with n_hash hashes, a multiple of 64"""
+    m = C.c_uint64(0)
+    check(_abi.lib().ntc_bloom_size(int(n_distinct), int(n_hash), float(fpr), C.byref(m)))
+    return int(m.value)
+
+
+def _offsets(offsets):
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets: a 1-d array of n_seqs + 1 values")
+    return off
+
+
+class BloomFilter:
+    """A Bloom filter of m_bits bits on one device, n_hash positions per k-mer, the k-mers' values taken as an Engine of that strand takes them.
+
+    insert / query take a torch uint8 tensor of bases on the filter's device and HOST offsets (n_seqs + 1, non-decreasing; sequence i is
+    bases[offsets[i]:offsets[i + 1]]), the layout of Engine.submit_long_device."""
+
+    def __init__(self, m_bits, n_hash, k, strand="canonical", device=0):
+        import torch
+        if strand not in _STRANDS:
+            raise ValueError(f"strand must be 'canonical', 'forward' or 'reverse', not {strand!r}")
+        m_bits, n_hash, k = int(m_bits), int(n_hash), int(k)
+        if not 1 <= m_bits < 1 << 40:
+            raise ValueError(f"m_bits={m_bits} outside 1 .. 2^40 - 1")
+        if not 1 <= n_hash <= 32:
+            raise ValueError(f"n_hash={n_hash} outside 1 .. 32")
+        if not 1 <= k <= _abi.lib().ntc_max_k():
+            raise ValueError(f"k={k} outside 1 .. {_abi.lib().ntc_max_k()}")
+        self.m_bits, self.n_hash, self.k, self.strand, self.device = m_bits, n_hash, k, strand, int(device)
+        self.n_inserted = 0
+        self.n_bytes = (m_bits + 7) // 8
+        self.filter = torch.zeros((self.n_bytes + 3) // 4 * 4, dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    @classmethod
+    def for_distinct(cls, n, fpr, n_hash, k, strand="canonical", device=0):
+        """A filter sized by ntc_bloom_size for n distinct k-mers at false positive rate fpr.  n is what ntCard estimates: the F0 that
+        `estimate(p_hist, r_bits, s_bits)` returns for the value histogram of `Engine.finish()` — or the F0 line of the `.hist` file."""
+        return cls(bloom_size(n, fpr, n_hash), n_hash, k, strand, device)
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _bases(self, bases):
+        import torch
+        if not isinstance(bases, torch.Tensor) or bases.dtype != torch.uint8 or not bases.is_cuda or bases.device.index != self.device or not bases.is_contiguous():
+            raise ValueError("bases: a contiguous torch uint8 tensor on the filter's device")
+        return bases
+
+    def insert(self, bases, offsets):
+        """Inserts every k-mer of the sequences; -> the windows inserted"""
+        off = _offsets(offsets)
+        bases = self._bases(bases)
+        if int(off[-1]) > bases.numel():
+            raise ValueError("offsets reach behind the end of bases")
+        n = C.c_uint64(0)
+        check(_abi.lib().ntc_bloom_insert_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k, _STRANDS[self.strand],
+                                                 bases.data_ptr(), off.ctypes.data_as(C.c_void_p), off.size - 1, C.byref(n)))
+        self.n_inserted += int(n.value)
+        return int(n.value)
+
+    def query(self, bases, offsets):
+        """-> (windows, hits): numpy uint32 [n_seqs] each, the k-mers of every sequence and those of them the filter holds"""
+        import torch
+        off = _offsets(offsets)
+        bases = self._bases(bases)
+        if int(off[-1]) > bases.numel():
+            raise ValueError("offsets reach behind the end of bases")
+        n_seqs = off.size - 1
+        out = torch.empty((2, max(n_seqs, 1)), dtype=torch.int32, device=self.filter.device)
+        check(_abi.lib().ntc_bloom_query_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k, _STRANDS[self.strand],
+                                                bases.data_ptr(), off.ctypes.data_as(C.c_void_p), n_seqs, out[0].data_ptr(), out[1].data_ptr()))
+        host = out[:, :n_seqs].cpu().numpy().view(np.uint32)
+        return host[0].copy(), host[1].copy()
+
+    def _hashes(self, h0):
+        import torch
+        if isinstance(h0, torch.Tensor):
+            if h0.dtype not in (torch.int64, torch.uint64) or not h0.is_cuda or h0.device.index != self.device or not h0.is_contiguous():
+                raise ValueError("hashes: a contiguous 64-bit torch tensor on the filter's device, or a numpy array")
+            return h0
+        return torch.from_numpy(np.ascontiguousarray(h0, dtype=np.uint64).view(np.int64)).to(self.filter.device)
+
+    def insert_hashes(self, h0):
+        """Sets the n_hash bits of every given value h_0 (numpy uint64, or a 64-bit tensor on the device) — a signature's hashes, say"""
+        d = self._hashes(h0)
+        check(_abi.lib().ntc_bloom_insert_hashes_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k,
+                                                        d.data_ptr() if d.numel() else None, d.numel()))
+        self.n_inserted += d.numel()
+
+    def query_hashes(self, h0):
+        """-> numpy bool [n]: whether all n_hash bits of each given h_0 are set"""
+        import torch
+        d = self._hashes(h0)
+        flags = torch.empty(max(d.numel(), 1), dtype=torch.uint8, device=self.filter.device)
+        check(_abi.lib().ntc_bloom_query_hashes_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k,
+                                                       d.data_ptr() if d.numel() else None, d.numel(), flags.data_ptr()))
+        return flags[: d.numel()].cpu().numpy().astype(bool)
+
+    def popcount(self):
+        pop = C.c_uint64(0)
+        check(_abi.lib().ntc_bloom_popcount_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, C.byref(pop)))
+        return int(pop.value)
+
+    def fpr(self):
+        """(popcount / m_bits) ** n_hash: the chance that a k-mer that was never inserted finds all its bits set"""
+        return (self.popcount() / self.m_bits) ** self.n_hash
+
+    def merge(self, other):
+        """ORs another filter of the same shape into this one (shards of one input, peers' filters)"""
+        if (other.m_bits, other.n_hash, other.k, other.strand) != (self.m_bits, self.n_hash, self.k, self.strand):
+            raise ValueError("merge: the filters differ in m_bits, n_hash, k or strand")
+        src = other.filter if other.device == self.device else other.filter.to(self.filter.device)
+        check(_abi.lib().ntc_bloom_or_device(self.device, self._stream(), self.filter.data_ptr(), src.data_ptr(), self.m_bits))
+        self.n_inserted += other.n_inserted
+
+    def bytes(self):
+        """The reference's byte image, (m_bits + 7) // 8 bytes, as numpy uint8"""
+        return self.filter[: self.n_bytes].cpu().numpy()
+
+    def save(self, path):
+        h = NtcBloomHeader(k=self.k, n_hash=self.n_hash, strand=_STRANDS[self.strand], reserved=0, m_bits=self.m_bits, n_inserted=self.n_inserted)
+        image = np.ascontiguousarray(self.bytes())
+        check(_abi.lib().ntc_bloom_write(str(path).encode(), C.byref(h), image.ctypes.data_as(C.c_void_p)))
+
+    @classmethod
+    def load(cls, path, device=0):
+        import torch
+        h, image = read_file(path)
+        f = cls(h["m_bits"], h["n_hash"], h["k"], h["strand"], device)
+        f.n_inserted = h["n_inserted"]
+        f.filter[: f.n_bytes] = torch.from_numpy(image).to(f.filter.device)
+        return f
+
+
+def read_file(path):
+    """ntc_bloom_read -> (header dict, the byte image as numpy uint8): pure host"""
+    h = NtcBloomHeader()
+    L = _abi.lib()
+    check(L.ntc_bloom_read(str(path).encode(), C.byref(h), None, 0))
+    image = np.zeros((h.m_bits + 7) // 8, dtype=np.uint8)
+    check(L.ntc_bloom_read(str(path).encode(), C.byref(h), image.ctypes.data_as(C.c_void_p), image.size))
+    return {"k": h.k, "n_hash": h.n_hash, "strand": _STRAND_NAMES[h.strand], "m_bits": int(h.m_bits), "n_inserted": int(h.n_inserted)}, image
