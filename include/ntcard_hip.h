@@ -456,7 +456,8 @@ int ntc_signature_header(ntc_engine *e, uint32_t plane, ntc_sig_header *h);
  *       here).  A sequence shorter than k contributes nothing.  strand: 0 canonical min(fh, rh), 1 forward fh, 2 reverse rh (the numbers of
  *       NTC_FLAG_STRAND_*).  Homopolymer compression is not a flag here: a caller who wants it runs ntc_hpc_compress_device first and passes its output.
  *   ntc_bloom_size           pure host: m = ceil(-n_distinct * n_hash / ln(1 - fpr^(1 / n_hash))) rounded up to a multiple of 64.  NTC_ERR_ARG for
- *       n_distinct == 0, n_hash outside 1 .. 32, fpr outside (0, 1), a NULL m_bits or a result of 2^40 or more.
+ *       n_distinct == 0, n_hash outside 1 .. 32, fpr outside (0, 1), a NULL m_bits or a result of 2^40 or more.  It serves both kinds of filter: the
+ *       positions it returns are bits for a plain filter and counters for a counting one (below).
  *   ntc_bloom_insert_device  sets the n_hash bits of every window; *n_windows = the windows inserted (may be NULL).  The byte range is cut into blocks
  *       of NTC_BLOOM_BLOCK window starts, counted from offsets[0]; a workgroup stages its block's bytes in LDS and a lane rolls over 16 consecutive
  *       windows.  A bit that a plain load already finds set costs no atomic.  Scratch: the offsets (8 B per sequence) and 8 B.
@@ -494,6 +495,54 @@ typedef struct {
 } ntc_bloom_header;
 int ntc_bloom_write(const char *path, const ntc_bloom_header *h, const void *filter_bytes);
 int ntc_bloom_read(const char *path, ntc_bloom_header *h, void *filter_bytes, uint64_t cap_bytes);
+
+/* COUNTING BLOOM FILTERS and SOLID k-mers (additive to ABI 6: eleven calls; NTC_ABI_VERSION and every other declaration are unchanged).  The other half
+ * of ntCard's output: f1 and the f_i lines say how many distinct k-mers occur once, twice, ...; a downstream tool keeps the SOLID ones, seen at least c
+ * times, in a filter it sizes from F0 - sum_{i<c} f_i.  Engine-less device tools like the Bloom calls above, with their input, their limits, their
+ * errors and their walk (ntc_bloom_size serves both kinds: the positions it returns are counters here and bits there).
+ *   The counters  caller-owned DEVICE memory: m unsigned 8-bit counters, counter loc = byte loc, m bytes rounded up to a multiple of 4, 4-byte aligned,
+ *       zeroed by the caller before the first insert.  The bytes from m on (the padding) stay zero.  1 <= m < 2^40.  A k-mer's n_hash positions are the
+ *       plain filter's: loc_i = h_i % m.
+ *   Insert        every one of the n_hash counters += 1, saturating at 255; two positions of one k-mer that coincide (small m) give that counter two
+ *       increments.  After any inserts, in any order, on any number of workgroups: counter[loc] = min(255, the increments aimed at loc).  There is NO
+ *       conservative update (incrementing only the minimal counters): its result depends on the order of concurrent inserts.
+ *   Count         of a k-mer: the minimum of its n_hash counters — never below its true number of occurrences capped at 255, above it only by collisions.
+ *   ntc_cbloom_insert_device   increments for every window; *n_windows = the windows inserted (may be NULL).  A counter that a plain load finds at 255
+ *       costs nothing; otherwise one 32-bit compare-and-swap loop on the containing dword, which adds 1 << 8 (loc % 4) and leaves at 255.
+ *   ntc_cbloom_query_device    d_windows_u32[i] = the windows of sequence i, d_hits_u32[i] = those whose count is >= min_count (1 .. 255); DEVICE arrays of
+ *       n_seqs uint32, zeroed by the call.
+ *   ntc_cbloom_profile_device  the coverage profile: for n = offsets[n_seqs] - offsets[0], d_counts_u8[p] = the count of the window that STARTS at
+ *       position p (byte offsets[0] + p of d_bases), 0 where none starts: the last k - 1 positions of a sequence, windows with a non-base, sequences
+ *       shorter than k.  All n bytes are written (a DEVICE array of n bytes, any alignment, not zeroed by the caller).
+ *   ntc_cbloom_insert_hashes_device / ntc_cbloom_query_hashes_device  the same arithmetic on n GIVEN h_0 values (DEVICE uint64); d_counts_u8[i] = the count.
+ *   ntc_cbloom_threshold_device  writes the plain filter of m_bits = m in the reference's layout: the bit of position loc is set iff
+ *       counter[loc] >= min_count, the padding behind m is zero.  Every k-mer seen >= min_count times has all its bits set; with min_count = 1 the image
+ *       is what ntc_bloom_insert_device builds from the same input with the same n_hash.  d_filter: (m + 7) / 8 bytes rounded up to 4, every byte written.
+ *   ntc_bloom_insert_solid_device  the second stage: walks the input again and sets, in a plain filter of its OWN m_bits and n_hash, every window whose
+ *       count in a finished counting filter (d_counters, m, c_n_hash) is >= min_count; *n_windows = the windows that passed (may be NULL).
+ *   ntc_cbloom_add_device      d_dst = min(255, d_dst + d_src) per counter: shards of one input, peers' filters.  The two arrays are distinct.
+ *   ntc_cbloom_hist_device     hist_u64[v] = how many of the first m counters hold v (HOST array of 256).  NTC_ERR_STATE when a padding byte is not 0.
+ *       (sum_{v>=c} hist[v] / m)^n_hash is the expected rate of a false "count >= c"; hist[255] the saturated counters.
+ * A counting filter FILE: the 8 bytes "NTCCB1\0\0", ntc_bloom_header with m_bits = the number of counters, then the m counter bytes.
+ * ntc_cbloom_write / ntc_cbloom_read behave as ntc_bloom_write / ntc_bloom_read do (".part" and rename; the size query with a NULL array). */
+int ntc_cbloom_insert_device(int32_t device, void *stream, void *d_counters, uint64_t m, uint32_t n_hash, uint32_t k, uint32_t strand,
+                             const void *d_bases, const uint64_t *offsets, uint64_t n_seqs, uint64_t *n_windows);
+int ntc_cbloom_query_device(int32_t device, void *stream, const void *d_counters, uint64_t m, uint32_t n_hash, uint32_t k, uint32_t strand,
+                            const void *d_bases, const uint64_t *offsets, uint64_t n_seqs, uint32_t min_count, void *d_windows_u32, void *d_hits_u32);
+int ntc_cbloom_profile_device(int32_t device, void *stream, const void *d_counters, uint64_t m, uint32_t n_hash, uint32_t k, uint32_t strand,
+                              const void *d_bases, const uint64_t *offsets, uint64_t n_seqs, void *d_counts_u8);
+int ntc_cbloom_insert_hashes_device(int32_t device, void *stream, void *d_counters, uint64_t m, uint32_t n_hash, uint32_t k, const void *d_h0_u64,
+                                    uint64_t n);
+int ntc_cbloom_query_hashes_device(int32_t device, void *stream, const void *d_counters, uint64_t m, uint32_t n_hash, uint32_t k,
+                                   const void *d_h0_u64, uint64_t n, void *d_counts_u8);
+int ntc_cbloom_threshold_device(int32_t device, void *stream, const void *d_counters, uint64_t m, uint32_t min_count, void *d_filter);
+int ntc_bloom_insert_solid_device(int32_t device, void *stream, void *d_filter, uint64_t m_bits, uint32_t n_hash, const void *d_counters, uint64_t m,
+                                  uint32_t c_n_hash, uint32_t min_count, uint32_t k, uint32_t strand, const void *d_bases, const uint64_t *offsets,
+                                  uint64_t n_seqs, uint64_t *n_windows);
+int ntc_cbloom_add_device(int32_t device, void *stream, void *d_dst, const void *d_src, uint64_t m);
+int ntc_cbloom_hist_device(int32_t device, void *stream, const void *d_counters, uint64_t m, uint64_t *hist_u64);
+int ntc_cbloom_write(const char *path, const ntc_bloom_header *h, const void *counter_bytes);
+int ntc_cbloom_read(const char *path, ntc_bloom_header *h, void *counter_bytes, uint64_t cap_bytes);
 
 int ntc_sync(ntc_engine *e); /* wait for all submitted work */
 

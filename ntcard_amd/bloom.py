@@ -1,4 +1,5 @@
-"""Bloom filters of every k-mer on the device (include/ntcard_hip.h: ntc_bloom_*; DESIGN.md §4 "Bloom filters"): the step behind ntCard's F0.
+"""Bloom filters of every k-mer on the device (include/ntcard_hip.h: ntc_bloom_*; DESIGN.md §4 "Bloom filters"): the step behind ntCard's F0 — and
+counting filters (ntc_cbloom_*; DESIGN.md §4 "Counting filters and solid k-mers"): the step behind its f_i, k-mer counts and the filter of the solid k-mers.
 
 The layout is the reference's vendor/ntHash/lib/BloomFilter.hpp — position h_i % m, bit 7 - loc % 8 of byte loc / 8, h_i the multi-hash of
 nthash.hpp:381-390 — so `BloomFilter.bytes()` is what `storeFilter` writes.  torch is plumbing only: it owns the filter's device memory.
@@ -15,7 +16,8 @@ _STRAND_NAMES = {v: s for s, v in _STRANDS.items()}
 
 
 def bloom_size(n_distinct, fpr, n_hash=3):
-    """ntc_bloom_size: the bits of a filter that holds n_distinct k-mers at false positive rate fpr with n_hash hashes, a multiple of 64"""
+    """ntc_bloom_size: the bits of a filter — or the counters of a counting filter — that holds n_distinct k-mers at false positive rate fpr with n_hash
+    hashes, a multiple of 64"""
     m = C.c_uint64(0)
     check(_abi.lib().ntc_bloom_size(int(n_distinct), int(n_hash), float(fpr), C.byref(m)))
     return int(m.value)
@@ -159,4 +161,163 @@ def read_file(path):
     check(L.ntc_bloom_read(str(path).encode(), C.byref(h), None, 0))
     image = np.zeros((h.m_bits + 7) // 8, dtype=np.uint8)
     check(L.ntc_bloom_read(str(path).encode(), C.byref(h), image.ctypes.data_as(C.c_void_p), image.size))
+    return {"k": h.k, "n_hash": h.n_hash, "strand": _STRAND_NAMES[h.strand], "m_bits": int(h.m_bits), "n_inserted": int(h.n_inserted)}, image
+
+
+class CountingBloomFilter:
+    """A counting Bloom filter of m_bits 8-bit counters on one device (m_bits: the NUMBER OF COUNTERS, the name BloomFilter uses for its positions): an
+    insert adds one to each of a k-mer's n_hash counters, saturating at 255; the count of a k-mer is the minimum of its counters.  Constructor, inputs and
+    streams as BloomFilter's."""
+
+    def __init__(self, m_bits, n_hash, k, strand="canonical", device=0):
+        import torch
+        if strand not in _STRANDS:
+            raise ValueError(f"strand must be 'canonical', 'forward' or 'reverse', not {strand!r}")
+        m_bits, n_hash, k = int(m_bits), int(n_hash), int(k)
+        if not 1 <= m_bits < 1 << 40:
+            raise ValueError(f"m_bits={m_bits} outside 1 .. 2^40 - 1")
+        if not 1 <= n_hash <= 32:
+            raise ValueError(f"n_hash={n_hash} outside 1 .. 32")
+        if not 1 <= k <= _abi.lib().ntc_max_k():
+            raise ValueError(f"k={k} outside 1 .. {_abi.lib().ntc_max_k()}")
+        self.m_bits, self.n_hash, self.k, self.strand, self.device = m_bits, n_hash, k, strand, int(device)
+        self.n_inserted = 0
+        self.n_bytes = m_bits
+        self.filter = torch.zeros((self.n_bytes + 3) // 4 * 4, dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    @classmethod
+    def for_distinct(cls, n, fpr, n_hash, k, strand="canonical", device=0):
+        """A filter of ntc_bloom_size(n, n_hash, fpr) counters: a k-mer that was never inserted reads a count >= 1 at rate fpr"""
+        return cls(bloom_size(n, fpr, n_hash), n_hash, k, strand, device)
+
+    _stream = BloomFilter._stream
+    _bases = BloomFilter._bases
+    _hashes = BloomFilter._hashes
+
+    def _input(self, bases, offsets):
+        off = _offsets(offsets)
+        bases = self._bases(bases)
+        if int(off[-1]) > bases.numel():
+            raise ValueError("offsets reach behind the end of bases")
+        return bases, off
+
+    @staticmethod
+    def _min_count(min_count):
+        min_count = int(min_count)
+        if not 1 <= min_count <= 255:
+            raise ValueError(f"min_count={min_count} outside 1 .. 255")
+        return min_count
+
+    def insert(self, bases, offsets):
+        """Counts every k-mer of the sequences; -> the windows inserted"""
+        bases, off = self._input(bases, offsets)
+        n = C.c_uint64(0)
+        check(_abi.lib().ntc_cbloom_insert_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k, _STRANDS[self.strand],
+                                                  bases.data_ptr(), off.ctypes.data_as(C.c_void_p), off.size - 1, C.byref(n)))
+        self.n_inserted += int(n.value)
+        return int(n.value)
+
+    def query(self, bases, offsets, min_count=1):
+        """-> (windows, hits): numpy uint32 [n_seqs] each, the k-mers of every sequence and those of them whose count is >= min_count"""
+        import torch
+        bases, off = self._input(bases, offsets)
+        n_seqs = off.size - 1
+        out = torch.empty((2, max(n_seqs, 1)), dtype=torch.int32, device=self.filter.device)
+        check(_abi.lib().ntc_cbloom_query_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k, _STRANDS[self.strand],
+                                                 bases.data_ptr(), off.ctypes.data_as(C.c_void_p), n_seqs, self._min_count(min_count), out[0].data_ptr(),
+                                                 out[1].data_ptr()))
+        host = out[:, :n_seqs].cpu().numpy().view(np.uint32)
+        return host[0].copy(), host[1].copy()
+
+    def profile(self, bases, offsets):
+        """-> numpy uint8 [offsets[-1] - offsets[0]]: byte p is the count of the k-mer that starts at position p, 0 where none starts"""
+        import torch
+        bases, off = self._input(bases, offsets)
+        n = int(off[-1]) - int(off[0])
+        out = torch.empty(max(n, 1), dtype=torch.uint8, device=self.filter.device)
+        check(_abi.lib().ntc_cbloom_profile_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k, _STRANDS[self.strand],
+                                                   bases.data_ptr(), off.ctypes.data_as(C.c_void_p), off.size - 1, out.data_ptr()))
+        return out[:n].cpu().numpy()
+
+    def insert_hashes(self, h0):
+        """Increments the n_hash counters of every given value h_0 (numpy uint64, or a 64-bit tensor on the device)"""
+        d = self._hashes(h0)
+        check(_abi.lib().ntc_cbloom_insert_hashes_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k,
+                                                         d.data_ptr() if d.numel() else None, d.numel()))
+        self.n_inserted += d.numel()
+
+    def counts_of_hashes(self, h0):
+        """-> numpy uint8 [n]: the count of each given h_0"""
+        import torch
+        d = self._hashes(h0)
+        counts = torch.empty(max(d.numel(), 1), dtype=torch.uint8, device=self.filter.device)
+        check(_abi.lib().ntc_cbloom_query_hashes_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k,
+                                                        d.data_ptr() if d.numel() else None, d.numel(), counts.data_ptr()))
+        return counts[: d.numel()].cpu().numpy()
+
+    def hist(self):
+        """-> numpy uint64 [256]: how many counters hold each value"""
+        h = np.zeros(256, dtype=np.uint64)
+        check(_abi.lib().ntc_cbloom_hist_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, h.ctypes.data_as(C.c_void_p)))
+        return h
+
+    def fpr(self, min_count=1):
+        """(the counters >= min_count / m_bits) ** n_hash: the chance that a k-mer that was never inserted reads a count >= min_count"""
+        h = self.hist()
+        return (int(h[self._min_count(min_count):].sum()) / self.m_bits) ** self.n_hash
+
+    def merge(self, other):
+        """Adds another filter of the same shape into this one, counter by counter, saturating (shards of one input, peers' filters)"""
+        if (other.m_bits, other.n_hash, other.k, other.strand) != (self.m_bits, self.n_hash, self.k, self.strand):
+            raise ValueError("merge: the filters differ in m_bits, n_hash, k or strand")
+        src = other.filter if other.device == self.device else other.filter.to(self.filter.device)
+        check(_abi.lib().ntc_cbloom_add_device(self.device, self._stream(), self.filter.data_ptr(), src.data_ptr(), self.m_bits))
+        self.n_inserted += other.n_inserted
+
+    def counters(self):
+        """The m_bits counters as numpy uint8"""
+        return self.filter[: self.n_bytes].cpu().numpy()
+
+    def threshold(self, min_count):
+        """-> a BloomFilter of the same m_bits, n_hash, k and strand: the bit of a position is set iff its counter is >= min_count"""
+        f = BloomFilter(self.m_bits, self.n_hash, self.k, self.strand, self.device)
+        check(_abi.lib().ntc_cbloom_threshold_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self._min_count(min_count), f.filter.data_ptr()))
+        f.n_inserted = self.n_inserted
+        return f
+
+    def solid(self, bases, offsets, min_count, into):
+        """Inserts into the BloomFilter `into` (its own m_bits and n_hash; this filter's k and strand) every k-mer of the sequences whose count here is
+        >= min_count; -> the windows that passed"""
+        if not isinstance(into, BloomFilter) or (into.k, into.strand, into.device) != (self.k, self.strand, self.device):
+            raise ValueError("solid: `into` is a BloomFilter of this filter's k, strand and device")
+        bases, off = self._input(bases, offsets)
+        n = C.c_uint64(0)
+        check(_abi.lib().ntc_bloom_insert_solid_device(self.device, self._stream(), into.filter.data_ptr(), into.m_bits, into.n_hash, self.filter.data_ptr(), self.m_bits,
+                                                       self.n_hash, self._min_count(min_count), self.k, _STRANDS[self.strand], bases.data_ptr(),
+                                                       off.ctypes.data_as(C.c_void_p), off.size - 1, C.byref(n)))
+        into.n_inserted += int(n.value)
+        return int(n.value)
+
+    def save(self, path):
+        h = NtcBloomHeader(k=self.k, n_hash=self.n_hash, strand=_STRANDS[self.strand], reserved=0, m_bits=self.m_bits, n_inserted=self.n_inserted)
+        image = np.ascontiguousarray(self.counters())
+        check(_abi.lib().ntc_cbloom_write(str(path).encode(), C.byref(h), image.ctypes.data_as(C.c_void_p)))
+
+    @classmethod
+    def load(cls, path, device=0):
+        import torch
+        h, image = read_counting_file(path)
+        f = cls(h["m_bits"], h["n_hash"], h["k"], h["strand"], device)
+        f.n_inserted = h["n_inserted"]
+        f.filter[: f.n_bytes] = torch.from_numpy(image).to(f.filter.device)
+        return f
+
+
+def read_counting_file(path):
+    """ntc_cbloom_read -> (header dict, the counters as numpy uint8): pure host"""
+    h = NtcBloomHeader()
+    L = _abi.lib()
+    check(L.ntc_cbloom_read(str(path).encode(), C.byref(h), None, 0))
+    image = np.zeros(h.m_bits, dtype=np.uint8)
+    check(L.ntc_cbloom_read(str(path).encode(), C.byref(h), image.ctypes.data_as(C.c_void_p), image.size))
     return {"k": h.k, "n_hash": h.n_hash, "strand": _STRAND_NAMES[h.strand], "m_bits": int(h.m_bits), "n_inserted": int(h.n_inserted)}, image

@@ -1,12 +1,25 @@
 // ntbloom_cli.cpp — `ntbloom`: Bloom filters of every k-mer of the input, in the reference's layout (vendor/ntHash/lib/BloomFilter.hpp), sized from ntcard's F0
-// (include/ntcard_hip.h: ntc_bloom_*; DESIGN.md §4 "Bloom filters").
+// (include/ntcard_hip.h: ntc_bloom_*; DESIGN.md §4 "Bloom filters"), and counting filters and the filter of the solid k-mers, sized from its f_i
+// (ntc_cbloom_*; DESIGN.md §4 "Counting filters and solid k-mers").
 //   ntbloom build -k K [-H N] [--strand=canonical|forward|reverse] (-m BITS | --distinct N --fpr P | --hist FILE --fpr P) -o OUT.bf FILE...
 //                               inserts every k-mer of the files.  The filter has BITS bits, or what ntc_bloom_size gives for N distinct k-mers at false
 //                               positive rate P; --hist takes N from the F0 line of a `.hist` file as ntcard writes it, so that
 //                               `ntcard -k 32 -p s reads.fq && ntbloom build -k 32 --hist s_k32.hist --fpr 0.01 -o s.bf reads.fq` composes.  -H: hashes per
 //                               k-mer (default 3).  OUT.bf is written whole or not at all (ntc_bloom_write).
-//   ntbloom query F.bf FILE...  one TSV row per record: name, length, windows, hits, hits / windows (k, hashes and strand come from F.bf)
-//   ntbloom info F.bf           the header, and with a GPU the popcount, the occupancy and the false positive rate it implies; without one the header alone
+//   ntbloom count -k K [-H N] [--strand=...] (-m COUNTERS | --distinct N --fpr P | --hist FILE --fpr P) -o OUT.cbf FILE...
+//                               the same with 8-bit counters: every k-mer adds one to each of its N counters, saturating at 255 (ntc_cbloom_write)
+//   ntbloom solid --min-count C [--fpr P --hist FILE [-H N]] -o OUT.bf IN.cbf [FILE...]
+//                               the plain filter of the k-mers counted at least C times (k and strand come from IN.cbf).  Without input files IN.cbf is
+//                               thresholded: OUT.bf has as many bits as IN.cbf counters and its hash count.  With input files, --hist and --fpr the
+//                               files are walked again and every k-mer whose count in IN.cbf is >= C goes into a filter sized by ntc_bloom_size for
+//                               n = F0 - sum_{i<C} f_i of the `.hist` file (its F0 line and its "i\tf_i" lines), N hashes (default 3):
+//                               `ntcard -k 32 -p s reads.fq && ntbloom count -k 32 --hist s_k32.hist --fpr 0.01 -o s.cbf reads.fq &&
+//                                ntbloom solid --min-count 2 --hist s_k32.hist --fpr 0.01 -o solid.bf s.cbf reads.fq && ntbloom query solid.bf other.fq`
+//   ntbloom query [--min-count C] F.bf|F.cbf FILE...
+//                               one TSV row per record: name, length, windows, hits, hits / windows (k, hashes and strand come from the file, whose
+//                               magic says which kind it is).  On a .cbf a hit is a window whose count is >= C (default 1); --min-count with a .bf is refused
+//   ntbloom info F.bf|F.cbf     the header, and with a GPU the popcount, the occupancy and the false positive rate it implies (a .cbf: the counters that
+//                               are not 0, the saturated ones, the rate of a false "count >= 1"); without one the header alone
 // Input: FASTA (a record's lines are joined) and FASTQ, plain or through the decompressor its extension names (cli_common.hpp: LineReader).  One thread
 // reads records into a pinned batch of at most 256 MiB, uploads it and calls ntc_bloom_insert_device / ntc_bloom_query_device.  SAM is not read here.
 // Every malformed argument is refused with a message that names it, before a device is looked for.
@@ -39,8 +52,10 @@ int usage(const char* why, const char* what = nullptr)
 		std::fprintf(stderr, "ntbloom: %s\n", why);
 	std::fprintf(stderr,
 	             "usage: ntbloom build -k K [-H N] [--strand=canonical|forward|reverse] (-m BITS | --distinct N --fpr P | --hist FILE --fpr P) -o OUT.bf FILE...\n"
-	             "       ntbloom query F.bf FILE...\n"
-	             "       ntbloom info F.bf\n");
+	             "       ntbloom count -k K [-H N] [--strand=canonical|forward|reverse] (-m COUNTERS | --distinct N --fpr P | --hist FILE --fpr P) -o OUT.cbf FILE...\n"
+	             "       ntbloom solid --min-count C [--fpr P --hist FILE [-H N]] -o OUT.bf IN.cbf [FILE...]\n"
+	             "       ntbloom query [--min-count C] F.bf|F.cbf FILE...\n"
+	             "       ntbloom info F.bf|F.cbf\n");
 	return EXIT_FAILURE;
 }
 
@@ -97,9 +112,51 @@ bool hist_f0(const char* path, uint64_t& f0)
 	return found;
 }
 
+// F0 - sum_{i < c} f_i of a `.hist` file: its F0 line and its "i\tf_i" lines, i = 1, 2, ... as ntc_write_hist writes them.  -1: no F0 line; -2: the f_i
+// lines stop below c - 1; -3: the lines sum to more than F0; 0: n is set
+int hist_solid_n(const char* path, uint64_t c, uint64_t& n)
+{
+	uint64_t f0 = 0;
+	if (!hist_f0(path, f0)) return -1;
+	FILE* f = std::fopen(path, "rb");
+	if (!f) return -1;
+	char line[256];
+	uint64_t next = 1, below = 0;
+	while (next < c && std::fgets(line, sizeof line, f)) {
+		char* tab = std::strchr(line, '\t');
+		if (!tab) continue;
+		*tab = '\0';
+		uint64_t i = 0, fi = 0;
+		if (!parse_u64(line, i) || i != next) continue; // (the F1 and F0 lines, and whatever is no "i\tf_i" line of the next i)
+		std::string v(tab + 1);
+		while (!v.empty() && (v.back() == '\n' || v.back() == '\r'))
+			v.pop_back();
+		if (!parse_u64(v.c_str(), fi)) break;
+		below += fi;
+		++next;
+	}
+	std::fclose(f);
+	if (next < c) return -2;
+	if (below > f0) return -3;
+	n = f0 - below;
+	return 0;
+}
+
+// the kind of a filter file by its magic: 1 a counting filter, 0 anything else (ntc_bloom_read then says what is wrong with it)
+bool is_counting_file(const char* path)
+{
+	FILE* f = std::fopen(path, "rb");
+	if (!f) return false;
+	char magic[8] = {0};
+	const bool yes = std::fread(magic, 1, 8, f) == 8 && std::memcmp(magic, "NTCCB1\0\0", 8) == 0;
+	std::fclose(f);
+	return yes;
+}
+
 // device and pinned memory of one run, freed on every way out
 struct Buffers {
 	unsigned char* d_filter = nullptr;
+	unsigned char* d_counters = nullptr; // solid: the counting filter beside the plain one
 	unsigned char* d_bases = nullptr;
 	unsigned char* h_bases = nullptr; // pinned
 	uint32_t* d_counts = nullptr;     // query: [2][seq_cap]
@@ -107,6 +164,7 @@ struct Buffers {
 	~Buffers()
 	{
 		if (d_filter) (void)hipFree(d_filter);
+		if (d_counters) (void)hipFree(d_counters);
 		if (d_bases) (void)hipFree(d_bases);
 		if (h_bases) (void)hipHostFree(h_bases);
 		if (d_counts) (void)hipFree(d_counts);
@@ -217,6 +275,9 @@ bool alloc_batch(Buffers& b)
 
 struct BuildCtx {
 	ntc_bloom_header h;
+	bool counting = false;       // count: d_filter holds counters
+	ntc_bloom_header c{};        // solid: the counting filter in d_counters ...
+	uint32_t min_count = 0;      // ... and the count a k-mer needs (0: not solid)
 };
 int build_flush(Reader& r, void* ctx)
 {
@@ -224,13 +285,23 @@ int build_flush(Reader& r, void* ctx)
 	const hipError_t rc = hipMemcpy(r.b.d_bases, r.b.h_bases, r.fill, hipMemcpyHostToDevice);
 	if (rc != hipSuccess) return fail_hip("cannot upload a batch", rc);
 	uint64_t n = 0;
-	if (ntc_bloom_insert_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), r.offsets.size() - 1, &n) != 0) return fail_lib();
+	int rc2;
+	if (c.min_count)
+		rc2 = ntc_bloom_insert_solid_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, r.b.d_counters, c.c.m_bits, c.c.n_hash, c.min_count, c.h.k, c.h.strand, r.b.d_bases,
+		                                    r.offsets.data(), r.offsets.size() - 1, &n);
+	else if (c.counting)
+		rc2 = ntc_cbloom_insert_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), r.offsets.size() - 1, &n);
+	else
+		rc2 = ntc_bloom_insert_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), r.offsets.size() - 1, &n);
+	if (rc2 != 0) return fail_lib();
 	c.h.n_inserted += n;
 	return EXIT_SUCCESS;
 }
 
 struct QueryCtx {
 	ntc_bloom_header h;
+	bool counting = false;
+	uint32_t min_count = 1;
 	std::vector<uint32_t> counts;
 };
 int query_flush(Reader& r, void* ctx)
@@ -248,7 +319,9 @@ int query_flush(Reader& r, void* ctx)
 	if (rc != hipSuccess) return fail_hip("cannot upload a batch", rc);
 	uint32_t* d_w = r.b.d_counts;
 	uint32_t* d_h = r.b.d_counts + r.b.seq_cap;
-	if (ntc_bloom_query_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, d_w, d_h) != 0) return fail_lib();
+	const int rc2 = c.counting ? ntc_cbloom_query_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, c.min_count, d_w, d_h)
+	                           : ntc_bloom_query_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, d_w, d_h);
+	if (rc2 != 0) return fail_lib();
 	c.counts.resize(2 * n_seqs);
 	rc = hipMemcpy(c.counts.data(), d_w, n_seqs * 4, hipMemcpyDeviceToHost);
 	if (rc == hipSuccess) rc = hipMemcpy(c.counts.data() + n_seqs, d_h, n_seqs * 4, hipMemcpyDeviceToHost);
@@ -260,34 +333,42 @@ int query_flush(Reader& r, void* ctx)
 	return EXIT_SUCCESS;
 }
 
-bool upload_filter(Buffers& b, const ntc_bloom_header& h, const std::vector<unsigned char>* image)
+// the bytes of a filter's image: a plain filter's bits, a counting filter's counters
+size_t image_bytes(const ntc_bloom_header& h, bool counting) { return counting ? h.m_bits : (h.m_bits + 7) / 8; }
+
+bool upload_filter(Buffers& b, const ntc_bloom_header& h, const std::vector<unsigned char>* image, bool counting = false, unsigned char** where = nullptr)
 {
-	const size_t padded = (((h.m_bits + 7) / 8) + 3) & ~(size_t)3;
-	hipError_t rc = hipMalloc((void**)&b.d_filter, padded);
-	if (rc == hipSuccess) rc = hipMemset(b.d_filter, 0, padded);
-	if (rc == hipSuccess && image) rc = hipMemcpy(b.d_filter, image->data(), image->size(), hipMemcpyHostToDevice);
+	unsigned char*& d = where ? *where : b.d_filter;
+	const size_t padded = (image_bytes(h, counting) + 3) & ~(size_t)3;
+	hipError_t rc = hipMalloc((void**)&d, padded);
+	if (rc == hipSuccess) rc = hipMemset(d, 0, padded);
+	if (rc == hipSuccess && image) rc = hipMemcpy(d, image->data(), image->size(), hipMemcpyHostToDevice);
 	if (rc == hipSuccess) return true;
 	(void)fail_hip("cannot bring the filter to the device", rc);
 	return false;
 }
 
-bool read_filter(const char* path, ntc_bloom_header& h, std::vector<unsigned char>* image)
+bool read_filter(const char* path, ntc_bloom_header& h, std::vector<unsigned char>* image, bool counting = false)
 {
-	if (ntc_bloom_read(path, &h, nullptr, 0) != 0) {
+	const auto read = counting ? ntc_cbloom_read : ntc_bloom_read;
+	if (read(path, &h, nullptr, 0) != 0) {
 		(void)fail_lib();
 		return false;
 	}
 	if (!image) return true;
-	image->resize((h.m_bits + 7) / 8);
-	if (ntc_bloom_read(path, &h, image->data(), image->size()) != 0) {
+	image->resize(image_bytes(h, counting));
+	if (read(path, &h, image->data(), image->size()) != 0) {
 		(void)fail_lib();
 		return false;
 	}
 	return true;
 }
 
-int build(int argc, char** argv)
+// build (a plain filter, OUT.bf) and count (a counting filter, OUT.cbf): the same arguments, -m in bits or in counters
+int build(int argc, char** argv, bool counting)
 {
+	const char* const cmd = counting ? "count" : "build";
+	auto needs = [&](const char* what) { return usage((std::string(cmd) + " needs " + what).c_str()); };
 	uint64_t k = 0, n_hash = 3, m_bits = 0, distinct = 0;
 	double fpr = 0.0;
 	bool have_k = false, have_m = false, have_distinct = false, have_fpr = false;
@@ -346,53 +427,163 @@ int build(int argc, char** argv)
 			files.push_back(argv[i]);
 		}
 	}
-	if (!have_k) return usage("build needs -k");
-	if (!out) return usage("build needs -o OUT.bf");
+	if (!have_k) return needs("-k");
+	if (!out) return needs(counting ? "-o OUT.cbf" : "-o OUT.bf");
 	const int ways = (have_m ? 1 : 0) + (have_distinct ? 1 : 0) + (hist ? 1 : 0);
-	if (ways != 1) return usage("build needs exactly one of -m BITS, --distinct N and --hist FILE");
+	if (ways != 1) return needs(counting ? "exactly one of -m COUNTERS, --distinct N and --hist FILE" : "exactly one of -m BITS, --distinct N and --hist FILE");
 	if (have_m && have_fpr) return usage("--fpr goes with --distinct or --hist, not with -m");
 	if (!have_m && !have_fpr) return usage("--distinct and --hist need --fpr P");
-	if (files.empty()) return usage("build needs at least one input file");
+	if (files.empty()) return needs("at least one input file");
 	if (hist && !hist_f0(hist, distinct)) return usage("no F0 line of a .hist file in", hist);
 	if (hist && distinct == 0) return usage("the F0 of the .hist file is 0", hist);
 	if (!have_m && ntc_bloom_size(distinct, (uint32_t)n_hash, fpr, &m_bits) != 0) return fail_lib();
 
 	BuildCtx c;
 	c.h = ntc_bloom_header{(uint32_t)k, (uint32_t)n_hash, strand, 0, m_bits, 0};
+	c.counting = counting;
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
 		std::fprintf(stderr, "ntbloom: no HIP device\n");
 		return EXIT_FAILURE;
 	}
 	Buffers b;
-	if (!upload_filter(b, c.h, nullptr) || !alloc_batch(b)) return EXIT_FAILURE;
+	if (!upload_filter(b, c.h, nullptr, counting) || !alloc_batch(b)) return EXIT_FAILURE;
 	Reader r(b, (uint32_t)k, false, build_flush, &c);
 	for (const char* f : files)
 		if (int rc = r.read_file(f)) return rc;
 	if (int rc = r.flush()) return rc;
-	std::vector<unsigned char> image((m_bits + 7) / 8);
+	std::vector<unsigned char> image(image_bytes(c.h, counting));
+	const hipError_t rc = hipMemcpy(image.data(), b.d_filter, image.size(), hipMemcpyDeviceToHost);
+	if (rc != hipSuccess) return fail_hip("cannot fetch the filter", rc);
+	if ((counting ? ntc_cbloom_write : ntc_bloom_write)(out, &c.h, image.data()) != 0) return fail_lib();
+	std::fprintf(stderr, "ntbloom: %llu k-mers into %llu %s, %u hashes each\n", (unsigned long long)c.h.n_inserted, (unsigned long long)m_bits, counting ? "counters" : "bits",
+	             (uint32_t)n_hash);
+	return EXIT_SUCCESS;
+}
+
+int solid(int argc, char** argv)
+{
+	uint64_t min_count = 0, n_hash = 3;
+	double fpr = 0.0;
+	bool have_c = false, have_fpr = false, have_h = false;
+	const char* out = nullptr;
+	const char* hist = nullptr;
+	std::vector<const char*> files; // IN.cbf, then the input files
+	for (int i = 0; i < argc; ++i) {
+		const std::string a = argv[i];
+		auto value = [&](const char* flag) -> const char* {
+			if (i + 1 >= argc) {
+				(void)usage("missing value behind", flag);
+				return nullptr;
+			}
+			return argv[++i];
+		};
+		if (a == "--min-count") {
+			const char* v = value("--min-count");
+			if (!v) return EXIT_FAILURE;
+			if (!parse_u64(v, min_count) || min_count < 1 || min_count > 255) return usage("--min-count is not a number of 1 .. 255", v);
+			have_c = true;
+		} else if (a == "-H") {
+			const char* v = value("-H");
+			if (!v) return EXIT_FAILURE;
+			if (!parse_u64(v, n_hash) || n_hash < 1 || n_hash > 32) return usage("-H is not a number of 1 .. 32", v);
+			have_h = true;
+		} else if (a == "--fpr") {
+			const char* v = value("--fpr");
+			if (!v) return EXIT_FAILURE;
+			if (!parse_double(v, fpr) || !(fpr > 0.0 && fpr < 1.0)) return usage("--fpr is not a number inside (0, 1)", v);
+			have_fpr = true;
+		} else if (a == "--hist") {
+			hist = value("--hist");
+			if (!hist) return EXIT_FAILURE;
+		} else if (a == "-o") {
+			out = value("-o");
+			if (!out) return EXIT_FAILURE;
+		} else if (a.size() > 1 && a[0] == '-') {
+			return usage("unknown option", a.c_str());
+		} else {
+			files.push_back(argv[i]);
+		}
+	}
+	if (!have_c) return usage("solid needs --min-count C");
+	if (!out) return usage("solid needs -o OUT.bf");
+	if (files.empty()) return usage("solid needs IN.cbf");
+	const bool walk = files.size() > 1;
+	if (!walk && (hist || have_fpr || have_h)) return usage("--hist, --fpr and -H go with input files: without them IN.cbf is thresholded");
+	if (walk && (!hist || !have_fpr)) return usage("solid with input files needs --hist FILE and --fpr P");
+	BuildCtx c;
+	std::vector<unsigned char> counters;
+	if (!read_filter(files[0], c.c, nullptr, true)) return EXIT_FAILURE; // (the header first: the refusals below need no counter)
+	uint64_t m_bits = c.c.m_bits;
+	if (walk) {
+		uint64_t n = 0;
+		const int rc = hist_solid_n(hist, min_count, n);
+		if (rc == -1) return usage("no F0 line of a .hist file in", hist);
+		if (rc == -2) return usage("the f_i lines of the .hist file stop below --min-count - 1", hist);
+		if (rc == -3) return usage("the f_i lines of the .hist file sum to more than its F0", hist);
+		if (n == 0) return usage("F0 minus the f_i below --min-count is 0 in", hist);
+		if (ntc_bloom_size(n, (uint32_t)n_hash, fpr, &m_bits) != 0) return fail_lib();
+	} else {
+		n_hash = c.c.n_hash;
+	}
+	if (!read_filter(files[0], c.c, &counters, true)) return EXIT_FAILURE;
+	c.h = ntc_bloom_header{c.c.k, (uint32_t)n_hash, c.c.strand, 0, m_bits, walk ? 0 : c.c.n_inserted};
+	c.min_count = (uint32_t)min_count;
+	int n_dev = 0;
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
+		std::fprintf(stderr, "ntbloom: no HIP device\n");
+		return EXIT_FAILURE;
+	}
+	Buffers b;
+	if (!upload_filter(b, c.c, &counters, true, &b.d_counters) || !upload_filter(b, c.h, nullptr)) return EXIT_FAILURE;
+	if (walk) {
+		if (!alloc_batch(b)) return EXIT_FAILURE;
+		Reader r(b, c.h.k, false, build_flush, &c);
+		for (size_t i = 1; i < files.size(); ++i)
+			if (int rc = r.read_file(files[i])) return rc;
+		if (int rc = r.flush()) return rc;
+	} else if (ntc_cbloom_threshold_device(0, nullptr, b.d_counters, c.c.m_bits, c.min_count, b.d_filter) != 0) {
+		return fail_lib();
+	}
+	std::vector<unsigned char> image(image_bytes(c.h, false));
 	const hipError_t rc = hipMemcpy(image.data(), b.d_filter, image.size(), hipMemcpyDeviceToHost);
 	if (rc != hipSuccess) return fail_hip("cannot fetch the filter", rc);
 	if (ntc_bloom_write(out, &c.h, image.data()) != 0) return fail_lib();
-	std::fprintf(stderr, "ntbloom: %llu k-mers into %llu bits, %u hashes each\n", (unsigned long long)c.h.n_inserted, (unsigned long long)m_bits, (uint32_t)n_hash);
+	if (walk)
+		std::fprintf(stderr, "ntbloom: %llu k-mers counted at least %u times into %llu bits, %u hashes each\n", (unsigned long long)c.h.n_inserted, c.min_count,
+		             (unsigned long long)m_bits, (uint32_t)n_hash);
+	else
+		std::fprintf(stderr, "ntbloom: the counters of at least %u into %llu bits\n", c.min_count, (unsigned long long)m_bits);
 	return EXIT_SUCCESS;
 }
 
 int query(int argc, char** argv)
 {
+	QueryCtx c;
+	bool have_c = false;
+	if (argc >= 1 && std::strcmp(argv[0], "--min-count") == 0) {
+		if (argc < 2) return usage("missing value behind", "--min-count");
+		uint64_t v = 0;
+		if (!parse_u64(argv[1], v) || v < 1 || v > 255) return usage("--min-count is not a number of 1 .. 255", argv[1]);
+		c.min_count = (uint32_t)v;
+		have_c = true;
+		argc -= 2, argv += 2;
+	}
 	if (argc < 2) return usage("query needs F.bf and at least one input file");
 	for (int i = 0; i < argc; ++i)
 		if (argv[i][0] == '-' && argv[i][1] != '\0') return usage("unknown option", argv[i]);
-	QueryCtx c;
+	c.counting = is_counting_file(argv[0]);
 	std::vector<unsigned char> image;
-	if (!read_filter(argv[0], c.h, &image)) return EXIT_FAILURE;
+	if (!read_filter(argv[0], c.h, nullptr, c.counting)) return EXIT_FAILURE;
+	if (have_c && !c.counting) return usage("--min-count goes with a counting filter (.cbf), not with", argv[0]);
+	if (!read_filter(argv[0], c.h, &image, c.counting)) return EXIT_FAILURE;
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
 		std::fprintf(stderr, "ntbloom: no HIP device\n");
 		return EXIT_FAILURE;
 	}
 	Buffers b;
-	if (!upload_filter(b, c.h, &image) || !alloc_batch(b)) return EXIT_FAILURE;
+	if (!upload_filter(b, c.h, &image, c.counting) || !alloc_batch(b)) return EXIT_FAILURE;
 	Reader r(b, c.h.k, true, query_flush, &c);
 	std::printf("name\tlength\twindows\thits\tfraction\n");
 	for (int i = 1; i < argc; ++i)
@@ -408,12 +599,21 @@ int info(int argc, char** argv)
 	int n_dev = 0;
 	const bool gpu = hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0;
 	std::vector<unsigned char> image;
-	if (!read_filter(argv[0], h, gpu ? &image : nullptr)) return EXIT_FAILURE;
-	std::printf("file\t%s\nk\t%u\nhashes\t%u\nstrand\t%s\nbits\t%llu\ninserted\t%llu\n", argv[0], h.k, h.n_hash, kStrand[h.strand], (unsigned long long)h.m_bits,
-	            (unsigned long long)h.n_inserted);
+	const bool counting = is_counting_file(argv[0]);
+	if (!read_filter(argv[0], h, gpu ? &image : nullptr, counting)) return EXIT_FAILURE;
+	std::printf("file\t%s\nk\t%u\nhashes\t%u\nstrand\t%s\n%s\t%llu\ninserted\t%llu\n", argv[0], h.k, h.n_hash, kStrand[h.strand], counting ? "counters" : "bits",
+	            (unsigned long long)h.m_bits, (unsigned long long)h.n_inserted);
 	if (!gpu) return EXIT_SUCCESS;
 	Buffers b;
-	if (!upload_filter(b, h, &image)) return EXIT_FAILURE;
+	if (!upload_filter(b, h, &image, counting)) return EXIT_FAILURE;
+	if (counting) {
+		uint64_t hist[256];
+		if (ntc_cbloom_hist_device(0, nullptr, b.d_filter, h.m_bits, hist) != 0) return fail_lib();
+		const uint64_t used = h.m_bits - hist[0];
+		const double occ = (double)used / (double)h.m_bits;
+		std::printf("nonzero\t%llu\nsaturated\t%llu\noccupancy\t%.6f\nfpr\t%.6g\n", (unsigned long long)used, (unsigned long long)hist[255], occ, std::pow(occ, (double)h.n_hash));
+		return EXIT_SUCCESS;
+	}
 	uint64_t pop = 0;
 	if (ntc_bloom_popcount_device(0, nullptr, b.d_filter, h.m_bits, &pop) != 0) return fail_lib();
 	const double occ = (double)pop / (double)h.m_bits;
@@ -427,7 +627,9 @@ int main(int argc, char** argv)
 {
 	if (argc < 2) return usage("no command");
 	const std::string cmd = argv[1];
-	if (cmd == "build") return build(argc - 2, argv + 2);
+	if (cmd == "build") return build(argc - 2, argv + 2, false);
+	if (cmd == "count") return build(argc - 2, argv + 2, true);
+	if (cmd == "solid") return solid(argc - 2, argv + 2);
 	if (cmd == "query") return query(argc - 2, argv + 2);
 	if (cmd == "info") return info(argc - 2, argv + 2);
 	return usage("unknown command", argv[1]);
