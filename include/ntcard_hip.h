@@ -490,7 +490,7 @@ int ntc_bloom_query_hashes_device(int32_t device, void *stream, const void *d_fi
 int ntc_bloom_popcount_device(int32_t device, void *stream, const void *d_filter, uint64_t m_bits, uint64_t *pop);
 int ntc_bloom_or_device(int32_t device, void *stream, void *d_dst, const void *d_src, uint64_t m_bits);
 typedef struct {
-    uint32_t k, n_hash, strand, reserved;   /* strand: 0 canonical, 1 forward, 2 reverse; reserved: 0 */
+    uint32_t k, n_hash, strand, reserved;   /* strand: 0 canonical, 1 forward, 2 reverse; reserved: 0 (a blocked filter's file: 512) */
     uint64_t m_bits, n_inserted;            /* n_inserted: the windows inserted so far (a count of insertions, not of distinct k-mers) */
 } ntc_bloom_header;
 int ntc_bloom_write(const char *path, const ntc_bloom_header *h, const void *filter_bytes);
@@ -543,6 +543,55 @@ int ntc_cbloom_add_device(int32_t device, void *stream, void *d_dst, const void 
 int ntc_cbloom_hist_device(int32_t device, void *stream, const void *d_counters, uint64_t m, uint64_t *hist_u64);
 int ntc_cbloom_write(const char *path, const ntc_bloom_header *h, const void *counter_bytes);
 int ntc_cbloom_read(const char *path, ntc_bloom_header *h, void *counter_bytes, uint64_t cap_bytes);
+
+/* BLOCKED BLOOM FILTERS (additive to ABI 6: ten calls, one constant; NTC_ABI_VERSION and every other declaration are unchanged).  A second kind of filter
+ * beside the plain one, not a change to it: all n_hash bits of a k-mer lie in ONE aligned block of NTC_BBLOOM_BLOCK_BITS = 512 bits, a 64-byte line
+ * (Putze, Sanders, Singler 2007), so a build or a query fetches one random line per k-mer where the plain filter fetches n_hash.  The price is a somewhat
+ * larger filter for the same false positive rate (about 2 % more bits at three hashes and 1 %) and a file the reference's tools do not read.  Input,
+ * strands, streams, scratch and the walk are the plain calls'.
+ *   The format    m_bits bits, a multiple of 512 with 512 <= m_bits < 2^40; n_blocks = m_bits / 512.  For a window value h_0:
+ *       block     b = h_0 mod n_blocks (exact for every 64-bit h_0)
+ *       position  p_i = (g >> (55 - 9 * (i mod 4))) & 511 for i = 0 .. n_hash - 1, g = the multi-hash of nthash.hpp:381-390 with index 1 + i / 4
+ *                 (g = t ^ t >> 27, t = h_0 * ((1 + i / 4) ^ k * multiSeed)): four 9-bit fields from the TOP 36 bits of each multi-hash value, highest
+ *                 first.  The top bits, because the low bits of g depend only on the low bits of h_0 — which chose the block when n_blocks is a power of two.
+ *       bit       loc_i = 512 * b + p_i by the plain filter's rule, bit 7 - loc % 8 of byte loc / 8.  Positions of one k-mer that coincide set one bit.
+ *       The image is therefore an ORDINARY BIT IMAGE of m_bits bits: ntc_bloom_popcount_device and ntc_bloom_or_device serve a blocked filter unchanged,
+ *       and the filter's memory is the plain filter's (m_bits / 8 bytes, 4-byte aligned, zeroed by the caller; there is no padding).
+ *       For n_hash > 8 the reference's multi-hash values are linearly related (their multipliers differ in four low bits) and the realised false positive
+ *       rate can lie above the formula's — up to 14 % in single runs at n_hash = 32.  A property of the multi-hash, not repaired here.
+ *   ntc_bbloom_fpr   pure host: *fpr = sum_j Poisson(j; l) * (1 - (1 - 1/512)^(j * n_hash))^n_hash, l = 512 * n_distinct / m_bits — the load of a block is
+ *       Poisson, and a block with j k-mers answers a foreign k-mer like a 512-bit filter.  Summed until the tail left is below 1e-15 of the sum.
+ *       n_distinct may be 0 (*fpr = 0).  NTC_ERR_ARG for an m_bits that is no legal blocked size, n_hash outside 1 .. 32, a NULL fpr.
+ *   ntc_bbloom_size  pure host: the smallest multiple of 512 whose ntc_bbloom_fpr is <= fpr, by bisection over n_blocks.  NTC_ERR_ARG where ntc_bloom_size
+ *       is: n_distinct == 0, n_hash outside 1 .. 32, fpr outside (0, 1), a NULL m_bits or a result of 2^40 bits or more.
+ *   ntc_bbloom_insert_device / ntc_bbloom_query_device / ntc_bbloom_insert_hashes_device / ntc_bbloom_query_hashes_device
+ *       the plain calls' signatures and results on a blocked filter.  An insert loads the dword first and issues one atomic OR per dword that still
+ *       lacks a bit: bits of one k-mer that share a dword go in one atomic.  A query leaves at the first clear bit.
+ *   ntc_bbloom_hist_device  hist_u64[v] = the blocks that hold v set bits, v = 0 .. 512 (HOST array of 513), exact integers.
+ *       sum_v hist[v] * (v / 512)^n_hash / n_blocks is the realised false positive rate: the chance that a k-mer never inserted finds its bits set.
+ *   ntc_bbloom_insert_solid_device  ntc_bloom_insert_solid_device with a blocked destination: sets every window whose count in a finished counting
+ *       filter (d_counters, m, c_n_hash) is >= min_count; *n_windows = the windows that passed (may be NULL).
+ * Before the device is touched, NTC_ERR_ARG for what the plain calls refuse, and for an m_bits that is no multiple of 512 or outside 512 .. 2^40 - 512.
+ * A blocked filter FILE: the 8 bytes "NTCBB1\0\0", ntc_bloom_header with reserved = the block size in bits (512 is the only accepted value), then the
+ * m_bits / 8 bytes.  ntc_bbloom_write / ntc_bbloom_read behave as ntc_bloom_write / ntc_bloom_read do (".part" and rename; the size query with a NULL
+ * array; the length checked against the header). */
+#define NTC_BBLOOM_BLOCK_BITS 512u
+int ntc_bbloom_fpr(uint64_t n_distinct, uint64_t m_bits, uint32_t n_hash, double *fpr);
+int ntc_bbloom_size(uint64_t n_distinct, uint32_t n_hash, double fpr, uint64_t *m_bits);
+int ntc_bbloom_insert_device(int32_t device, void *stream, void *d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k, uint32_t strand,
+                             const void *d_bases, const uint64_t *offsets, uint64_t n_seqs, uint64_t *n_windows);
+int ntc_bbloom_query_device(int32_t device, void *stream, const void *d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k, uint32_t strand,
+                            const void *d_bases, const uint64_t *offsets, uint64_t n_seqs, void *d_windows_u32, void *d_hits_u32);
+int ntc_bbloom_insert_hashes_device(int32_t device, void *stream, void *d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k, const void *d_h0_u64,
+                                    uint64_t n);
+int ntc_bbloom_query_hashes_device(int32_t device, void *stream, const void *d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k,
+                                   const void *d_h0_u64, uint64_t n, void *d_flags_u8);
+int ntc_bbloom_hist_device(int32_t device, void *stream, const void *d_filter, uint64_t m_bits, uint64_t *hist_u64);
+int ntc_bbloom_insert_solid_device(int32_t device, void *stream, void *d_filter, uint64_t m_bits, uint32_t n_hash, const void *d_counters, uint64_t m,
+                                   uint32_t c_n_hash, uint32_t min_count, uint32_t k, uint32_t strand, const void *d_bases, const uint64_t *offsets,
+                                   uint64_t n_seqs, uint64_t *n_windows);
+int ntc_bbloom_write(const char *path, const ntc_bloom_header *h, const void *filter_bytes);
+int ntc_bbloom_read(const char *path, ntc_bloom_header *h, void *filter_bytes, uint64_t cap_bytes);
 
 int ntc_sync(ntc_engine *e); /* wait for all submitted work */
 

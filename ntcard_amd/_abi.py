@@ -31,9 +31,12 @@ ABI_SYMBOLS = [
     "ntc_bloom_popcount_device", "ntc_bloom_or_device", "ntc_bloom_write", "ntc_bloom_read",
     "ntc_cbloom_insert_device", "ntc_cbloom_query_device", "ntc_cbloom_profile_device", "ntc_cbloom_insert_hashes_device", "ntc_cbloom_query_hashes_device",
     "ntc_cbloom_threshold_device", "ntc_bloom_insert_solid_device", "ntc_cbloom_add_device", "ntc_cbloom_hist_device", "ntc_cbloom_write", "ntc_cbloom_read",
+    "ntc_bbloom_fpr", "ntc_bbloom_size", "ntc_bbloom_insert_device", "ntc_bbloom_query_device", "ntc_bbloom_insert_hashes_device", "ntc_bbloom_query_hashes_device",
+    "ntc_bbloom_hist_device", "ntc_bbloom_insert_solid_device", "ntc_bbloom_write", "ntc_bbloom_read",
 ]
 
 BLOOM_BLOCK = 4096  # NTC_BLOOM_BLOCK
+BBLOOM_BLOCK_BITS = 512  # NTC_BBLOOM_BLOCK_BITS
 
 
 class NtcBloomHeader(C.Structure):
@@ -239,6 +242,16 @@ def lib():
     L.ntc_cbloom_hist_device.argtypes = [i32, p, p, u64, p]
     L.ntc_cbloom_write.argtypes = [C.c_char_p, C.POINTER(NtcBloomHeader), p]
     L.ntc_cbloom_read.argtypes = [C.c_char_p, C.POINTER(NtcBloomHeader), p, u64]
+    L.ntc_bbloom_fpr.argtypes = [u64, u64, u32, C.POINTER(C.c_double)]
+    L.ntc_bbloom_size.argtypes = [u64, u32, C.c_double, C.POINTER(u64)]
+    L.ntc_bbloom_insert_device.argtypes = [i32, p, p, u64, u32, u32, u32, p, p, u64, C.POINTER(u64)]
+    L.ntc_bbloom_query_device.argtypes = [i32, p, p, u64, u32, u32, u32, p, p, u64, p, p]
+    L.ntc_bbloom_insert_hashes_device.argtypes = [i32, p, p, u64, u32, u32, p, u64]
+    L.ntc_bbloom_query_hashes_device.argtypes = [i32, p, p, u64, u32, u32, p, u64, p]
+    L.ntc_bbloom_hist_device.argtypes = [i32, p, p, u64, p]
+    L.ntc_bbloom_insert_solid_device.argtypes = [i32, p, p, u64, u32, p, u64, u32, u32, u32, u32, p, p, u64, C.POINTER(u64)]
+    L.ntc_bbloom_write.argtypes = [C.c_char_p, C.POINTER(NtcBloomHeader), p]
+    L.ntc_bbloom_read.argtypes = [C.c_char_p, C.POINTER(NtcBloomHeader), p, u64]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("ntc_abi_version", "ntc_max_k", "ntc_last_error", "ntc_destroy", "ntc_tiled_bytes"):

@@ -2,14 +2,15 @@
 counting filters (ntc_cbloom_*; DESIGN.md §4 "Counting filters and solid k-mers"): the step behind its f_i, k-mer counts and the filter of the solid k-mers.
 
 The layout is the reference's vendor/ntHash/lib/BloomFilter.hpp — position h_i % m, bit 7 - loc % 8 of byte loc / 8, h_i the multi-hash of
-nthash.hpp:381-390 — so `BloomFilter.bytes()` is what `storeFilter` writes.  torch is plumbing only: it owns the filter's device memory.
+nthash.hpp:381-390 — so `BloomFilter.bytes()` is what `storeFilter` writes.  BlockedBloomFilter (ntc_bbloom_*; DESIGN.md §4 "Blocked filters") is a
+second kind beside it, in a layout of its own: every bit of a k-mer in one 64-byte block.  torch is plumbing only: it owns the filter's device memory.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _abi
-from ._abi import BLOOM_BLOCK, NtcBloomHeader, check  # noqa: F401  (BLOOM_BLOCK is re-exported)
+from ._abi import BBLOOM_BLOCK_BITS, BLOOM_BLOCK, NtcBloomHeader, check  # noqa: F401  (BLOOM_BLOCK is re-exported)
 
 _STRANDS = {"canonical": 0, "forward": 1, "reverse": 2}
 _STRAND_NAMES = {v: s for s, v in _STRANDS.items()}
@@ -162,6 +163,155 @@ def read_file(path):
     image = np.zeros((h.m_bits + 7) // 8, dtype=np.uint8)
     check(L.ntc_bloom_read(str(path).encode(), C.byref(h), image.ctypes.data_as(C.c_void_p), image.size))
     return {"k": h.k, "n_hash": h.n_hash, "strand": _STRAND_NAMES[h.strand], "m_bits": int(h.m_bits), "n_inserted": int(h.n_inserted)}, image
+
+
+def bbloom_fpr(n_distinct, m_bits, n_hash=3):
+    """ntc_bbloom_fpr: the false positive rate of a blocked filter of m_bits bits that holds n_distinct k-mers"""
+    fpr = C.c_double(0.0)
+    check(_abi.lib().ntc_bbloom_fpr(int(n_distinct), int(m_bits), int(n_hash), C.byref(fpr)))
+    return float(fpr.value)
+
+
+def bbloom_size(n_distinct, fpr, n_hash=3):
+    """ntc_bbloom_size: the bits of a blocked filter that holds n_distinct k-mers at false positive rate fpr, the smallest multiple of 512 that does"""
+    m = C.c_uint64(0)
+    check(_abi.lib().ntc_bbloom_size(int(n_distinct), int(n_hash), float(fpr), C.byref(m)))
+    return int(m.value)
+
+
+class BlockedBloomFilter:
+    """A BLOCKED Bloom filter of m_bits bits (a multiple of 512) on one device: all n_hash bits of a k-mer lie in one aligned 512-bit block — one random
+    cache line per k-mer where BloomFilter fetches n_hash — at the price of a somewhat larger filter for the same false positive rate (bbloom_size) and
+    of a format of its own (include/ntcard_hip.h: ntc_bbloom_*).  Constructor, inputs and streams as BloomFilter's; the image is an ordinary bit image,
+    so popcount and merge are BloomFilter's calls."""
+
+    def __init__(self, m_bits, n_hash, k, strand="canonical", device=0):
+        import torch
+        if strand not in _STRANDS:
+            raise ValueError(f"strand must be 'canonical', 'forward' or 'reverse', not {strand!r}")
+        m_bits, n_hash, k = int(m_bits), int(n_hash), int(k)
+        if not BBLOOM_BLOCK_BITS <= m_bits < 1 << 40 or m_bits % BBLOOM_BLOCK_BITS:
+            raise ValueError(f"m_bits={m_bits} is no multiple of 512 in 512 .. 2^40 - 512")
+        if not 1 <= n_hash <= 32:
+            raise ValueError(f"n_hash={n_hash} outside 1 .. 32")
+        if not 1 <= k <= _abi.lib().ntc_max_k():
+            raise ValueError(f"k={k} outside 1 .. {_abi.lib().ntc_max_k()}")
+        self.m_bits, self.n_hash, self.k, self.strand, self.device = m_bits, n_hash, k, strand, int(device)
+        self.n_inserted = 0
+        self.n_bytes = m_bits // 8
+        self.n_blocks = m_bits // BBLOOM_BLOCK_BITS
+        self.filter = torch.zeros(self.n_bytes, dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    @classmethod
+    def for_distinct(cls, n, fpr, n_hash, k, strand="canonical", device=0):
+        """A filter sized by ntc_bbloom_size for n distinct k-mers at false positive rate fpr (n: ntCard's F0, as for BloomFilter.for_distinct)"""
+        return cls(bbloom_size(n, fpr, n_hash), n_hash, k, strand, device)
+
+    _stream = BloomFilter._stream
+    _bases = BloomFilter._bases
+    _hashes = BloomFilter._hashes
+    popcount = BloomFilter.popcount
+    bytes = BloomFilter.bytes
+
+    def merge(self, other):
+        """ORs another blocked filter of the same shape into this one (ntc_bloom_or_device: the image is an ordinary bit image)"""
+        if not isinstance(other, BlockedBloomFilter):
+            raise ValueError("merge: the other filter is no blocked filter")
+        BloomFilter.merge(self, other)
+
+    def _input(self, bases, offsets):
+        off = _offsets(offsets)
+        bases = self._bases(bases)
+        if int(off[-1]) > bases.numel():
+            raise ValueError("offsets reach behind the end of bases")
+        return bases, off
+
+    def insert(self, bases, offsets):
+        """Inserts every k-mer of the sequences; -> the windows inserted"""
+        bases, off = self._input(bases, offsets)
+        n = C.c_uint64(0)
+        check(_abi.lib().ntc_bbloom_insert_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k, _STRANDS[self.strand],
+                                                  bases.data_ptr(), off.ctypes.data_as(C.c_void_p), off.size - 1, C.byref(n)))
+        self.n_inserted += int(n.value)
+        return int(n.value)
+
+    def query(self, bases, offsets):
+        """-> (windows, hits): numpy uint32 [n_seqs] each, the k-mers of every sequence and those of them the filter holds"""
+        import torch
+        bases, off = self._input(bases, offsets)
+        n_seqs = off.size - 1
+        out = torch.empty((2, max(n_seqs, 1)), dtype=torch.int32, device=self.filter.device)
+        check(_abi.lib().ntc_bbloom_query_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k, _STRANDS[self.strand],
+                                                 bases.data_ptr(), off.ctypes.data_as(C.c_void_p), n_seqs, out[0].data_ptr(), out[1].data_ptr()))
+        host = out[:, :n_seqs].cpu().numpy().view(np.uint32)
+        return host[0].copy(), host[1].copy()
+
+    def insert_hashes(self, h0):
+        """Sets the n_hash bits of every given value h_0 (numpy uint64, or a 64-bit tensor on the device)"""
+        d = self._hashes(h0)
+        check(_abi.lib().ntc_bbloom_insert_hashes_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k,
+                                                         d.data_ptr() if d.numel() else None, d.numel()))
+        self.n_inserted += d.numel()
+
+    def query_hashes(self, h0):
+        """-> numpy bool [n]: whether all n_hash bits of each given h_0 are set"""
+        import torch
+        d = self._hashes(h0)
+        flags = torch.empty(max(d.numel(), 1), dtype=torch.uint8, device=self.filter.device)
+        check(_abi.lib().ntc_bbloom_query_hashes_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, self.k,
+                                                        d.data_ptr() if d.numel() else None, d.numel(), flags.data_ptr()))
+        return flags[: d.numel()].cpu().numpy().astype(bool)
+
+    def insert_solid(self, counting, bases, offsets, min_count):
+        """Inserts every k-mer of the sequences whose count in the CountingBloomFilter `counting` (this filter's k, strand and device) is >= min_count;
+        -> the windows that passed"""
+        if not isinstance(counting, CountingBloomFilter) or (counting.k, counting.strand, counting.device) != (self.k, self.strand, self.device):
+            raise ValueError("insert_solid: `counting` is a CountingBloomFilter of this filter's k, strand and device")
+        bases, off = self._input(bases, offsets)
+        n = C.c_uint64(0)
+        check(_abi.lib().ntc_bbloom_insert_solid_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, self.n_hash, counting.filter.data_ptr(),
+                                                        counting.m_bits, counting.n_hash, CountingBloomFilter._min_count(min_count), self.k, _STRANDS[self.strand],
+                                                        bases.data_ptr(), off.ctypes.data_as(C.c_void_p), off.size - 1, C.byref(n)))
+        self.n_inserted += int(n.value)
+        return int(n.value)
+
+    def block_hist(self):
+        """-> numpy uint64 [513]: how many blocks hold 0, 1, .. 512 set bits"""
+        h = np.zeros(BBLOOM_BLOCK_BITS + 1, dtype=np.uint64)
+        check(_abi.lib().ntc_bbloom_hist_device(self.device, self._stream(), self.filter.data_ptr(), self.m_bits, h.ctypes.data_as(C.c_void_p)))
+        return h
+
+    def fpr(self):
+        """sum_v hist[v] (v / 512)^n_hash / n_blocks: the chance that a k-mer that was never inserted finds all its bits set — per block, not from the
+        overall popcount: a block fuller than the average answers wrongly more often than the average says"""
+        h = self.block_hist()
+        v = np.arange(BBLOOM_BLOCK_BITS + 1, dtype=np.float64) / BBLOOM_BLOCK_BITS
+        return float((h.astype(np.float64) * v ** self.n_hash).sum() / self.n_blocks)
+
+    def write(self, path):
+        h = NtcBloomHeader(k=self.k, n_hash=self.n_hash, strand=_STRANDS[self.strand], reserved=BBLOOM_BLOCK_BITS, m_bits=self.m_bits, n_inserted=self.n_inserted)
+        image = np.ascontiguousarray(self.bytes())
+        check(_abi.lib().ntc_bbloom_write(str(path).encode(), C.byref(h), image.ctypes.data_as(C.c_void_p)))
+
+    @classmethod
+    def read(cls, path, device=0):
+        import torch
+        h, image = read_blocked_file(path)
+        f = cls(h["m_bits"], h["n_hash"], h["k"], h["strand"], device)
+        f.n_inserted = h["n_inserted"]
+        f.filter[: f.n_bytes] = torch.from_numpy(image).to(f.filter.device)
+        return f
+
+
+def read_blocked_file(path):
+    """ntc_bbloom_read -> (header dict, the byte image as numpy uint8): pure host"""
+    h = NtcBloomHeader()
+    L = _abi.lib()
+    check(L.ntc_bbloom_read(str(path).encode(), C.byref(h), None, 0))
+    image = np.zeros(h.m_bits // 8, dtype=np.uint8)
+    check(L.ntc_bbloom_read(str(path).encode(), C.byref(h), image.ctypes.data_as(C.c_void_p), image.size))
+    return {"k": h.k, "n_hash": h.n_hash, "strand": _STRAND_NAMES[h.strand], "m_bits": int(h.m_bits), "n_inserted": int(h.n_inserted),
+            "block_bits": int(h.reserved)}, image
 
 
 class CountingBloomFilter:

@@ -1,25 +1,30 @@
 // ntbloom_cli.cpp — `ntbloom`: Bloom filters of every k-mer of the input, in the reference's layout (vendor/ntHash/lib/BloomFilter.hpp), sized from ntcard's F0
 // (include/ntcard_hip.h: ntc_bloom_*; DESIGN.md §4 "Bloom filters"), and counting filters and the filter of the solid k-mers, sized from its f_i
 // (ntc_cbloom_*; DESIGN.md §4 "Counting filters and solid k-mers").
-//   ntbloom build -k K [-H N] [--strand=canonical|forward|reverse] (-m BITS | --distinct N --fpr P | --hist FILE --fpr P) -o OUT.bf FILE...
+//   ntbloom build -k K [-H N] [--blocked] [--strand=canonical|forward|reverse] (-m BITS | --distinct N --fpr P | --hist FILE --fpr P) -o OUT.bf FILE...
 //                               inserts every k-mer of the files.  The filter has BITS bits, or what ntc_bloom_size gives for N distinct k-mers at false
 //                               positive rate P; --hist takes N from the F0 line of a `.hist` file as ntcard writes it, so that
 //                               `ntcard -k 32 -p s reads.fq && ntbloom build -k 32 --hist s_k32.hist --fpr 0.01 -o s.bf reads.fq` composes.  -H: hashes per
-//                               k-mer (default 3).  OUT.bf is written whole or not at all (ntc_bloom_write).
+//                               k-mer (default 3).  OUT.bf is written whole or not at all (ntc_bloom_write).  --blocked: a BLOCKED filter (ntc_bbloom_*;
+//                               DESIGN.md §4 "Blocked filters"), every bit of a k-mer in one 64-byte block: BITS is a multiple of 512, --distinct and --hist
+//                               size by ntc_bbloom_size, the file has a magic of its own.  --blocked with `count` is refused: there is no blocked counting filter
 //   ntbloom count -k K [-H N] [--strand=...] (-m COUNTERS | --distinct N --fpr P | --hist FILE --fpr P) -o OUT.cbf FILE...
 //                               the same with 8-bit counters: every k-mer adds one to each of its N counters, saturating at 255 (ntc_cbloom_write)
-//   ntbloom solid --min-count C [--fpr P --hist FILE [-H N]] -o OUT.bf IN.cbf [FILE...]
+//   ntbloom solid --min-count C [--fpr P --hist FILE [-H N] [--blocked]] -o OUT.bf IN.cbf [FILE...]
 //                               the plain filter of the k-mers counted at least C times (k and strand come from IN.cbf).  Without input files IN.cbf is
 //                               thresholded: OUT.bf has as many bits as IN.cbf counters and its hash count.  With input files, --hist and --fpr the
 //                               files are walked again and every k-mer whose count in IN.cbf is >= C goes into a filter sized by ntc_bloom_size for
-//                               n = F0 - sum_{i<C} f_i of the `.hist` file (its F0 line and its "i\tf_i" lines), N hashes (default 3):
+//                               n = F0 - sum_{i<C} f_i of the `.hist` file (its F0 line and its "i\tf_i" lines), N hashes (default 3); --blocked makes that
+//                               filter a blocked one (ntc_bbloom_size, ntc_bbloom_insert_solid_device) and is refused without input files — a threshold has
+//                               the counting filter's positions, which are not blocked:
 //                               `ntcard -k 32 -p s reads.fq && ntbloom count -k 32 --hist s_k32.hist --fpr 0.01 -o s.cbf reads.fq &&
 //                                ntbloom solid --min-count 2 --hist s_k32.hist --fpr 0.01 -o solid.bf s.cbf reads.fq && ntbloom query solid.bf other.fq`
-//   ntbloom query [--min-count C] F.bf|F.cbf FILE...
+//   ntbloom query [--min-count C] F.bf|F.cbf|F.bbf FILE...
 //                               one TSV row per record: name, length, windows, hits, hits / windows (k, hashes and strand come from the file, whose
-//                               magic says which kind it is).  On a .cbf a hit is a window whose count is >= C (default 1); --min-count with a .bf is refused
-//   ntbloom info F.bf|F.cbf     the header, and with a GPU the popcount, the occupancy and the false positive rate it implies (a .cbf: the counters that
-//                               are not 0, the saturated ones, the rate of a false "count >= 1"); without one the header alone
+//                               magic says which of the three kinds it is).  On a .cbf a hit is a window whose count is >= C (default 1); --min-count with a .bf is refused
+//   ntbloom info F.bf|F.cbf|F.bbf  the header (a blocked filter: its block size too), and with a GPU the popcount, the occupancy and the false positive
+//                               rate it implies (a .cbf: the counters that are not 0, the saturated ones, the rate of a false "count >= 1"; a blocked
+//                               filter: the rate from the histogram of its blocks' set bits); without one the header alone
 // Input: FASTA (a record's lines are joined) and FASTQ, plain or through the decompressor its extension names (cli_common.hpp: LineReader).  One thread
 // reads records into a pinned batch of at most 256 MiB, uploads it and calls ntc_bloom_insert_device / ntc_bloom_query_device.  SAM is not read here.
 // Every malformed argument is refused with a message that names it, before a device is looked for.
@@ -51,11 +56,11 @@ int usage(const char* why, const char* what = nullptr)
 	else
 		std::fprintf(stderr, "ntbloom: %s\n", why);
 	std::fprintf(stderr,
-	             "usage: ntbloom build -k K [-H N] [--strand=canonical|forward|reverse] (-m BITS | --distinct N --fpr P | --hist FILE --fpr P) -o OUT.bf FILE...\n"
+	             "usage: ntbloom build -k K [-H N] [--blocked] [--strand=canonical|forward|reverse] (-m BITS | --distinct N --fpr P | --hist FILE --fpr P) -o OUT.bf FILE...\n"
 	             "       ntbloom count -k K [-H N] [--strand=canonical|forward|reverse] (-m COUNTERS | --distinct N --fpr P | --hist FILE --fpr P) -o OUT.cbf FILE...\n"
-	             "       ntbloom solid --min-count C [--fpr P --hist FILE [-H N]] -o OUT.bf IN.cbf [FILE...]\n"
-	             "       ntbloom query [--min-count C] F.bf|F.cbf FILE...\n"
-	             "       ntbloom info F.bf|F.cbf\n");
+	             "       ntbloom solid --min-count C [--fpr P --hist FILE [-H N] [--blocked]] -o OUT.bf IN.cbf [FILE...]\n"
+	             "       ntbloom query [--min-count C] F.bf|F.cbf|F.bbf FILE...\n"
+	             "       ntbloom info F.bf|F.cbf|F.bbf\n");
 	return EXIT_FAILURE;
 }
 
@@ -142,15 +147,19 @@ int hist_solid_n(const char* path, uint64_t c, uint64_t& n)
 	return 0;
 }
 
-// the kind of a filter file by its magic: 1 a counting filter, 0 anything else (ntc_bloom_read then says what is wrong with it)
-bool is_counting_file(const char* path)
+// the kind of a filter file by its magic: a counting filter, a blocked filter, or plain — which is also anything else (ntc_bloom_read then says what is
+// wrong with it)
+enum Kind { kPlain = 0, kCounting = 1, kBlocked = 2 };
+Kind file_kind(const char* path)
 {
 	FILE* f = std::fopen(path, "rb");
-	if (!f) return false;
+	if (!f) return kPlain;
 	char magic[8] = {0};
-	const bool yes = std::fread(magic, 1, 8, f) == 8 && std::memcmp(magic, "NTCCB1\0\0", 8) == 0;
+	const bool whole = std::fread(magic, 1, 8, f) == 8;
 	std::fclose(f);
-	return yes;
+	if (whole && std::memcmp(magic, "NTCCB1\0\0", 8) == 0) return kCounting;
+	if (whole && std::memcmp(magic, "NTCBB1\0\0", 8) == 0) return kBlocked;
+	return kPlain;
 }
 
 // device and pinned memory of one run, freed on every way out
@@ -276,6 +285,7 @@ bool alloc_batch(Buffers& b)
 struct BuildCtx {
 	ntc_bloom_header h;
 	bool counting = false;       // count: d_filter holds counters
+	bool blocked = false;        // build --blocked, solid --blocked: d_filter is a blocked filter
 	ntc_bloom_header c{};        // solid: the counting filter in d_counters ...
 	uint32_t min_count = 0;      // ... and the count a k-mer needs (0: not solid)
 };
@@ -287,8 +297,10 @@ int build_flush(Reader& r, void* ctx)
 	uint64_t n = 0;
 	int rc2;
 	if (c.min_count)
-		rc2 = ntc_bloom_insert_solid_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, r.b.d_counters, c.c.m_bits, c.c.n_hash, c.min_count, c.h.k, c.h.strand, r.b.d_bases,
-		                                    r.offsets.data(), r.offsets.size() - 1, &n);
+		rc2 = (c.blocked ? ntc_bbloom_insert_solid_device : ntc_bloom_insert_solid_device)(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, r.b.d_counters, c.c.m_bits, c.c.n_hash,
+		                                                                                   c.min_count, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), r.offsets.size() - 1, &n);
+	else if (c.blocked)
+		rc2 = ntc_bbloom_insert_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), r.offsets.size() - 1, &n);
 	else if (c.counting)
 		rc2 = ntc_cbloom_insert_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), r.offsets.size() - 1, &n);
 	else
@@ -301,6 +313,7 @@ int build_flush(Reader& r, void* ctx)
 struct QueryCtx {
 	ntc_bloom_header h;
 	bool counting = false;
+	bool blocked = false;
 	uint32_t min_count = 1;
 	std::vector<uint32_t> counts;
 };
@@ -320,7 +333,8 @@ int query_flush(Reader& r, void* ctx)
 	uint32_t* d_w = r.b.d_counts;
 	uint32_t* d_h = r.b.d_counts + r.b.seq_cap;
 	const int rc2 = c.counting ? ntc_cbloom_query_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, c.min_count, d_w, d_h)
-	                           : ntc_bloom_query_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, d_w, d_h);
+	                : c.blocked ? ntc_bbloom_query_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, d_w, d_h)
+	                            : ntc_bloom_query_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, d_w, d_h);
 	if (rc2 != 0) return fail_lib();
 	c.counts.resize(2 * n_seqs);
 	rc = hipMemcpy(c.counts.data(), d_w, n_seqs * 4, hipMemcpyDeviceToHost);
@@ -348,9 +362,10 @@ bool upload_filter(Buffers& b, const ntc_bloom_header& h, const std::vector<unsi
 	return false;
 }
 
-bool read_filter(const char* path, ntc_bloom_header& h, std::vector<unsigned char>* image, bool counting = false)
+bool read_filter(const char* path, ntc_bloom_header& h, std::vector<unsigned char>* image, Kind kind = kPlain)
 {
-	const auto read = counting ? ntc_cbloom_read : ntc_bloom_read;
+	const bool counting = kind == kCounting;
+	const auto read = counting ? ntc_cbloom_read : kind == kBlocked ? ntc_bbloom_read : ntc_bloom_read;
 	if (read(path, &h, nullptr, 0) != 0) {
 		(void)fail_lib();
 		return false;
@@ -371,7 +386,7 @@ int build(int argc, char** argv, bool counting)
 	auto needs = [&](const char* what) { return usage((std::string(cmd) + " needs " + what).c_str()); };
 	uint64_t k = 0, n_hash = 3, m_bits = 0, distinct = 0;
 	double fpr = 0.0;
-	bool have_k = false, have_m = false, have_distinct = false, have_fpr = false;
+	bool have_k = false, have_m = false, have_distinct = false, have_fpr = false, blocked = false;
 	uint32_t strand = 0;
 	const char* out = nullptr;
 	const char* hist = nullptr;
@@ -415,6 +430,8 @@ int build(int argc, char** argv, bool counting)
 		} else if (a == "-o") {
 			out = value("-o");
 			if (!out) return EXIT_FAILURE;
+		} else if (a == "--blocked") {
+			blocked = true;
 		} else if (a.compare(0, 9, "--strand=") == 0) {
 			const std::string s = a.substr(9);
 			if (s == "canonical") strand = 0;
@@ -427,6 +444,7 @@ int build(int argc, char** argv, bool counting)
 			files.push_back(argv[i]);
 		}
 	}
+	if (blocked && counting) return usage("--blocked goes with build and solid: there is no blocked counting filter");
 	if (!have_k) return needs("-k");
 	if (!out) return needs(counting ? "-o OUT.cbf" : "-o OUT.bf");
 	const int ways = (have_m ? 1 : 0) + (have_distinct ? 1 : 0) + (hist ? 1 : 0);
@@ -436,11 +454,13 @@ int build(int argc, char** argv, bool counting)
 	if (files.empty()) return needs("at least one input file");
 	if (hist && !hist_f0(hist, distinct)) return usage("no F0 line of a .hist file in", hist);
 	if (hist && distinct == 0) return usage("the F0 of the .hist file is 0", hist);
-	if (!have_m && ntc_bloom_size(distinct, (uint32_t)n_hash, fpr, &m_bits) != 0) return fail_lib();
+	if (blocked && have_m && m_bits % NTC_BBLOOM_BLOCK_BITS != 0) return usage("-m of a blocked filter is not a multiple of 512", std::to_string(m_bits).c_str());
+	if (!have_m && (blocked ? ntc_bbloom_size : ntc_bloom_size)(distinct, (uint32_t)n_hash, fpr, &m_bits) != 0) return fail_lib();
 
 	BuildCtx c;
-	c.h = ntc_bloom_header{(uint32_t)k, (uint32_t)n_hash, strand, 0, m_bits, 0};
+	c.h = ntc_bloom_header{(uint32_t)k, (uint32_t)n_hash, strand, blocked ? NTC_BBLOOM_BLOCK_BITS : 0u, m_bits, 0};
 	c.counting = counting;
+	c.blocked = blocked;
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
 		std::fprintf(stderr, "ntbloom: no HIP device\n");
@@ -455,9 +475,9 @@ int build(int argc, char** argv, bool counting)
 	std::vector<unsigned char> image(image_bytes(c.h, counting));
 	const hipError_t rc = hipMemcpy(image.data(), b.d_filter, image.size(), hipMemcpyDeviceToHost);
 	if (rc != hipSuccess) return fail_hip("cannot fetch the filter", rc);
-	if ((counting ? ntc_cbloom_write : ntc_bloom_write)(out, &c.h, image.data()) != 0) return fail_lib();
-	std::fprintf(stderr, "ntbloom: %llu k-mers into %llu %s, %u hashes each\n", (unsigned long long)c.h.n_inserted, (unsigned long long)m_bits, counting ? "counters" : "bits",
-	             (uint32_t)n_hash);
+	if ((counting ? ntc_cbloom_write : blocked ? ntc_bbloom_write : ntc_bloom_write)(out, &c.h, image.data()) != 0) return fail_lib();
+	std::fprintf(stderr, "ntbloom: %llu k-mers into %llu %s, %u hashes each\n", (unsigned long long)c.h.n_inserted, (unsigned long long)m_bits,
+	             counting ? "counters" : blocked ? "bits in blocks of 512" : "bits", (uint32_t)n_hash);
 	return EXIT_SUCCESS;
 }
 
@@ -465,7 +485,7 @@ int solid(int argc, char** argv)
 {
 	uint64_t min_count = 0, n_hash = 3;
 	double fpr = 0.0;
-	bool have_c = false, have_fpr = false, have_h = false;
+	bool have_c = false, have_fpr = false, have_h = false, blocked = false;
 	const char* out = nullptr;
 	const char* hist = nullptr;
 	std::vector<const char*> files; // IN.cbf, then the input files
@@ -499,6 +519,8 @@ int solid(int argc, char** argv)
 		} else if (a == "-o") {
 			out = value("-o");
 			if (!out) return EXIT_FAILURE;
+		} else if (a == "--blocked") {
+			blocked = true;
 		} else if (a.size() > 1 && a[0] == '-') {
 			return usage("unknown option", a.c_str());
 		} else {
@@ -509,11 +531,12 @@ int solid(int argc, char** argv)
 	if (!out) return usage("solid needs -o OUT.bf");
 	if (files.empty()) return usage("solid needs IN.cbf");
 	const bool walk = files.size() > 1;
+	if (!walk && blocked) return usage("--blocked goes with input files: a threshold of IN.cbf has the counting filter's positions, which are not blocked");
 	if (!walk && (hist || have_fpr || have_h)) return usage("--hist, --fpr and -H go with input files: without them IN.cbf is thresholded");
 	if (walk && (!hist || !have_fpr)) return usage("solid with input files needs --hist FILE and --fpr P");
 	BuildCtx c;
 	std::vector<unsigned char> counters;
-	if (!read_filter(files[0], c.c, nullptr, true)) return EXIT_FAILURE; // (the header first: the refusals below need no counter)
+	if (!read_filter(files[0], c.c, nullptr, kCounting)) return EXIT_FAILURE; // (the header first: the refusals below need no counter)
 	uint64_t m_bits = c.c.m_bits;
 	if (walk) {
 		uint64_t n = 0;
@@ -522,13 +545,14 @@ int solid(int argc, char** argv)
 		if (rc == -2) return usage("the f_i lines of the .hist file stop below --min-count - 1", hist);
 		if (rc == -3) return usage("the f_i lines of the .hist file sum to more than its F0", hist);
 		if (n == 0) return usage("F0 minus the f_i below --min-count is 0 in", hist);
-		if (ntc_bloom_size(n, (uint32_t)n_hash, fpr, &m_bits) != 0) return fail_lib();
+		if ((blocked ? ntc_bbloom_size : ntc_bloom_size)(n, (uint32_t)n_hash, fpr, &m_bits) != 0) return fail_lib();
 	} else {
 		n_hash = c.c.n_hash;
 	}
-	if (!read_filter(files[0], c.c, &counters, true)) return EXIT_FAILURE;
-	c.h = ntc_bloom_header{c.c.k, (uint32_t)n_hash, c.c.strand, 0, m_bits, walk ? 0 : c.c.n_inserted};
+	if (!read_filter(files[0], c.c, &counters, kCounting)) return EXIT_FAILURE;
+	c.h = ntc_bloom_header{c.c.k, (uint32_t)n_hash, c.c.strand, blocked ? NTC_BBLOOM_BLOCK_BITS : 0u, m_bits, walk ? 0 : c.c.n_inserted};
 	c.min_count = (uint32_t)min_count;
+	c.blocked = blocked;
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
 		std::fprintf(stderr, "ntbloom: no HIP device\n");
@@ -548,10 +572,10 @@ int solid(int argc, char** argv)
 	std::vector<unsigned char> image(image_bytes(c.h, false));
 	const hipError_t rc = hipMemcpy(image.data(), b.d_filter, image.size(), hipMemcpyDeviceToHost);
 	if (rc != hipSuccess) return fail_hip("cannot fetch the filter", rc);
-	if (ntc_bloom_write(out, &c.h, image.data()) != 0) return fail_lib();
+	if ((blocked ? ntc_bbloom_write : ntc_bloom_write)(out, &c.h, image.data()) != 0) return fail_lib();
 	if (walk)
-		std::fprintf(stderr, "ntbloom: %llu k-mers counted at least %u times into %llu bits, %u hashes each\n", (unsigned long long)c.h.n_inserted, c.min_count,
-		             (unsigned long long)m_bits, (uint32_t)n_hash);
+		std::fprintf(stderr, "ntbloom: %llu k-mers counted at least %u times into %llu %s, %u hashes each\n", (unsigned long long)c.h.n_inserted, c.min_count,
+		             (unsigned long long)m_bits, blocked ? "bits in blocks of 512" : "bits", (uint32_t)n_hash);
 	else
 		std::fprintf(stderr, "ntbloom: the counters of at least %u into %llu bits\n", c.min_count, (unsigned long long)m_bits);
 	return EXIT_SUCCESS;
@@ -572,11 +596,13 @@ int query(int argc, char** argv)
 	if (argc < 2) return usage("query needs F.bf and at least one input file");
 	for (int i = 0; i < argc; ++i)
 		if (argv[i][0] == '-' && argv[i][1] != '\0') return usage("unknown option", argv[i]);
-	c.counting = is_counting_file(argv[0]);
+	const Kind kind = file_kind(argv[0]);
+	c.counting = kind == kCounting;
+	c.blocked = kind == kBlocked;
 	std::vector<unsigned char> image;
-	if (!read_filter(argv[0], c.h, nullptr, c.counting)) return EXIT_FAILURE;
+	if (!read_filter(argv[0], c.h, nullptr, kind)) return EXIT_FAILURE;
 	if (have_c && !c.counting) return usage("--min-count goes with a counting filter (.cbf), not with", argv[0]);
-	if (!read_filter(argv[0], c.h, &image, c.counting)) return EXIT_FAILURE;
+	if (!read_filter(argv[0], c.h, &image, kind)) return EXIT_FAILURE;
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
 		std::fprintf(stderr, "ntbloom: no HIP device\n");
@@ -599,10 +625,12 @@ int info(int argc, char** argv)
 	int n_dev = 0;
 	const bool gpu = hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0;
 	std::vector<unsigned char> image;
-	const bool counting = is_counting_file(argv[0]);
-	if (!read_filter(argv[0], h, gpu ? &image : nullptr, counting)) return EXIT_FAILURE;
+	const Kind kind = file_kind(argv[0]);
+	const bool counting = kind == kCounting;
+	if (!read_filter(argv[0], h, gpu ? &image : nullptr, kind)) return EXIT_FAILURE;
 	std::printf("file\t%s\nk\t%u\nhashes\t%u\nstrand\t%s\n%s\t%llu\ninserted\t%llu\n", argv[0], h.k, h.n_hash, kStrand[h.strand], counting ? "counters" : "bits",
 	            (unsigned long long)h.m_bits, (unsigned long long)h.n_inserted);
+	if (kind == kBlocked) std::printf("block\t%u\nblocks\t%llu\n", h.reserved, (unsigned long long)(h.m_bits / h.reserved));
 	if (!gpu) return EXIT_SUCCESS;
 	Buffers b;
 	if (!upload_filter(b, h, &image, counting)) return EXIT_FAILURE;
@@ -617,7 +645,16 @@ int info(int argc, char** argv)
 	uint64_t pop = 0;
 	if (ntc_bloom_popcount_device(0, nullptr, b.d_filter, h.m_bits, &pop) != 0) return fail_lib();
 	const double occ = (double)pop / (double)h.m_bits;
-	std::printf("popcount\t%llu\noccupancy\t%.6f\nfpr\t%.6g\n", (unsigned long long)pop, occ, std::pow(occ, (double)h.n_hash));
+	double fpr = std::pow(occ, (double)h.n_hash);
+	if (kind == kBlocked) { // per block: a block fuller than the average answers wrongly more often than the average says
+		uint64_t hist[NTC_BBLOOM_BLOCK_BITS + 1];
+		if (ntc_bbloom_hist_device(0, nullptr, b.d_filter, h.m_bits, hist) != 0) return fail_lib();
+		fpr = 0.0;
+		for (uint32_t v = 0; v <= NTC_BBLOOM_BLOCK_BITS; ++v)
+			fpr += (double)hist[v] * std::pow((double)v / (double)NTC_BBLOOM_BLOCK_BITS, (double)h.n_hash);
+		fpr /= (double)(h.m_bits / NTC_BBLOOM_BLOCK_BITS);
+	}
+	std::printf("popcount\t%llu\noccupancy\t%.6f\nfpr\t%.6g\n", (unsigned long long)pop, occ, fpr);
 	return EXIT_SUCCESS;
 }
 

@@ -3,8 +3,9 @@
 // k-mer's n_hash positions are the plain filter's (ntc_bloom_walk.hpp: h_i % m); an insert adds one to each, saturating at 255, so that after any inserts
 // in any order counter[loc] = min(255, increments aimed at loc) — no conservative update, whose result would depend on the order of concurrent inserts.
 // The count of a k-mer is the minimum of its counters.  The walk over the input is ntc_bloom_walk.hpp's, the one the plain filters use: here are the
-// actions (increment, count >= c, count, "count >= c -> set in a plain filter") and the streaming kernels over the counters (threshold, add, hist).
-#include "ntc_bloom_walk.hpp"
+// actions (increment, count >= c, count, "count >= c -> set in a plain filter", "count >= c -> set in a blocked filter") and the streaming kernels over
+// the counters (threshold, add, hist).
+#include "ntc_bbloom.hpp"
 
 using namespace ntc_eng;
 using namespace ntc_bloom;
@@ -80,6 +81,21 @@ struct SolidAct {
 			uint32_t* w = filter + (loc >> 5);
 			if ((*w & bit) == 0) (void)__hip_atomic_fetch_or(w, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (the plain load: as in ntc_bloom.hip)
 		}
+		return 1u;
+	}
+};
+// the same second stage with a BLOCKED destination (ntc_bbloom.hpp): one line of the destination per window that passed
+struct BlockedSolidAct {
+	static constexpr int kMode = kWalkTotal;
+	const unsigned char* counters;
+	BloomHashes chs;
+	uint32_t min_count;
+	uint32_t* filter;
+	BlockedHashes hs;
+	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const
+	{
+		if (cbloom_count(counters, chs, h0, min_count) < min_count) return 0u;
+		bbloom_set(filter, hs, h0);
 		return 1u;
 	}
 };
@@ -290,6 +306,17 @@ int ntc_bloom_insert_solid_device(int32_t device, void* stream, void* d_filter, 
 	if (int rc = check_input("ntc_bloom_insert_solid_device", strand, d_bases, offsets, n_seqs)) return rc;
 	const SolidAct act{static_cast<const unsigned char*>(d_counters), bloom_hashes(m, c_n_hash, k), min_count, static_cast<uint32_t*>(d_filter), bloom_hashes(m_bits, n_hash, k)};
 	return walk_total("ntc_bloom_insert_solid_device", device, stream, act, k, strand, d_bases, offsets, n_seqs, n_windows);
+}
+
+int ntc_bbloom_insert_solid_device(int32_t device, void* stream, void* d_filter, uint64_t m_bits, uint32_t n_hash, const void* d_counters, uint64_t m, uint32_t c_n_hash,
+                                   uint32_t min_count, uint32_t k, uint32_t strand, const void* d_bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t* n_windows)
+{
+	if (int rc = check_blocked("ntc_bbloom_insert_solid_device", d_filter, m_bits, n_hash, k)) return rc;
+	if (int rc = check_counters("ntc_bbloom_insert_solid_device", d_counters, m, c_n_hash, k)) return rc;
+	if (int rc = check_min_count("ntc_bbloom_insert_solid_device", min_count)) return rc;
+	if (int rc = check_input("ntc_bbloom_insert_solid_device", strand, d_bases, offsets, n_seqs)) return rc;
+	const BlockedSolidAct act{static_cast<const unsigned char*>(d_counters), bloom_hashes(m, c_n_hash, k), min_count, static_cast<uint32_t*>(d_filter), bbloom_hashes(m_bits, n_hash, k)};
+	return walk_total("ntc_bbloom_insert_solid_device", device, stream, act, k, strand, d_bases, offsets, n_seqs, n_windows);
 }
 
 int ntc_cbloom_add_device(int32_t device, void* stream, void* d_dst, const void* d_src, uint64_t m)
