@@ -98,67 +98,124 @@ bool parse_double(const char* s, double& out)
 	return true;
 }
 
-// the F0 line of a `.hist` file as ntc_write_hist writes it: "F0\t<integer>"
-bool hist_f0(const char* path, uint64_t& f0)
-{
-	FILE* f = std::fopen(path, "rb");
-	if (!f) return false;
-	char line[256];
-	bool found = false;
-	while (!found && std::fgets(line, sizeof line, f)) {
-		if (std::strncmp(line, "F0\t", 3) != 0) continue;
-		std::string v(line + 3);
-		while (!v.empty() && (v.back() == '\n' || v.back() == '\r'))
-			v.pop_back();
-		found = parse_u64(v.c_str(), f0);
-		break;
-	}
-	std::fclose(f);
-	return found;
-}
-
-// F0 - sum_{i < c} f_i of a `.hist` file: its F0 line and its "i\tf_i" lines, i = 1, 2, ... as ntc_write_hist writes them.  -1: no F0 line; -2: the f_i
-// lines stop below c - 1; -3: the lines sum to more than F0; 0: n is set
-int hist_solid_n(const char* path, uint64_t c, uint64_t& n)
-{
+// A `.hist` file as ntc_write_hist writes it, read in one pass: the value of its first "F0\t<integer>" line, and its "i\tf_i" lines, i = 1, 2, ... as far
+// as they follow each other (whatever is no "i\tf_i" line of the next i is passed over: the F1 and F0 lines, say; an f_i that is no number ends the list)
+struct Hist {
+	bool have_f0 = false;
 	uint64_t f0 = 0;
-	if (!hist_f0(path, f0)) return -1;
+	std::vector<uint64_t> f; // f[i - 1] = f_i
+};
+Hist read_hist(const char* path)
+{
+	Hist h;
 	FILE* f = std::fopen(path, "rb");
-	if (!f) return -1;
+	if (!f) return h;
 	char line[256];
-	uint64_t next = 1, below = 0;
-	while (next < c && std::fgets(line, sizeof line, f)) {
+	bool f0_line = false, list_ended = false;
+	while (std::fgets(line, sizeof line, f)) {
 		char* tab = std::strchr(line, '\t');
 		if (!tab) continue;
-		*tab = '\0';
-		uint64_t i = 0, fi = 0;
-		if (!parse_u64(line, i) || i != next) continue; // (the F1 and F0 lines, and whatever is no "i\tf_i" line of the next i)
 		std::string v(tab + 1);
 		while (!v.empty() && (v.back() == '\n' || v.back() == '\r'))
 			v.pop_back();
-		if (!parse_u64(v.c_str(), fi)) break;
-		below += fi;
-		++next;
+		*tab = '\0';
+		uint64_t i = 0, fi = 0;
+		if (std::strcmp(line, "F0") == 0) {
+			if (!f0_line) h.have_f0 = parse_u64(v.c_str(), h.f0);
+			f0_line = true;
+		} else if (!list_ended && parse_u64(line, i) && i == h.f.size() + 1) {
+			if (parse_u64(v.c_str(), fi))
+				h.f.push_back(fi);
+			else
+				list_ended = true;
+		}
 	}
 	std::fclose(f);
-	if (next < c) return -2;
-	if (below > f0) return -3;
-	n = f0 - below;
-	return 0;
+	return h;
 }
 
-// the kind of a filter file by its magic: a counting filter, a blocked filter, or plain — which is also anything else (ntc_bloom_read then says what is
-// wrong with it)
-enum Kind { kPlain = 0, kCounting = 1, kBlocked = 2 };
-Kind file_kind(const char* path)
+// A KIND of filter — plain, counting, blocked — is one row of this table: its file, its size, what its m counts and its entry points.  A command picks
+// the row once, from `count` / --blocked or from a file's magic, and carries it; nothing below asks which kind it has.
+struct Kind {
+	const char* magic; // of its file; nullptr: the plain kind, which is also any file of no known magic (ntc_bloom_read then says what is wrong with it)
+	int (*read)(const char*, ntc_bloom_header*, void*, uint64_t);
+	int (*write)(const char*, const ntc_bloom_header*, const void*);
+	int (*size)(uint64_t, uint32_t, double, uint64_t*);
+	size_t (*image_bytes)(uint64_t m); // the bytes of its image
+	uint32_t reserved;                 // of its header: the block size of a kind in blocks, else 0
+	const char* what;                  // what m counts, in the reports ...
+	const char* info_m;                // ... in `info` ...
+	const char* need_out;              // ... and in the refusals of build and count
+	const char* need_size;
+	int (*insert)(int32_t, void*, void*, uint64_t, uint32_t, uint32_t, uint32_t, const void*, const uint64_t*, uint64_t, uint64_t*);
+	// solid: the windows counted at least min_count times in a counting filter go into a filter of this kind (nullptr: no such destination)
+	int (*insert_solid)(int32_t, void*, void*, uint64_t, uint32_t, const void*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, const void*, const uint64_t*, uint64_t, uint64_t*);
+	// the kind's query call; min_count is the counting kind's
+	int (*query)(const ntc_bloom_header& h, const void* d_filter, const void* d_bases, const uint64_t* offsets, uint64_t n_seqs, uint32_t min_count, void* d_w, void* d_h);
+	// info, with a device: the lines behind the header
+	int (*report)(const ntc_bloom_header& h, const void* d_filter);
+};
+
+int report_bits(const ntc_bloom_header& h, const void* d_filter, const double* fpr_given)
 {
-	FILE* f = std::fopen(path, "rb");
-	if (!f) return kPlain;
+	uint64_t pop = 0;
+	if (ntc_bloom_popcount_device(0, nullptr, d_filter, h.m_bits, &pop) != 0) return fail_lib();
+	const double occ = (double)pop / (double)h.m_bits;
+	std::printf("popcount\t%llu\noccupancy\t%.6f\nfpr\t%.6g\n", (unsigned long long)pop, occ, fpr_given ? *fpr_given : std::pow(occ, (double)h.n_hash));
+	return EXIT_SUCCESS;
+}
+int report_plain(const ntc_bloom_header& h, const void* d_filter) { return report_bits(h, d_filter, nullptr); }
+int report_blocked(const ntc_bloom_header& h, const void* d_filter)
+{
+	uint64_t hist[NTC_BBLOOM_BLOCK_BITS + 1]; // per block: a block fuller than the average answers wrongly more often than the average says
+	if (ntc_bbloom_hist_device(0, nullptr, d_filter, h.m_bits, hist) != 0) return fail_lib();
+	double fpr = 0.0;
+	for (uint32_t v = 0; v <= NTC_BBLOOM_BLOCK_BITS; ++v)
+		fpr += (double)hist[v] * std::pow((double)v / (double)NTC_BBLOOM_BLOCK_BITS, (double)h.n_hash);
+	fpr /= (double)(h.m_bits / NTC_BBLOOM_BLOCK_BITS);
+	return report_bits(h, d_filter, &fpr);
+}
+int report_counting(const ntc_bloom_header& h, const void* d_filter)
+{
+	uint64_t hist[256];
+	if (ntc_cbloom_hist_device(0, nullptr, d_filter, h.m_bits, hist) != 0) return fail_lib();
+	const uint64_t used = h.m_bits - hist[0];
+	const double occ = (double)used / (double)h.m_bits;
+	std::printf("nonzero\t%llu\nsaturated\t%llu\noccupancy\t%.6f\nfpr\t%.6g\n", (unsigned long long)used, (unsigned long long)hist[255], occ, std::pow(occ, (double)h.n_hash));
+	return EXIT_SUCCESS;
+}
+
+size_t bytes_of_bits(uint64_t m) { return (m + 7) / 8; }
+size_t bytes_of_counters(uint64_t m) { return m; }
+
+const Kind kPlain = {nullptr, ntc_bloom_read, ntc_bloom_write, ntc_bloom_size, bytes_of_bits, 0, "bits", "bits", "-o OUT.bf", "exactly one of -m BITS, --distinct N and --hist FILE",
+                     ntc_bloom_insert_device, ntc_bloom_insert_solid_device,
+                     [](const ntc_bloom_header& h, const void* f, const void* bases, const uint64_t* off, uint64_t n, uint32_t, void* w, void* hits) {
+	                     return ntc_bloom_query_device(0, nullptr, f, h.m_bits, h.n_hash, h.k, h.strand, bases, off, n, w, hits);
+                     },
+                     report_plain};
+const Kind kCounting = {"NTCCB1\0\0", ntc_cbloom_read, ntc_cbloom_write, ntc_bloom_size, bytes_of_counters, 0, "counters", "counters", "-o OUT.cbf",
+                        "exactly one of -m COUNTERS, --distinct N and --hist FILE", ntc_cbloom_insert_device, nullptr,
+                        [](const ntc_bloom_header& h, const void* f, const void* bases, const uint64_t* off, uint64_t n, uint32_t min_count, void* w, void* hits) {
+	                        return ntc_cbloom_query_device(0, nullptr, f, h.m_bits, h.n_hash, h.k, h.strand, bases, off, n, min_count, w, hits);
+                        },
+                        report_counting};
+const Kind kBlocked = {"NTCBB1\0\0", ntc_bbloom_read, ntc_bbloom_write, ntc_bbloom_size, bytes_of_bits, NTC_BBLOOM_BLOCK_BITS, "bits in blocks of 512", "bits", "-o OUT.bf",
+                       "exactly one of -m BITS, --distinct N and --hist FILE", ntc_bbloom_insert_device, ntc_bbloom_insert_solid_device,
+                       [](const ntc_bloom_header& h, const void* f, const void* bases, const uint64_t* off, uint64_t n, uint32_t, void* w, void* hits) {
+	                       return ntc_bbloom_query_device(0, nullptr, f, h.m_bits, h.n_hash, h.k, h.strand, bases, off, n, w, hits);
+                       },
+                       report_blocked};
+
+// the kind of a filter file by its magic
+const Kind& file_kind(const char* path)
+{
 	char magic[8] = {0};
-	const bool whole = std::fread(magic, 1, 8, f) == 8;
-	std::fclose(f);
-	if (whole && std::memcmp(magic, "NTCCB1\0\0", 8) == 0) return kCounting;
-	if (whole && std::memcmp(magic, "NTCBB1\0\0", 8) == 0) return kBlocked;
+	FILE* f = std::fopen(path, "rb");
+	const bool whole = f && std::fread(magic, 1, 8, f) == 8;
+	if (f) std::fclose(f);
+	for (const Kind* kind : {&kCounting, &kBlocked})
+		if (whole && std::memcmp(magic, kind->magic, 8) == 0) return *kind;
 	return kPlain;
 }
 
@@ -283,11 +340,10 @@ bool alloc_batch(Buffers& b)
 }
 
 struct BuildCtx {
+	const Kind* kind;       // of the filter in d_filter
 	ntc_bloom_header h;
-	bool counting = false;       // count: d_filter holds counters
-	bool blocked = false;        // build --blocked, solid --blocked: d_filter is a blocked filter
-	ntc_bloom_header c{};        // solid: the counting filter in d_counters ...
-	uint32_t min_count = 0;      // ... and the count a k-mer needs (0: not solid)
+	ntc_bloom_header c{};   // solid: the counting filter in d_counters ...
+	uint32_t min_count = 0; // ... and the count a k-mer needs (0: not solid)
 };
 int build_flush(Reader& r, void* ctx)
 {
@@ -295,25 +351,18 @@ int build_flush(Reader& r, void* ctx)
 	const hipError_t rc = hipMemcpy(r.b.d_bases, r.b.h_bases, r.fill, hipMemcpyHostToDevice);
 	if (rc != hipSuccess) return fail_hip("cannot upload a batch", rc);
 	uint64_t n = 0;
-	int rc2;
-	if (c.min_count)
-		rc2 = (c.blocked ? ntc_bbloom_insert_solid_device : ntc_bloom_insert_solid_device)(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, r.b.d_counters, c.c.m_bits, c.c.n_hash,
-		                                                                                   c.min_count, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), r.offsets.size() - 1, &n);
-	else if (c.blocked)
-		rc2 = ntc_bbloom_insert_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), r.offsets.size() - 1, &n);
-	else if (c.counting)
-		rc2 = ntc_cbloom_insert_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), r.offsets.size() - 1, &n);
-	else
-		rc2 = ntc_bloom_insert_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), r.offsets.size() - 1, &n);
+	const uint64_t n_seqs = r.offsets.size() - 1;
+	const int rc2 = c.min_count ? c.kind->insert_solid(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, r.b.d_counters, c.c.m_bits, c.c.n_hash, c.min_count, c.h.k, c.h.strand,
+	                                                   r.b.d_bases, r.offsets.data(), n_seqs, &n)
+	                            : c.kind->insert(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, &n);
 	if (rc2 != 0) return fail_lib();
 	c.h.n_inserted += n;
 	return EXIT_SUCCESS;
 }
 
 struct QueryCtx {
+	const Kind* kind;
 	ntc_bloom_header h;
-	bool counting = false;
-	bool blocked = false;
 	uint32_t min_count = 1;
 	std::vector<uint32_t> counts;
 };
@@ -332,10 +381,7 @@ int query_flush(Reader& r, void* ctx)
 	if (rc != hipSuccess) return fail_hip("cannot upload a batch", rc);
 	uint32_t* d_w = r.b.d_counts;
 	uint32_t* d_h = r.b.d_counts + r.b.seq_cap;
-	const int rc2 = c.counting ? ntc_cbloom_query_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, c.min_count, d_w, d_h)
-	                : c.blocked ? ntc_bbloom_query_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, d_w, d_h)
-	                            : ntc_bloom_query_device(0, nullptr, r.b.d_filter, c.h.m_bits, c.h.n_hash, c.h.k, c.h.strand, r.b.d_bases, r.offsets.data(), n_seqs, d_w, d_h);
-	if (rc2 != 0) return fail_lib();
+	if (c.kind->query(c.h, r.b.d_filter, r.b.d_bases, r.offsets.data(), n_seqs, c.min_count, d_w, d_h) != 0) return fail_lib();
 	c.counts.resize(2 * n_seqs);
 	rc = hipMemcpy(c.counts.data(), d_w, n_seqs * 4, hipMemcpyDeviceToHost);
 	if (rc == hipSuccess) rc = hipMemcpy(c.counts.data() + n_seqs, d_h, n_seqs * 4, hipMemcpyDeviceToHost);
@@ -347,13 +393,10 @@ int query_flush(Reader& r, void* ctx)
 	return EXIT_SUCCESS;
 }
 
-// the bytes of a filter's image: a plain filter's bits, a counting filter's counters
-size_t image_bytes(const ntc_bloom_header& h, bool counting) { return counting ? h.m_bits : (h.m_bits + 7) / 8; }
-
-bool upload_filter(Buffers& b, const ntc_bloom_header& h, const std::vector<unsigned char>* image, bool counting = false, unsigned char** where = nullptr)
+// a filter of the kind on the device at `d`: zeros, or the image
+bool upload_filter(unsigned char*& d, const Kind& kind, const ntc_bloom_header& h, const std::vector<unsigned char>* image)
 {
-	unsigned char*& d = where ? *where : b.d_filter;
-	const size_t padded = (image_bytes(h, counting) + 3) & ~(size_t)3;
+	const size_t padded = (kind.image_bytes(h.m_bits) + 3) & ~(size_t)3;
 	hipError_t rc = hipMalloc((void**)&d, padded);
 	if (rc == hipSuccess) rc = hipMemset(d, 0, padded);
 	if (rc == hipSuccess && image) rc = hipMemcpy(d, image->data(), image->size(), hipMemcpyHostToDevice);
@@ -362,220 +405,207 @@ bool upload_filter(Buffers& b, const ntc_bloom_header& h, const std::vector<unsi
 	return false;
 }
 
-bool read_filter(const char* path, ntc_bloom_header& h, std::vector<unsigned char>* image, Kind kind = kPlain)
+// a file of the kind: its header, and its image where one is asked for
+bool read_filter(const char* path, const Kind& kind, ntc_bloom_header& h, std::vector<unsigned char>* image)
 {
-	const bool counting = kind == kCounting;
-	const auto read = counting ? ntc_cbloom_read : kind == kBlocked ? ntc_bbloom_read : ntc_bloom_read;
-	if (read(path, &h, nullptr, 0) != 0) {
+	if (kind.read(path, &h, nullptr, 0) != 0) {
 		(void)fail_lib();
 		return false;
 	}
 	if (!image) return true;
-	image->resize(image_bytes(h, counting));
-	if (read(path, &h, image->data(), image->size()) != 0) {
+	image->resize(kind.image_bytes(h.m_bits));
+	if (kind.read(path, &h, image->data(), image->size()) != 0) {
 		(void)fail_lib();
 		return false;
 	}
 	return true;
 }
 
-// build (a plain filter, OUT.bf) and count (a counting filter, OUT.cbf): the same arguments, -m in bits or in counters
+// the end of build, count and solid: the image comes back and goes to OUT, whole or not at all
+int write_filter(const Buffers& b, const Kind& kind, const ntc_bloom_header& h, const char* out)
+{
+	std::vector<unsigned char> image(kind.image_bytes(h.m_bits));
+	const hipError_t rc = hipMemcpy(image.data(), b.d_filter, image.size(), hipMemcpyDeviceToHost);
+	if (rc != hipSuccess) return fail_hip("cannot fetch the filter", rc);
+	return kind.write(out, &h, image.data()) != 0 ? fail_lib() : EXIT_SUCCESS;
+}
+
+bool have_device()
+{
+	int n_dev = 0;
+	return hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0;
+}
+int need_device()
+{
+	if (have_device()) return EXIT_SUCCESS;
+	std::fprintf(stderr, "ntbloom: no HIP device\n");
+	return EXIT_FAILURE;
+}
+
+// The options build, count and solid share, scanned in the order given; a command states which of them it `takes`, every other one is unknown to it.
+// What is no option is a file.
+enum : unsigned { kOptK = 1, kOptH = 2, kOptM = 4, kOptDistinct = 8, kOptFpr = 16, kOptHist = 32, kOptOut = 64, kOptBlocked = 128, kOptStrand = 256, kOptMinCount = 512 };
+struct Options {
+	uint64_t k = 0, n_hash = 3, m_bits = 0, distinct = 0, min_count = 0;
+	double fpr = 0.0;
+	uint32_t strand = 0;
+	unsigned given = 0; // the options seen, as kOpt bits
+	const char* out = nullptr;
+	const char* hist = nullptr;
+	std::vector<const char*> files;
+	bool has(unsigned opt) const { return (given & opt) != 0; }
+};
+int scan_options(int argc, char** argv, unsigned takes, Options& o)
+{
+	const struct {
+		const char* flag;
+		unsigned opt;
+		uint64_t Options::*to;
+		uint64_t lo, hi;
+		const char* why;
+	} numbers[] = {{"-k", kOptK, &Options::k, 1, ntc_max_k(), "-k is not a number of 1 .. ntc_max_k()"},
+	               {"-H", kOptH, &Options::n_hash, 1, 32, "-H is not a number of 1 .. 32"},
+	               {"-m", kOptM, &Options::m_bits, 1, (1ull << 40) - 1, "-m is not a number of 1 .. 2^40 - 1"},
+	               {"--distinct", kOptDistinct, &Options::distinct, 1, UINT64_MAX, "--distinct is not a positive number"},
+	               {"--min-count", kOptMinCount, &Options::min_count, 1, 255, "--min-count is not a number of 1 .. 255"}};
+	const struct {
+		const char* flag;
+		unsigned opt;
+		const char* Options::*to;
+	} names[] = {{"--hist", kOptHist, &Options::hist}, {"-o", kOptOut, &Options::out}};
+	for (int i = 0; i < argc; ++i) {
+		const std::string a = argv[i];
+		unsigned opt = 0; // the option `a` is, if the command takes it
+		const char* v = nullptr;
+		auto value = [&](const char* flag, unsigned is) {
+			if (a != flag || !(takes & is)) return false;
+			opt = is;
+			if (i + 1 >= argc)
+				(void)usage("missing value behind", flag);
+			else
+				v = argv[++i];
+			return true;
+		};
+		for (const auto& n : numbers)
+			if (value(n.flag, n.opt)) {
+				if (!v) return EXIT_FAILURE;
+				if (!parse_u64(v, o.*n.to) || o.*n.to < n.lo || o.*n.to > n.hi) return usage(n.why, v);
+			}
+		for (const auto& n : names)
+			if (value(n.flag, n.opt)) {
+				if (!v) return EXIT_FAILURE;
+				o.*n.to = v;
+			}
+		if (value("--fpr", kOptFpr)) {
+			if (!v) return EXIT_FAILURE;
+			if (!parse_double(v, o.fpr) || !(o.fpr > 0.0 && o.fpr < 1.0)) return usage("--fpr is not a number inside (0, 1)", v);
+		} else if (a == "--blocked" && (takes & kOptBlocked)) {
+			opt = kOptBlocked;
+		} else if (a.compare(0, 9, "--strand=") == 0 && (takes & kOptStrand)) {
+			opt = kOptStrand;
+			const std::string s = a.substr(9);
+			if (s == "canonical") o.strand = 0;
+			else if (s == "forward") o.strand = 1;
+			else if (s == "reverse") o.strand = 2;
+			else return usage("--strand is none of canonical, forward, reverse", s.c_str());
+		}
+		if (opt)
+			o.given |= opt;
+		else if (a.size() > 1 && a[0] == '-')
+			return usage("unknown option", a.c_str());
+		else
+			o.files.push_back(argv[i]);
+	}
+	return EXIT_SUCCESS;
+}
+
+// build (a plain or a blocked filter, OUT.bf) and count (a counting filter, OUT.cbf): the same arguments, -m in bits or in counters
 int build(int argc, char** argv, bool counting)
 {
 	const char* const cmd = counting ? "count" : "build";
 	auto needs = [&](const char* what) { return usage((std::string(cmd) + " needs " + what).c_str()); };
-	uint64_t k = 0, n_hash = 3, m_bits = 0, distinct = 0;
-	double fpr = 0.0;
-	bool have_k = false, have_m = false, have_distinct = false, have_fpr = false, blocked = false;
-	uint32_t strand = 0;
-	const char* out = nullptr;
-	const char* hist = nullptr;
-	std::vector<const char*> files;
-	for (int i = 0; i < argc; ++i) {
-		const std::string a = argv[i];
-		auto value = [&](const char* flag) -> const char* {
-			if (i + 1 >= argc) {
-				(void)usage("missing value behind", flag);
-				return nullptr;
-			}
-			return argv[++i];
-		};
-		if (a == "-k") {
-			const char* v = value("-k");
-			if (!v) return EXIT_FAILURE;
-			if (!parse_u64(v, k) || k < 1 || k > ntc_max_k()) return usage("-k is not a number of 1 .. ntc_max_k()", v);
-			have_k = true;
-		} else if (a == "-H") {
-			const char* v = value("-H");
-			if (!v) return EXIT_FAILURE;
-			if (!parse_u64(v, n_hash) || n_hash < 1 || n_hash > 32) return usage("-H is not a number of 1 .. 32", v);
-		} else if (a == "-m") {
-			const char* v = value("-m");
-			if (!v) return EXIT_FAILURE;
-			if (!parse_u64(v, m_bits) || m_bits < 1 || m_bits >= (1ull << 40)) return usage("-m is not a number of 1 .. 2^40 - 1", v);
-			have_m = true;
-		} else if (a == "--distinct") {
-			const char* v = value("--distinct");
-			if (!v) return EXIT_FAILURE;
-			if (!parse_u64(v, distinct) || distinct == 0) return usage("--distinct is not a positive number", v);
-			have_distinct = true;
-		} else if (a == "--fpr") {
-			const char* v = value("--fpr");
-			if (!v) return EXIT_FAILURE;
-			if (!parse_double(v, fpr) || !(fpr > 0.0 && fpr < 1.0)) return usage("--fpr is not a number inside (0, 1)", v);
-			have_fpr = true;
-		} else if (a == "--hist") {
-			hist = value("--hist");
-			if (!hist) return EXIT_FAILURE;
-		} else if (a == "-o") {
-			out = value("-o");
-			if (!out) return EXIT_FAILURE;
-		} else if (a == "--blocked") {
-			blocked = true;
-		} else if (a.compare(0, 9, "--strand=") == 0) {
-			const std::string s = a.substr(9);
-			if (s == "canonical") strand = 0;
-			else if (s == "forward") strand = 1;
-			else if (s == "reverse") strand = 2;
-			else return usage("--strand is none of canonical, forward, reverse", s.c_str());
-		} else if (a.size() > 1 && a[0] == '-') {
-			return usage("unknown option", a.c_str());
-		} else {
-			files.push_back(argv[i]);
-		}
+	Options o;
+	if (int rc = scan_options(argc, argv, kOptK | kOptH | kOptM | kOptDistinct | kOptFpr | kOptHist | kOptOut | kOptBlocked | kOptStrand, o)) return rc;
+	if (o.has(kOptBlocked) && counting) return usage("--blocked goes with build and solid: there is no blocked counting filter");
+	const Kind& kind = counting ? kCounting : o.has(kOptBlocked) ? kBlocked : kPlain;
+	if (!o.has(kOptK)) return needs("-k");
+	if (!o.out) return needs(kind.need_out);
+	const int ways = (o.has(kOptM) ? 1 : 0) + (o.has(kOptDistinct) ? 1 : 0) + (o.hist ? 1 : 0);
+	if (ways != 1) return needs(kind.need_size);
+	if (o.has(kOptM) && o.has(kOptFpr)) return usage("--fpr goes with --distinct or --hist, not with -m");
+	if (!o.has(kOptM) && !o.has(kOptFpr)) return usage("--distinct and --hist need --fpr P");
+	if (o.files.empty()) return needs("at least one input file");
+	if (o.hist) {
+		const Hist hist = read_hist(o.hist);
+		if (!hist.have_f0) return usage("no F0 line of a .hist file in", o.hist);
+		if (hist.f0 == 0) return usage("the F0 of the .hist file is 0", o.hist);
+		o.distinct = hist.f0;
 	}
-	if (blocked && counting) return usage("--blocked goes with build and solid: there is no blocked counting filter");
-	if (!have_k) return needs("-k");
-	if (!out) return needs(counting ? "-o OUT.cbf" : "-o OUT.bf");
-	const int ways = (have_m ? 1 : 0) + (have_distinct ? 1 : 0) + (hist ? 1 : 0);
-	if (ways != 1) return needs(counting ? "exactly one of -m COUNTERS, --distinct N and --hist FILE" : "exactly one of -m BITS, --distinct N and --hist FILE");
-	if (have_m && have_fpr) return usage("--fpr goes with --distinct or --hist, not with -m");
-	if (!have_m && !have_fpr) return usage("--distinct and --hist need --fpr P");
-	if (files.empty()) return needs("at least one input file");
-	if (hist && !hist_f0(hist, distinct)) return usage("no F0 line of a .hist file in", hist);
-	if (hist && distinct == 0) return usage("the F0 of the .hist file is 0", hist);
-	if (blocked && have_m && m_bits % NTC_BBLOOM_BLOCK_BITS != 0) return usage("-m of a blocked filter is not a multiple of 512", std::to_string(m_bits).c_str());
-	if (!have_m && (blocked ? ntc_bbloom_size : ntc_bloom_size)(distinct, (uint32_t)n_hash, fpr, &m_bits) != 0) return fail_lib();
+	if (kind.reserved && o.has(kOptM) && o.m_bits % kind.reserved != 0) return usage("-m of a blocked filter is not a multiple of 512", std::to_string(o.m_bits).c_str());
+	if (!o.has(kOptM) && kind.size(o.distinct, (uint32_t)o.n_hash, o.fpr, &o.m_bits) != 0) return fail_lib();
 
-	BuildCtx c;
-	c.h = ntc_bloom_header{(uint32_t)k, (uint32_t)n_hash, strand, blocked ? NTC_BBLOOM_BLOCK_BITS : 0u, m_bits, 0};
-	c.counting = counting;
-	c.blocked = blocked;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-		std::fprintf(stderr, "ntbloom: no HIP device\n");
-		return EXIT_FAILURE;
-	}
+	BuildCtx c{&kind, ntc_bloom_header{(uint32_t)o.k, (uint32_t)o.n_hash, o.strand, kind.reserved, o.m_bits, 0}};
+	if (int rc = need_device()) return rc;
 	Buffers b;
-	if (!upload_filter(b, c.h, nullptr, counting) || !alloc_batch(b)) return EXIT_FAILURE;
-	Reader r(b, (uint32_t)k, false, build_flush, &c);
-	for (const char* f : files)
+	if (!upload_filter(b.d_filter, kind, c.h, nullptr) || !alloc_batch(b)) return EXIT_FAILURE;
+	Reader r(b, (uint32_t)o.k, false, build_flush, &c);
+	for (const char* f : o.files)
 		if (int rc = r.read_file(f)) return rc;
 	if (int rc = r.flush()) return rc;
-	std::vector<unsigned char> image(image_bytes(c.h, counting));
-	const hipError_t rc = hipMemcpy(image.data(), b.d_filter, image.size(), hipMemcpyDeviceToHost);
-	if (rc != hipSuccess) return fail_hip("cannot fetch the filter", rc);
-	if ((counting ? ntc_cbloom_write : blocked ? ntc_bbloom_write : ntc_bloom_write)(out, &c.h, image.data()) != 0) return fail_lib();
-	std::fprintf(stderr, "ntbloom: %llu k-mers into %llu %s, %u hashes each\n", (unsigned long long)c.h.n_inserted, (unsigned long long)m_bits,
-	             counting ? "counters" : blocked ? "bits in blocks of 512" : "bits", (uint32_t)n_hash);
+	if (int rc = write_filter(b, kind, c.h, o.out)) return rc;
+	std::fprintf(stderr, "ntbloom: %llu k-mers into %llu %s, %u hashes each\n", (unsigned long long)c.h.n_inserted, (unsigned long long)o.m_bits, kind.what, (uint32_t)o.n_hash);
 	return EXIT_SUCCESS;
 }
 
 int solid(int argc, char** argv)
 {
-	uint64_t min_count = 0, n_hash = 3;
-	double fpr = 0.0;
-	bool have_c = false, have_fpr = false, have_h = false, blocked = false;
-	const char* out = nullptr;
-	const char* hist = nullptr;
-	std::vector<const char*> files; // IN.cbf, then the input files
-	for (int i = 0; i < argc; ++i) {
-		const std::string a = argv[i];
-		auto value = [&](const char* flag) -> const char* {
-			if (i + 1 >= argc) {
-				(void)usage("missing value behind", flag);
-				return nullptr;
-			}
-			return argv[++i];
-		};
-		if (a == "--min-count") {
-			const char* v = value("--min-count");
-			if (!v) return EXIT_FAILURE;
-			if (!parse_u64(v, min_count) || min_count < 1 || min_count > 255) return usage("--min-count is not a number of 1 .. 255", v);
-			have_c = true;
-		} else if (a == "-H") {
-			const char* v = value("-H");
-			if (!v) return EXIT_FAILURE;
-			if (!parse_u64(v, n_hash) || n_hash < 1 || n_hash > 32) return usage("-H is not a number of 1 .. 32", v);
-			have_h = true;
-		} else if (a == "--fpr") {
-			const char* v = value("--fpr");
-			if (!v) return EXIT_FAILURE;
-			if (!parse_double(v, fpr) || !(fpr > 0.0 && fpr < 1.0)) return usage("--fpr is not a number inside (0, 1)", v);
-			have_fpr = true;
-		} else if (a == "--hist") {
-			hist = value("--hist");
-			if (!hist) return EXIT_FAILURE;
-		} else if (a == "-o") {
-			out = value("-o");
-			if (!out) return EXIT_FAILURE;
-		} else if (a == "--blocked") {
-			blocked = true;
-		} else if (a.size() > 1 && a[0] == '-') {
-			return usage("unknown option", a.c_str());
-		} else {
-			files.push_back(argv[i]);
-		}
-	}
-	if (!have_c) return usage("solid needs --min-count C");
-	if (!out) return usage("solid needs -o OUT.bf");
-	if (files.empty()) return usage("solid needs IN.cbf");
-	const bool walk = files.size() > 1;
-	if (!walk && blocked) return usage("--blocked goes with input files: a threshold of IN.cbf has the counting filter's positions, which are not blocked");
-	if (!walk && (hist || have_fpr || have_h)) return usage("--hist, --fpr and -H go with input files: without them IN.cbf is thresholded");
-	if (walk && (!hist || !have_fpr)) return usage("solid with input files needs --hist FILE and --fpr P");
-	BuildCtx c;
+	Options o; // files: IN.cbf, then the input files
+	if (int rc = scan_options(argc, argv, kOptMinCount | kOptH | kOptFpr | kOptHist | kOptOut | kOptBlocked, o)) return rc;
+	if (!o.has(kOptMinCount)) return usage("solid needs --min-count C");
+	if (!o.out) return usage("solid needs -o OUT.bf");
+	if (o.files.empty()) return usage("solid needs IN.cbf");
+	const bool walk = o.files.size() > 1;
+	const Kind& kind = o.has(kOptBlocked) ? kBlocked : kPlain;
+	if (!walk && o.has(kOptBlocked)) return usage("--blocked goes with input files: a threshold of IN.cbf has the counting filter's positions, which are not blocked");
+	if (!walk && (o.hist || o.has(kOptFpr) || o.has(kOptH))) return usage("--hist, --fpr and -H go with input files: without them IN.cbf is thresholded");
+	if (walk && (!o.hist || !o.has(kOptFpr))) return usage("solid with input files needs --hist FILE and --fpr P");
+	BuildCtx c{&kind, ntc_bloom_header{}};
 	std::vector<unsigned char> counters;
-	if (!read_filter(files[0], c.c, nullptr, kCounting)) return EXIT_FAILURE; // (the header first: the refusals below need no counter)
+	if (!read_filter(o.files[0], kCounting, c.c, nullptr)) return EXIT_FAILURE; // (the header first: the refusals below need no counter)
 	uint64_t m_bits = c.c.m_bits;
-	if (walk) {
-		uint64_t n = 0;
-		const int rc = hist_solid_n(hist, min_count, n);
-		if (rc == -1) return usage("no F0 line of a .hist file in", hist);
-		if (rc == -2) return usage("the f_i lines of the .hist file stop below --min-count - 1", hist);
-		if (rc == -3) return usage("the f_i lines of the .hist file sum to more than its F0", hist);
-		if (n == 0) return usage("F0 minus the f_i below --min-count is 0 in", hist);
-		if ((blocked ? ntc_bbloom_size : ntc_bloom_size)(n, (uint32_t)n_hash, fpr, &m_bits) != 0) return fail_lib();
+	if (walk) { // n = F0 - sum_{i < C} f_i of the `.hist` file
+		const Hist hist = read_hist(o.hist);
+		if (!hist.have_f0) return usage("no F0 line of a .hist file in", o.hist);
+		if (hist.f.size() < o.min_count - 1) return usage("the f_i lines of the .hist file stop below --min-count - 1", o.hist);
+		uint64_t n = hist.f0;
+		for (uint64_t i = 1; i < o.min_count; ++i) {
+			if (hist.f[i - 1] > n) return usage("the f_i lines of the .hist file sum to more than its F0", o.hist);
+			n -= hist.f[i - 1];
+		}
+		if (n == 0) return usage("F0 minus the f_i below --min-count is 0 in", o.hist);
+		if (kind.size(n, (uint32_t)o.n_hash, o.fpr, &m_bits) != 0) return fail_lib();
 	} else {
-		n_hash = c.c.n_hash;
+		o.n_hash = c.c.n_hash;
 	}
-	if (!read_filter(files[0], c.c, &counters, kCounting)) return EXIT_FAILURE;
-	c.h = ntc_bloom_header{c.c.k, (uint32_t)n_hash, c.c.strand, blocked ? NTC_BBLOOM_BLOCK_BITS : 0u, m_bits, walk ? 0 : c.c.n_inserted};
-	c.min_count = (uint32_t)min_count;
-	c.blocked = blocked;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-		std::fprintf(stderr, "ntbloom: no HIP device\n");
-		return EXIT_FAILURE;
-	}
+	if (!read_filter(o.files[0], kCounting, c.c, &counters)) return EXIT_FAILURE;
+	c.h = ntc_bloom_header{c.c.k, (uint32_t)o.n_hash, c.c.strand, kind.reserved, m_bits, walk ? 0 : c.c.n_inserted};
+	c.min_count = (uint32_t)o.min_count;
+	if (int rc = need_device()) return rc;
 	Buffers b;
-	if (!upload_filter(b, c.c, &counters, true, &b.d_counters) || !upload_filter(b, c.h, nullptr)) return EXIT_FAILURE;
+	if (!upload_filter(b.d_counters, kCounting, c.c, &counters) || !upload_filter(b.d_filter, kind, c.h, nullptr)) return EXIT_FAILURE;
 	if (walk) {
 		if (!alloc_batch(b)) return EXIT_FAILURE;
 		Reader r(b, c.h.k, false, build_flush, &c);
-		for (size_t i = 1; i < files.size(); ++i)
-			if (int rc = r.read_file(files[i])) return rc;
+		for (size_t i = 1; i < o.files.size(); ++i)
+			if (int rc = r.read_file(o.files[i])) return rc;
 		if (int rc = r.flush()) return rc;
 	} else if (ntc_cbloom_threshold_device(0, nullptr, b.d_counters, c.c.m_bits, c.min_count, b.d_filter) != 0) {
 		return fail_lib();
 	}
-	std::vector<unsigned char> image(image_bytes(c.h, false));
-	const hipError_t rc = hipMemcpy(image.data(), b.d_filter, image.size(), hipMemcpyDeviceToHost);
-	if (rc != hipSuccess) return fail_hip("cannot fetch the filter", rc);
-	if ((blocked ? ntc_bbloom_write : ntc_bloom_write)(out, &c.h, image.data()) != 0) return fail_lib();
+	if (int rc = write_filter(b, kind, c.h, o.out)) return rc;
 	if (walk)
 		std::fprintf(stderr, "ntbloom: %llu k-mers counted at least %u times into %llu %s, %u hashes each\n", (unsigned long long)c.h.n_inserted, c.min_count,
-		             (unsigned long long)m_bits, blocked ? "bits in blocks of 512" : "bits", (uint32_t)n_hash);
+		             (unsigned long long)m_bits, kind.what, (uint32_t)o.n_hash);
 	else
 		std::fprintf(stderr, "ntbloom: the counters of at least %u into %llu bits\n", c.min_count, (unsigned long long)m_bits);
 	return EXIT_SUCCESS;
@@ -583,33 +613,25 @@ int solid(int argc, char** argv)
 
 int query(int argc, char** argv)
 {
-	QueryCtx c;
+	uint64_t min_count = 1;
 	bool have_c = false;
 	if (argc >= 1 && std::strcmp(argv[0], "--min-count") == 0) {
 		if (argc < 2) return usage("missing value behind", "--min-count");
-		uint64_t v = 0;
-		if (!parse_u64(argv[1], v) || v < 1 || v > 255) return usage("--min-count is not a number of 1 .. 255", argv[1]);
-		c.min_count = (uint32_t)v;
+		if (!parse_u64(argv[1], min_count) || min_count < 1 || min_count > 255) return usage("--min-count is not a number of 1 .. 255", argv[1]);
 		have_c = true;
 		argc -= 2, argv += 2;
 	}
 	if (argc < 2) return usage("query needs F.bf and at least one input file");
 	for (int i = 0; i < argc; ++i)
 		if (argv[i][0] == '-' && argv[i][1] != '\0') return usage("unknown option", argv[i]);
-	const Kind kind = file_kind(argv[0]);
-	c.counting = kind == kCounting;
-	c.blocked = kind == kBlocked;
+	QueryCtx c{&file_kind(argv[0]), ntc_bloom_header{}, (uint32_t)min_count, {}};
 	std::vector<unsigned char> image;
-	if (!read_filter(argv[0], c.h, nullptr, kind)) return EXIT_FAILURE;
-	if (have_c && !c.counting) return usage("--min-count goes with a counting filter (.cbf), not with", argv[0]);
-	if (!read_filter(argv[0], c.h, &image, kind)) return EXIT_FAILURE;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-		std::fprintf(stderr, "ntbloom: no HIP device\n");
-		return EXIT_FAILURE;
-	}
+	if (!read_filter(argv[0], *c.kind, c.h, nullptr)) return EXIT_FAILURE;
+	if (have_c && c.kind != &kCounting) return usage("--min-count goes with a counting filter (.cbf), not with", argv[0]);
+	if (!read_filter(argv[0], *c.kind, c.h, &image)) return EXIT_FAILURE;
+	if (int rc = need_device()) return rc;
 	Buffers b;
-	if (!upload_filter(b, c.h, &image, c.counting) || !alloc_batch(b)) return EXIT_FAILURE;
+	if (!upload_filter(b.d_filter, *c.kind, c.h, &image) || !alloc_batch(b)) return EXIT_FAILURE;
 	Reader r(b, c.h.k, true, query_flush, &c);
 	std::printf("name\tlength\twindows\thits\tfraction\n");
 	for (int i = 1; i < argc; ++i)
@@ -622,40 +644,17 @@ int info(int argc, char** argv)
 	if (argc != 1) return usage("info takes one file");
 	if (argv[0][0] == '-' && argv[0][1] != '\0') return usage("unknown option", argv[0]);
 	ntc_bloom_header h;
-	int n_dev = 0;
-	const bool gpu = hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0;
+	const bool gpu = have_device();
 	std::vector<unsigned char> image;
-	const Kind kind = file_kind(argv[0]);
-	const bool counting = kind == kCounting;
-	if (!read_filter(argv[0], h, gpu ? &image : nullptr, kind)) return EXIT_FAILURE;
-	std::printf("file\t%s\nk\t%u\nhashes\t%u\nstrand\t%s\n%s\t%llu\ninserted\t%llu\n", argv[0], h.k, h.n_hash, kStrand[h.strand], counting ? "counters" : "bits",
-	            (unsigned long long)h.m_bits, (unsigned long long)h.n_inserted);
-	if (kind == kBlocked) std::printf("block\t%u\nblocks\t%llu\n", h.reserved, (unsigned long long)(h.m_bits / h.reserved));
+	const Kind& kind = file_kind(argv[0]);
+	if (!read_filter(argv[0], kind, h, gpu ? &image : nullptr)) return EXIT_FAILURE;
+	std::printf("file\t%s\nk\t%u\nhashes\t%u\nstrand\t%s\n%s\t%llu\ninserted\t%llu\n", argv[0], h.k, h.n_hash, kStrand[h.strand], kind.info_m, (unsigned long long)h.m_bits,
+	            (unsigned long long)h.n_inserted);
+	if (kind.reserved) std::printf("block\t%u\nblocks\t%llu\n", h.reserved, (unsigned long long)(h.m_bits / h.reserved));
 	if (!gpu) return EXIT_SUCCESS;
 	Buffers b;
-	if (!upload_filter(b, h, &image, counting)) return EXIT_FAILURE;
-	if (counting) {
-		uint64_t hist[256];
-		if (ntc_cbloom_hist_device(0, nullptr, b.d_filter, h.m_bits, hist) != 0) return fail_lib();
-		const uint64_t used = h.m_bits - hist[0];
-		const double occ = (double)used / (double)h.m_bits;
-		std::printf("nonzero\t%llu\nsaturated\t%llu\noccupancy\t%.6f\nfpr\t%.6g\n", (unsigned long long)used, (unsigned long long)hist[255], occ, std::pow(occ, (double)h.n_hash));
-		return EXIT_SUCCESS;
-	}
-	uint64_t pop = 0;
-	if (ntc_bloom_popcount_device(0, nullptr, b.d_filter, h.m_bits, &pop) != 0) return fail_lib();
-	const double occ = (double)pop / (double)h.m_bits;
-	double fpr = std::pow(occ, (double)h.n_hash);
-	if (kind == kBlocked) { // per block: a block fuller than the average answers wrongly more often than the average says
-		uint64_t hist[NTC_BBLOOM_BLOCK_BITS + 1];
-		if (ntc_bbloom_hist_device(0, nullptr, b.d_filter, h.m_bits, hist) != 0) return fail_lib();
-		fpr = 0.0;
-		for (uint32_t v = 0; v <= NTC_BBLOOM_BLOCK_BITS; ++v)
-			fpr += (double)hist[v] * std::pow((double)v / (double)NTC_BBLOOM_BLOCK_BITS, (double)h.n_hash);
-		fpr /= (double)(h.m_bits / NTC_BBLOOM_BLOCK_BITS);
-	}
-	std::printf("popcount\t%llu\noccupancy\t%.6f\nfpr\t%.6g\n", (unsigned long long)pop, occ, fpr);
-	return EXIT_SUCCESS;
+	if (!upload_filter(b.d_filter, kind, h, &image)) return EXIT_FAILURE;
+	return kind.report(h, b.d_filter);
 }
 
 } // namespace

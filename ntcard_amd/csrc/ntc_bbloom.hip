@@ -1,7 +1,7 @@
 // ntc_bbloom.hip — BLOCKED Bloom filters on the device (include/ntcard_hip.h: ntc_bbloom_*_device; DESIGN.md §4 "Blocked filters"): every bit of a k-mer
 // in one aligned 512-bit block, one random cache line per k-mer where the plain filter (ntc_bloom.hip) fetches n_hash.  The block arithmetic is
-// ntc_bbloom.hpp's; the walk over the input, the remainder and the input checks are ntc_bloom_walk.hpp's, unchanged: here are the two actions of a blocked
-// filter, the kernels over given h_0 values and the histogram of the blocks' set bits.  The image is an ordinary bit image in the plain filter's bit rule:
+// ntc_bbloom.hpp's, and so is the blocked filter's view (BlockedView); the walk over the input, the remainder, the checks, the insert and test actions
+// and the kernels over given h_0 values are ntc_bloom_walk.hpp's templates over a view: here are the entry points and the histogram of the blocks' set bits.  The image is an ordinary bit image in the plain filter's bit rule:
 // ntc_bloom_popcount_device and ntc_bloom_or_device serve it as they are.  (The solid insert with a blocked destination is in ntc_cbloom.hip, beside the
 // counters it reads.)
 #include "ntc_bbloom.hpp"
@@ -10,37 +10,6 @@ using namespace ntc_eng;
 using namespace ntc_bloom;
 
 namespace {
-
-// the walk's actions (ntc_bloom_walk.hpp)
-struct BlockedSetAct {
-	static constexpr int kMode = kWalkTotal;
-	uint32_t* filter;
-	BlockedHashes hs;
-	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const
-	{
-		bbloom_set(filter, hs, h0);
-		return 1u;
-	}
-};
-struct BlockedTestAct {
-	static constexpr int kMode = kWalkPerSeq;
-	const uint32_t* filter;
-	BlockedHashes hs;
-	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const { return bbloom_test(filter, hs, h0) ? 1u : 0u; }
-};
-
-__global__ __launch_bounds__(256) void bbloom_insert_hashes_kernel(uint32_t* filter, BlockedHashes hs, const uint64_t* __restrict__ h0, uint64_t n)
-{
-	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
-		bbloom_set(filter, hs, h0[i]);
-}
-
-__global__ __launch_bounds__(256) void bbloom_query_hashes_kernel(const uint32_t* __restrict__ filter, BlockedHashes hs, const uint64_t* __restrict__ h0, uint64_t n,
-                                                                  unsigned char* __restrict__ flags)
-{
-	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
-		flags[i] = bbloom_test(filter, hs, h0[i]) ? 1 : 0;
-}
 
 // out[v] += the blocks that hold v set bits, v = 0 .. 512.  A lane takes a block: its 16 dwords as four 16-byte loads where the filter is 16-byte aligned
 // (`wide`), else dword by dword.  One histogram per workgroup in LDS (a workgroup sees fewer than 2^31 blocks), one global add per used bin; the empty
@@ -77,13 +46,6 @@ __global__ __launch_bounds__(256) void bbloom_hist_kernel(const uint32_t* __rest
 		if (h[s]) atomicAdd(&out[s], (unsigned long long)h[s]);
 }
 
-int check_hashes(const char* who, const void* d_h0_u64, uint64_t n)
-{
-	if (n && !d_h0_u64) return fail(NTC_ERR_ARG, "%s: null hashes", who);
-	if ((uintptr_t)d_h0_u64 & 7u) return fail(NTC_ERR_ARG, "%s: the hashes are not 8-byte aligned", who);
-	return 0;
-}
-
 } // namespace
 
 extern "C" {
@@ -93,7 +55,7 @@ int ntc_bbloom_insert_device(int32_t device, void* stream, void* d_filter, uint6
 {
 	if (int rc = check_blocked("ntc_bbloom_insert_device", d_filter, m_bits, n_hash, k)) return rc;
 	if (int rc = check_input("ntc_bbloom_insert_device", strand, d_bases, offsets, n_seqs)) return rc;
-	const BlockedSetAct act{static_cast<uint32_t*>(d_filter), bbloom_hashes(m_bits, n_hash, k)};
+	const InsertAct<BlockedView> act{blocked_view(d_filter, m_bits, n_hash, k)};
 	return walk_total("ntc_bbloom_insert_device", device, stream, act, k, strand, d_bases, offsets, n_seqs, n_windows);
 }
 
@@ -102,7 +64,7 @@ int ntc_bbloom_query_device(int32_t device, void* stream, const void* d_filter, 
 {
 	if (int rc = check_blocked("ntc_bbloom_query_device", d_filter, m_bits, n_hash, k)) return rc;
 	if (int rc = check_input("ntc_bbloom_query_device", strand, d_bases, offsets, n_seqs)) return rc;
-	const BlockedTestAct act{static_cast<const uint32_t*>(d_filter), bbloom_hashes(m_bits, n_hash, k)};
+	const TestAct<BlockedView> act{blocked_view(d_filter, m_bits, n_hash, k)};
 	return walk_per_seq("ntc_bbloom_query_device", device, stream, act, k, strand, d_bases, offsets, n_seqs, d_windows_u32, d_hits_u32);
 }
 
@@ -111,13 +73,7 @@ int ntc_bbloom_insert_hashes_device(int32_t device, void* stream, void* d_filter
 	if (int rc = check_blocked("ntc_bbloom_insert_hashes_device", d_filter, m_bits, n_hash, k)) return rc;
 	if (int rc = check_hashes("ntc_bbloom_insert_hashes_device", d_h0_u64, n)) return rc;
 	if (n == 0) return 0;
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(bbloom_insert_hashes_kernel, dim3(stride_grid(n)), dim3(256), 0, st, static_cast<uint32_t*>(d_filter), bbloom_hashes(m_bits, n_hash, k),
-	                   static_cast<const uint64_t*>(d_h0_u64), n);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return launch_strided(device, stream, insert_hashes_kernel<BlockedView>, n, blocked_view(d_filter, m_bits, n_hash, k), static_cast<const uint64_t*>(d_h0_u64), n);
 }
 
 int ntc_bbloom_query_hashes_device(int32_t device, void* stream, const void* d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k, const void* d_h0_u64, uint64_t n,
@@ -127,13 +83,8 @@ int ntc_bbloom_query_hashes_device(int32_t device, void* stream, const void* d_f
 	if (int rc = check_hashes("ntc_bbloom_query_hashes_device", d_h0_u64, n)) return rc;
 	if (n && !d_flags_u8) return fail(NTC_ERR_ARG, "ntc_bbloom_query_hashes_device: null flags");
 	if (n == 0) return 0;
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(bbloom_query_hashes_kernel, dim3(stride_grid(n)), dim3(256), 0, st, static_cast<const uint32_t*>(d_filter), bbloom_hashes(m_bits, n_hash, k),
-	                   static_cast<const uint64_t*>(d_h0_u64), n, static_cast<unsigned char*>(d_flags_u8));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return launch_strided(device, stream, query_hashes_kernel<BlockedView>, n, blocked_view(d_filter, m_bits, n_hash, k), static_cast<const uint64_t*>(d_h0_u64), n,
+	                      static_cast<unsigned char*>(d_flags_u8));
 }
 
 int ntc_bbloom_hist_device(int32_t device, void* stream, const void* d_filter, uint64_t m_bits, uint64_t* hist_u64)

@@ -64,16 +64,25 @@ __device__ __forceinline__ bool bbloom_test(const uint32_t* filter, const Blocke
 	return true;
 }
 
-// the checks every blocked-filter call shares, before a device is looked for
+// the view of a blocked filter (internal linkage, as BitsView)
+namespace {
+struct BlockedView {
+	uint32_t* filter;
+	BlockedHashes hs;
+	__device__ __forceinline__ void insert(uint64_t h0) const { bbloom_set(filter, hs, h0); }
+	__device__ __forceinline__ bool test(uint64_t h0) const { return bbloom_test(filter, hs, h0); }
+	__device__ __forceinline__ unsigned char answer(uint64_t h0) const { return test(h0) ? 1 : 0; }
+};
+} // namespace
+inline BlockedView blocked_view(const void* d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k)
+{
+	return BlockedView{static_cast<uint32_t*>(const_cast<void*>(d_filter)), bbloom_hashes(m_bits, n_hash, k)};
+}
+
+// the checks every blocked-filter call shares, before a device is looked for: check_filter with the rule for m_bits of a filter in blocks
 inline int check_blocked(const char* who, const void* d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k)
 {
-	if (!d_filter) return fail(NTC_ERR_ARG, "%s: null filter", who);
-	if ((uintptr_t)d_filter & 3u) return fail(NTC_ERR_ARG, "%s: the filter is not 4-byte aligned", who);
-	if (m_bits < kBlockBits || m_bits >= (1ull << 40) || m_bits % kBlockBits != 0)
-		return fail(NTC_ERR_ARG, "%s: m_bits=%llu is no multiple of %u in %u..2^40-%u", who, (unsigned long long)m_bits, kBlockBits, kBlockBits, kBlockBits);
-	if (n_hash < 1 || n_hash > 32) return fail(NTC_ERR_ARG, "%s: n_hash=%u outside 1..32", who, n_hash);
-	if (k < 1 || k > kMaxK) return fail(NTC_ERR_ARG, "%s: k=%u outside 1..%u", who, k, kMaxK);
-	return 0;
+	return check_filter(who, d_filter, m_bits, n_hash, k, "m_bits", "filter", kBlockBits);
 }
 
 } // namespace ntc_bloom

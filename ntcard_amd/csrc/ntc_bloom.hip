@@ -2,66 +2,15 @@
 // reference's vendor/ntHash/lib/BloomFilter.hpp:56-66: position loc = h_i % m_bits, bit 7 - loc % 8 of byte loc / 8; h_0 the window's value, h_i the
 // multi-hash of nthash.hpp:381-390.  Engine-less tools: kernels and their entry points in one file.
 //
-// The walk over the input (stage as codes, mark sequence starts, 16 window starts per lane, roll), the remainder by m_bits and the argument checks are
-// ntc_bloom_walk.hpp's, shared with the counting filters (ntc_cbloom.hip): here are the two actions of a plain filter — set the n_hash bits of a window
-// (insert), test them (query) — and the kernels that need no walk.
+// The walk over the input (stage as codes, mark sequence starts, 16 window starts per lane, roll), the remainder by m_bits, the argument checks and the
+// plain filter's view (BitsView: set the n_hash bits of a value, test them) are ntc_bloom_walk.hpp's, shared with the counting and the blocked filters
+// (ntc_cbloom.hip, ntc_bbloom.hip): here are the entry points — the shared actions and kernels over that view — and the streaming kernels of a bit image.
 #include "ntc_bloom_walk.hpp"
 
 using namespace ntc_eng;
 using namespace ntc_bloom;
 
 namespace {
-
-__device__ __forceinline__ void bloom_set(uint32_t* filter, const BloomHashes& hs, uint64_t h0)
-{
-	for (uint32_t i = 0; i < hs.n_hash; ++i) {
-		const uint64_t loc = hs.loc(h0, i);
-		const uint32_t bit = bloom_bit(loc);
-		uint32_t* w = filter + (loc >> 5);
-		// A PLAIN load decides whether the atomic is needed.  No ordering is required: bits only go 0 -> 1 during a build, so a stale value can only
-		// show a bit clear that is already set — a redundant atomic, never a lost one.
-		if ((*w & bit) == 0) (void)__hip_atomic_fetch_or(w, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	}
-}
-__device__ __forceinline__ bool bloom_test(const uint32_t* filter, const BloomHashes& hs, uint64_t h0)
-{
-	for (uint32_t i = 0; i < hs.n_hash; ++i) {
-		const uint64_t loc = hs.loc(h0, i);
-		if ((filter[loc >> 5] & bloom_bit(loc)) == 0) return false; // leave at the first clear bit
-	}
-	return true;
-}
-
-// the walk's actions (ntc_bloom_walk.hpp)
-struct SetAct {
-	static constexpr int kMode = kWalkTotal;
-	uint32_t* filter;
-	BloomHashes hs;
-	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const
-	{
-		bloom_set(filter, hs, h0);
-		return 1u;
-	}
-};
-struct TestAct {
-	static constexpr int kMode = kWalkPerSeq;
-	const uint32_t* filter;
-	BloomHashes hs;
-	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const { return bloom_test(filter, hs, h0) ? 1u : 0u; }
-};
-
-__global__ __launch_bounds__(256) void bloom_insert_hashes_kernel(uint32_t* filter, BloomHashes hs, const uint64_t* __restrict__ h0, uint64_t n)
-{
-	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
-		bloom_set(filter, hs, h0[i]);
-}
-
-__global__ __launch_bounds__(256) void bloom_query_hashes_kernel(const uint32_t* __restrict__ filter, BloomHashes hs, const uint64_t* __restrict__ h0, uint64_t n,
-                                                                 unsigned char* __restrict__ flags)
-{
-	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
-		flags[i] = bloom_test(filter, hs, h0[i]) ? 1 : 0;
-}
 
 // out[0] += the set bits of the filter's first m_bits; out[1] += the set bits behind them (last_mask: the bits of the LAST dword that are below m_bits)
 __global__ __launch_bounds__(256) void bloom_popcount_kernel(const uint32_t* __restrict__ filter, uint64_t n_words, uint32_t last_mask, unsigned long long* out)
@@ -104,7 +53,7 @@ int ntc_bloom_insert_device(int32_t device, void* stream, void* d_filter, uint64
 {
 	if (int rc = check_filter("ntc_bloom_insert_device", d_filter, m_bits, n_hash, k)) return rc;
 	if (int rc = check_input("ntc_bloom_insert_device", strand, d_bases, offsets, n_seqs)) return rc;
-	const SetAct act{static_cast<uint32_t*>(d_filter), bloom_hashes(m_bits, n_hash, k)};
+	const InsertAct<BitsView> act{bits_view(d_filter, m_bits, n_hash, k)};
 	return walk_total("ntc_bloom_insert_device", device, stream, act, k, strand, d_bases, offsets, n_seqs, n_windows);
 }
 
@@ -113,39 +62,26 @@ int ntc_bloom_query_device(int32_t device, void* stream, const void* d_filter, u
 {
 	if (int rc = check_filter("ntc_bloom_query_device", d_filter, m_bits, n_hash, k)) return rc;
 	if (int rc = check_input("ntc_bloom_query_device", strand, d_bases, offsets, n_seqs)) return rc;
-	const TestAct act{static_cast<const uint32_t*>(d_filter), bloom_hashes(m_bits, n_hash, k)};
+	const TestAct<BitsView> act{bits_view(d_filter, m_bits, n_hash, k)};
 	return walk_per_seq("ntc_bloom_query_device", device, stream, act, k, strand, d_bases, offsets, n_seqs, d_windows_u32, d_hits_u32);
 }
 
 int ntc_bloom_insert_hashes_device(int32_t device, void* stream, void* d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k, const void* d_h0_u64, uint64_t n)
 {
 	if (int rc = check_filter("ntc_bloom_insert_hashes_device", d_filter, m_bits, n_hash, k)) return rc;
-	if (n && !d_h0_u64) return fail(NTC_ERR_ARG, "ntc_bloom_insert_hashes_device: null hashes");
-	if ((uintptr_t)d_h0_u64 & 7u) return fail(NTC_ERR_ARG, "ntc_bloom_insert_hashes_device: the hashes are not 8-byte aligned");
+	if (int rc = check_hashes("ntc_bloom_insert_hashes_device", d_h0_u64, n)) return rc;
 	if (n == 0) return 0;
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(bloom_insert_hashes_kernel, dim3(stride_grid(n)), dim3(256), 0, st, static_cast<uint32_t*>(d_filter), bloom_hashes(m_bits, n_hash, k),
-	                   static_cast<const uint64_t*>(d_h0_u64), n);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return launch_strided(device, stream, insert_hashes_kernel<BitsView>, n, bits_view(d_filter, m_bits, n_hash, k), static_cast<const uint64_t*>(d_h0_u64), n);
 }
 
 int ntc_bloom_query_hashes_device(int32_t device, void* stream, const void* d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k, const void* d_h0_u64, uint64_t n,
                                   void* d_flags_u8)
 {
 	if (int rc = check_filter("ntc_bloom_query_hashes_device", d_filter, m_bits, n_hash, k)) return rc;
-	if (n && (!d_h0_u64 || !d_flags_u8)) return fail(NTC_ERR_ARG, "ntc_bloom_query_hashes_device: null hashes or flags");
-	if ((uintptr_t)d_h0_u64 & 7u) return fail(NTC_ERR_ARG, "ntc_bloom_query_hashes_device: the hashes are not 8-byte aligned");
+	if (int rc = check_hashes("ntc_bloom_query_hashes_device", d_h0_u64, n, "hashes or flags", d_flags_u8 != nullptr)) return rc;
 	if (n == 0) return 0;
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(bloom_query_hashes_kernel, dim3(stride_grid(n)), dim3(256), 0, st, static_cast<const uint32_t*>(d_filter), bloom_hashes(m_bits, n_hash, k),
-	                   static_cast<const uint64_t*>(d_h0_u64), n, static_cast<unsigned char*>(d_flags_u8));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return launch_strided(device, stream, query_hashes_kernel<BitsView>, n, bits_view(d_filter, m_bits, n_hash, k), static_cast<const uint64_t*>(d_h0_u64), n,
+	                      static_cast<unsigned char*>(d_flags_u8));
 }
 
 int ntc_bloom_popcount_device(int32_t device, void* stream, const void* d_filter, uint64_t m_bits, uint64_t* pop)
@@ -160,7 +96,7 @@ int ntc_bloom_popcount_device(int32_t device, void* stream, const void* d_filter
 	const uint64_t n_words = filter_words(m_bits);
 	uint32_t last_mask = 0; // the positions of the last dword that are below m_bits, by the bit rule
 	for (uint64_t loc = (n_words - 1) * 32; loc < m_bits; ++loc)
-		last_mask |= 1u << (uint32_t)((loc & 24u) + 7u - (loc & 7u));
+		last_mask |= bloom_bit(loc);
 	hipLaunchKernelGGL(bloom_popcount_kernel, dim3(stride_grid(n_words)), dim3(256), 0, st, static_cast<const uint32_t*>(d_filter), n_words, last_mask, d_out.get());
 	HIP_TRY(hipGetLastError());
 	unsigned long long out[2] = {0, 0};
@@ -176,13 +112,8 @@ int ntc_bloom_or_device(int32_t device, void* stream, void* d_dst, const void* d
 	if (int rc = check_filter("ntc_bloom_or_device", d_dst, m_bits, 1, 1)) return rc;
 	if (int rc = check_filter("ntc_bloom_or_device", d_src, m_bits, 1, 1)) return rc;
 	if (d_dst == d_src) return 0;
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
 	const uint64_t n_words = filter_words(m_bits);
-	hipLaunchKernelGGL(bloom_or_kernel, dim3(stride_grid(n_words)), dim3(256), 0, st, static_cast<uint32_t*>(d_dst), static_cast<const uint32_t*>(d_src), n_words);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return launch_strided(device, stream, bloom_or_kernel, n_words, static_cast<uint32_t*>(d_dst), static_cast<const uint32_t*>(d_src), n_words);
 }
 
 } // extern "C"

@@ -1,6 +1,13 @@
-// ntc_bloom_walk.hpp — what the plain Bloom filters (ntc_bloom.hip) and the counting filters (ntc_cbloom.hip) share: the remainder by the filter's size,
-// the multi-hash, the argument checks and THE WALK over every window of a device-resident input (DESIGN.md §4 "Bloom filters").  What is done with a
-// window's value is a template parameter of the walk kernel, an action `Act`:
+// ntc_bloom_walk.hpp — what the plain Bloom filters (ntc_bloom.hip), the counting filters (ntc_cbloom.hip) and the blocked filters (ntc_bbloom.hip)
+// share: the remainder by the filter's size, the multi-hash, the argument checks, THE WALK over every window of a device-resident input (DESIGN.md §4
+// "Bloom filters") and the layer between the walk and a KIND of filter.  A kind is a VIEW: a small struct passed by value — the filter's pointer and its
+// hashes — with the per-value operations the kind has (BitsView here, BlockedView in ntc_bbloom.hpp, CountersView in ntc_cbloom.hip):
+//   void     View::insert(uint64_t h0) const         every kind
+//   bool     View::test(uint64_t h0) const           the bit kinds: whether all bits of h0 are set
+//   uint32_t View::count(uint64_t h0, floor) const   the counting kind
+//   unsigned char View::answer(uint64_t h0) const    what a query over given h_0 values writes per value: test as 0 / 1, or the count
+// InsertAct<View>, TestAct<View> and the two kernels over given h_0 values are templates over the view; the kinds differ by that type and nowhere else.
+// What is done with a window's value is a template parameter of the walk kernel, an action `Act`:
 //   Act::kMode                         kWalkTotal    r = act(h0) is added to one total per call (an insert: 1 per window; the solid insert: 1 per window
 //                                                    that passed)
 //                                      kWalkPerSeq   per sequence: its windows, and the sum of r = act(h0) over them (a query: r = hit)
@@ -71,7 +78,7 @@ __device__ __forceinline__ uint64_t bloom_loc(const BloomMod& d, uint64_t h)
 	return h - t * d.m;
 }
 // the dword of a plain filter and the bit in it (little-endian dwords over the reference's bytes: bit 7 - loc % 8 of byte loc / 8)
-__device__ __forceinline__ uint32_t bloom_bit(uint64_t loc) { return 1u << (uint32_t)((loc & 24u) + 7u - (loc & 7u)); }
+__host__ __device__ __forceinline__ uint32_t bloom_bit(uint64_t loc) { return 1u << (uint32_t)((loc & 24u) + 7u - (loc & 7u)); }
 inline uint64_t filter_words(uint64_t m_bits) { return ((m_bits + 7u) / 8u + 3u) / 4u; }
 __device__ __forceinline__ uint64_t bloom_multi(uint64_t h0, uint32_t i, uint64_t kmul)
 {
@@ -86,6 +93,41 @@ struct BloomHashes {
 	__device__ __forceinline__ uint64_t loc(uint64_t h0, uint32_t i) const { return bloom_loc(mod, i ? bloom_multi(h0, i, kmul) : h0); }
 };
 inline BloomHashes bloom_hashes(uint64_t m, uint32_t n_hash, uint32_t k) { return BloomHashes{bloom_mod(m), n_hash, (uint64_t)k * kMultiSeed}; }
+
+__device__ __forceinline__ void bloom_set(uint32_t* filter, const BloomHashes& hs, uint64_t h0)
+{
+	for (uint32_t i = 0; i < hs.n_hash; ++i) {
+		const uint64_t loc = hs.loc(h0, i);
+		const uint32_t bit = bloom_bit(loc);
+		uint32_t* w = filter + (loc >> 5);
+		// A PLAIN load decides whether the atomic is needed.  No ordering is required: bits only go 0 -> 1 during a build, so a stale value can only
+		// show a bit clear that is already set — a redundant atomic, never a lost one.
+		if ((*w & bit) == 0) (void)__hip_atomic_fetch_or(w, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
+__device__ __forceinline__ bool bloom_test(const uint32_t* filter, const BloomHashes& hs, uint64_t h0)
+{
+	for (uint32_t i = 0; i < hs.n_hash; ++i) {
+		const uint64_t loc = hs.loc(h0, i);
+		if ((filter[loc >> 5] & bloom_bit(loc)) == 0) return false; // leave at the first clear bit
+	}
+	return true;
+}
+// The view of a plain filter.  A view has internal linkage, and with it every kernel instantiated over it: the kernel is its translation unit's own, and
+// LDS that an instantiation only writes (block_total of a kWalkPerSeq walk) can be dropped from it.
+namespace {
+struct BitsView {
+	uint32_t* filter;
+	BloomHashes hs;
+	__device__ __forceinline__ void insert(uint64_t h0) const { bloom_set(filter, hs, h0); }
+	__device__ __forceinline__ bool test(uint64_t h0) const { return bloom_test(filter, hs, h0); }
+	__device__ __forceinline__ unsigned char answer(uint64_t h0) const { return test(h0) ? 1 : 0; }
+};
+} // namespace
+inline BitsView bits_view(const void* d_filter, uint64_t m_bits, uint32_t n_hash, uint32_t k)
+{
+	return BitsView{static_cast<uint32_t*>(const_cast<void*>(d_filter)), bloom_hashes(m_bits, n_hash, k)};
+}
 
 // split rotate by one to the left / right (nthash.hpp:186-217): bits [0, 33) and [33, 64) rotate on their own
 __device__ __forceinline__ uint64_t srol1(uint64_t x)
@@ -294,16 +336,67 @@ template <class Act> __global__ __launch_bounds__(256) void bloom_walk_kernel(co
 	}
 }
 
+// the walk's actions of every kind: insert a window's value (1 per window), test it (1 per hit)
+template <class View> struct InsertAct {
+	static constexpr int kMode = kWalkTotal;
+	View v;
+	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const
+	{
+		v.insert(h0);
+		return 1u;
+	}
+};
+template <class View> struct TestAct {
+	static constexpr int kMode = kWalkPerSeq;
+	View v;
+	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const { return v.test(h0) ? 1u : 0u; }
+};
+
+// the same over n given values h_0, without a walk
+template <class View> __global__ __launch_bounds__(256) void insert_hashes_kernel(View v, const uint64_t* __restrict__ h0, uint64_t n)
+{
+	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
+		v.insert(h0[i]);
+}
+template <class View> __global__ __launch_bounds__(256) void query_hashes_kernel(View v, const uint64_t* __restrict__ h0, uint64_t n, unsigned char* __restrict__ out)
+{
+	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
+		out[i] = v.answer(h0[i]);
+}
+
 inline unsigned stride_grid(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255u) / 256u, 256u * 16u); }
 
-// the checks every filter call shares; `who` names the call, `what` the unit of m ("m_bits" of a plain filter, "m" counters of a counting one)
-inline int check_filter(const char* who, const void* d_filter, uint64_t m, uint32_t n_hash, uint32_t k, const char* what = "m_bits", const char* array = "filter")
+// one launch of a grid-stride kernel over n items on the caller's stream, waited for: what every entry point without a walk and without scratch is
+template <class... Params, class... Args> int launch_strided(int32_t device, void* stream, void (*kernel)(Params...), uint64_t n, Args... args)
+{
+	HIP_TRY(hipSetDevice(device));
+	hipStream_t st = (hipStream_t)stream;
+	hipLaunchKernelGGL(kernel, dim3(stride_grid(n)), dim3(256), 0, st, args...);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(st));
+	return 0;
+}
+
+// The checks every filter call shares; `who` names the call, `what` the unit of m ("m_bits" of a plain filter, "m" counters of a counting one).  A kind
+// whose m is a multiple of a block (ntc_bbloom.hpp) passes the block's bits as `block`: the rule for m and its wording follow from it.
+inline int check_filter(const char* who, const void* d_filter, uint64_t m, uint32_t n_hash, uint32_t k, const char* what = "m_bits", const char* array = "filter",
+                        uint32_t block = 0)
 {
 	if (!d_filter) return fail(NTC_ERR_ARG, "%s: null %s", who, array);
 	if ((uintptr_t)d_filter & 3u) return fail(NTC_ERR_ARG, "%s: the %s is not 4-byte aligned", who, array);
+	if (block && (m < block || m >= (1ull << 40) || m % block != 0))
+		return fail(NTC_ERR_ARG, "%s: %s=%llu is no multiple of %u in %u..2^40-%u", who, what, (unsigned long long)m, block, block, block);
 	if (m < 1 || m >= (1ull << 40)) return fail(NTC_ERR_ARG, "%s: %s=%llu outside 1..2^40-1", who, what, (unsigned long long)m);
 	if (n_hash < 1 || n_hash > 32) return fail(NTC_ERR_ARG, "%s: n_hash=%u outside 1..32", who, n_hash);
 	if (k < 1 || k > kMaxK) return fail(NTC_ERR_ARG, "%s: k=%u outside 1..%u", who, k, kMaxK);
+	return 0;
+}
+
+// n given values h_0 and, for a query, the array their answers go to (`out_ok`: it is there; `what` names the pair in the message)
+inline int check_hashes(const char* who, const void* d_h0_u64, uint64_t n, const char* what = "hashes", bool out_ok = true)
+{
+	if (n && (!d_h0_u64 || !out_ok)) return fail(NTC_ERR_ARG, "%s: null %s", who, what);
+	if ((uintptr_t)d_h0_u64 & 7u) return fail(NTC_ERR_ARG, "%s: the hashes are not 8-byte aligned", who);
 	return 0;
 }
 
@@ -319,9 +412,13 @@ inline int check_input(const char* who, uint32_t strand, const void* d_bases, co
 	return 0;
 }
 
-inline void fill_walk(BloomWalk& a, uint32_t k, uint32_t strand, const void* d_bases, const uint64_t* offsets, uint64_t n_seqs, const uint64_t* d_off)
+// What the three shapes below share: the offsets go up into `d_off`, the walk's arguments are filled in beside the outputs the caller has set in `a`
+// (all else zero), one launch over `blocks` blocks of window starts, checked.
+template <class Act>
+int walk_launch(hipStream_t st, BloomWalk a, const Act& act, uint32_t k, uint32_t strand, const void* d_bases, const uint64_t* offsets, uint64_t n_seqs, uint64_t* d_off,
+                uint64_t blocks)
 {
-	std::memset(&a, 0, sizeof a);
+	HIP_TRY(hipMemcpyAsync(d_off, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
 	const uintptr_t first = reinterpret_cast<uintptr_t>(d_bases) + offsets[0];
 	a.src16 = reinterpret_cast<const uint4*>(first & ~(uintptr_t)15);
 	a.lead = (uint32_t)(first & 15u);
@@ -335,10 +432,13 @@ inline void fill_walk(BloomWalk& a, uint32_t k, uint32_t strand, const void* d_b
 		a.out[c][0] = ntc::srol(ntc::seed_of(c), k);
 		a.out[c][1] = ntc::comp_of(c);
 	}
+	hipLaunchKernelGGL(bloom_walk_kernel<Act>, dim3((unsigned)blocks), dim3(256), 0, st, a, act); // (n <= 2^43: blocks is below 2^31)
+	HIP_TRY(hipGetLastError());
+	return 0;
 }
 
-// The two shapes every walking entry point has.  walk_total: the offsets go up, one launch over the blocks of window starts, *total comes back (the call
-// is synchronous).  walk_per_seq: the two per-sequence arrays are zeroed and filled.  `who` names the call in messages.
+// The three shapes a walking entry point has.  walk_total: one launch over the blocks of window starts, *total comes back (the call is synchronous).
+// walk_per_seq: the two per-sequence arrays are zeroed and filled.  walk_profile: one byte per position.  `who` names the call in messages.
 template <class Act>
 int walk_total(const char* who, int32_t device, void* stream, const Act& act, uint32_t k, uint32_t strand, const void* d_bases, const uint64_t* offsets, uint64_t n_seqs,
                uint64_t* total_out)
@@ -355,14 +455,10 @@ int walk_total(const char* who, int32_t device, void* stream, const Act& act, ui
 	ntc_eng::DevBuf<unsigned long long> d_total;
 	if (!d_off.reserve((n_seqs + 1) * 8) || !d_total.reserve(8))
 		return fail(NTC_ERR_MEMORY, "%s: cannot allocate %llu B of scratch on device", who, (unsigned long long)((n_seqs + 1) * 8 + 8));
-	HIP_TRY(hipMemcpyAsync(d_off, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemsetAsync(d_total, 0, 8, st));
-	BloomWalk a;
-	fill_walk(a, k, strand, d_bases, offsets, n_seqs, d_off);
+	BloomWalk a{};
 	a.total = d_total;
-	const uint64_t blocks = (n - k + 1 + kBlock - 1) / kBlock; // (n <= 2^43: below 2^31)
-	hipLaunchKernelGGL(bloom_walk_kernel<Act>, dim3((unsigned)blocks), dim3(256), 0, st, a, act);
-	HIP_TRY(hipGetLastError());
+	if (int rc = walk_launch(st, a, act, k, strand, d_bases, offsets, n_seqs, d_off, (n - k + 1 + kBlock - 1) / kBlock)) return rc;
 	unsigned long long total = 0;
 	HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
@@ -385,15 +481,31 @@ int walk_per_seq(const char* who, int32_t device, void* stream, const Act& act, 
 	HIP_TRY(hipMemsetAsync(d_windows_u32, 0, n_seqs * 4, st));
 	HIP_TRY(hipMemsetAsync(d_hits_u32, 0, n_seqs * 4, st));
 	if (n >= k) {
-		HIP_TRY(hipMemcpyAsync(d_off, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-		BloomWalk a;
-		fill_walk(a, k, strand, d_bases, offsets, n_seqs, d_off);
+		BloomWalk a{};
 		a.windows = static_cast<uint32_t*>(d_windows_u32);
 		a.hits = static_cast<uint32_t*>(d_hits_u32);
-		const uint64_t blocks = (n - k + 1 + kBlock - 1) / kBlock;
-		hipLaunchKernelGGL(bloom_walk_kernel<Act>, dim3((unsigned)blocks), dim3(256), 0, st, a, act);
-		HIP_TRY(hipGetLastError());
+		if (int rc = walk_launch(st, a, act, k, strand, d_bases, offsets, n_seqs, d_off, (n - k + 1 + kBlock - 1) / kBlock)) return rc;
 	}
+	HIP_TRY(hipStreamSynchronize(st));
+	return 0;
+}
+
+template <class Act>
+int walk_profile(const char* who, int32_t device, void* stream, const Act& act, uint32_t k, uint32_t strand, const void* d_bases, const uint64_t* offsets, uint64_t n_seqs,
+                 void* d_profile_u8)
+{
+	static_assert(Act::kMode == kWalkProfile, "an action that gives the byte of a window's start");
+	const uint64_t n = offsets[n_seqs] - offsets[0];
+	if (n && !d_profile_u8) return fail(NTC_ERR_ARG, "%s: null output", who);
+	if (n == 0) return 0;
+	HIP_TRY(hipSetDevice(device));
+	hipStream_t st = (hipStream_t)stream;
+	ntc_eng::DevBuf<uint64_t> d_off; // (scratch of this call: freed on every way out)
+	if (!d_off.reserve((n_seqs + 1) * 8)) return fail(NTC_ERR_MEMORY, "%s: cannot allocate %llu B of scratch on device", who, (unsigned long long)((n_seqs + 1) * 8));
+	BloomWalk a{};
+	a.profile = static_cast<unsigned char*>(d_profile_u8);
+	// every POSITION has a lane, not only every window start: the last k - 1 positions, and all of an input shorter than k, get their zeros from the kernel
+	if (int rc = walk_launch(st, a, act, k, strand, d_bases, offsets, n_seqs, d_off, (n + kBlock - 1) / kBlock)) return rc;
 	HIP_TRY(hipStreamSynchronize(st));
 	return 0;
 }

@@ -2,9 +2,9 @@
 // filters and solid k-mers").  m unsigned 8-bit counters, counter loc = byte loc, the array padded to a multiple of 4 bytes whose padding stays 0.  A
 // k-mer's n_hash positions are the plain filter's (ntc_bloom_walk.hpp: h_i % m); an insert adds one to each, saturating at 255, so that after any inserts
 // in any order counter[loc] = min(255, increments aimed at loc) — no conservative update, whose result would depend on the order of concurrent inserts.
-// The count of a k-mer is the minimum of its counters.  The walk over the input is ntc_bloom_walk.hpp's, the one the plain filters use: here are the
-// actions (increment, count >= c, count, "count >= c -> set in a plain filter", "count >= c -> set in a blocked filter") and the streaming kernels over
-// the counters (threshold, add, hist).
+// The count of a k-mer is the minimum of its counters.  The walk over the input, the insert action and the kernels over given h_0 values are
+// ntc_bloom_walk.hpp's templates over a filter's view: here are the counting filter's view (CountersView), the counting kind's own actions (count >= c,
+// count, "count >= c -> insert into a plain or a blocked filter") and the streaming kernels over the counters (threshold, add, hist).
 #include "ntc_bbloom.hpp"
 
 using namespace ntc_eng;
@@ -41,16 +41,20 @@ __device__ __forceinline__ uint32_t cbloom_count(const unsigned char* counters, 
 	return c;
 }
 
-struct IncAct {
-	static constexpr int kMode = kWalkTotal;
+// the view of a counting filter
+struct CountersView {
 	uint32_t* counters;
 	BloomHashes hs;
-	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const
-	{
-		cbloom_insert(counters, hs, h0);
-		return 1u;
-	}
+	__device__ __forceinline__ void insert(uint64_t h0) const { cbloom_insert(counters, hs, h0); }
+	__device__ __forceinline__ uint32_t count(uint64_t h0, uint32_t floor) const { return cbloom_count(reinterpret_cast<const unsigned char*>(counters), hs, h0, floor); }
+	__device__ __forceinline__ unsigned char answer(uint64_t h0) const { return (unsigned char)count(h0, 0u); }
 };
+CountersView counters_view(const void* d_counters, uint64_t m, uint32_t n_hash, uint32_t k)
+{
+	return CountersView{static_cast<uint32_t*>(const_cast<void*>(d_counters)), bloom_hashes(m, n_hash, k)};
+}
+
+// the counting kind's own actions
 struct AtLeastAct {
 	static constexpr int kMode = kWalkPerSeq;
 	const unsigned char* counters;
@@ -64,54 +68,21 @@ struct CountAct {
 	BloomHashes hs;
 	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const { return cbloom_count(counters, hs, h0, 0u); }
 };
-// the second stage: a window whose count in a FINISHED counting filter is >= min_count is set in a plain filter of its own size and hash count
-struct SolidAct {
+// the second stage: a window whose count in a FINISHED counting filter is >= min_count is inserted into a filter of its own kind, size and hash count —
+// `Dst` is that filter's view: plain (BitsView) or blocked (BlockedView: one line of the destination per window that passed)
+template <class Dst> struct SolidAct {
 	static constexpr int kMode = kWalkTotal;
 	const unsigned char* counters;
 	BloomHashes chs;
 	uint32_t min_count;
-	uint32_t* filter;
-	BloomHashes hs;
+	Dst dst;
 	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const
 	{
 		if (cbloom_count(counters, chs, h0, min_count) < min_count) return 0u;
-		for (uint32_t i = 0; i < hs.n_hash; ++i) {
-			const uint64_t loc = hs.loc(h0, i);
-			const uint32_t bit = bloom_bit(loc);
-			uint32_t* w = filter + (loc >> 5);
-			if ((*w & bit) == 0) (void)__hip_atomic_fetch_or(w, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (the plain load: as in ntc_bloom.hip)
-		}
+		dst.insert(h0);
 		return 1u;
 	}
 };
-// the same second stage with a BLOCKED destination (ntc_bbloom.hpp): one line of the destination per window that passed
-struct BlockedSolidAct {
-	static constexpr int kMode = kWalkTotal;
-	const unsigned char* counters;
-	BloomHashes chs;
-	uint32_t min_count;
-	uint32_t* filter;
-	BlockedHashes hs;
-	__device__ __forceinline__ uint32_t operator()(uint64_t h0) const
-	{
-		if (cbloom_count(counters, chs, h0, min_count) < min_count) return 0u;
-		bbloom_set(filter, hs, h0);
-		return 1u;
-	}
-};
-
-__global__ __launch_bounds__(256) void cbloom_insert_hashes_kernel(uint32_t* counters, BloomHashes hs, const uint64_t* __restrict__ h0, uint64_t n)
-{
-	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
-		cbloom_insert(counters, hs, h0[i]);
-}
-
-__global__ __launch_bounds__(256) void cbloom_query_hashes_kernel(const unsigned char* __restrict__ counters, BloomHashes hs, const uint64_t* __restrict__ h0, uint64_t n,
-                                                                  unsigned char* __restrict__ counts)
-{
-	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
-		counts[i] = (unsigned char)cbloom_count(counters, hs, h0[i], 0u);
-}
 
 // dword i of the plain filter = the positions 32 i .. 32 i + 31: a lane reads their 32 counters — two 16-byte loads where the array is 16-byte aligned
 // and holds all 32, else the dwords that exist (n_dwords = the padded array's) — and writes the dword.  The padding counters are 0 and min_count >= 1: no
@@ -132,7 +103,7 @@ __global__ __launch_bounds__(256) void cbloom_threshold_kernel(const uint32_t* _
 		uint32_t word = 0;
 #pragma unroll
 		for (uint32_t j = 0; j < 32; ++j) // position 32 i + j: bit 7 - j % 8 of byte j / 8 of the dword
-			word |= ((c[j >> 2] >> (8u * (j & 3u))) & 0xffu) >= min_count ? 1u << ((j & 24u) + 7u - (j & 7u)) : 0u;
+			word |= ((c[j >> 2] >> (8u * (j & 3u))) & 0xffu) >= min_count ? bloom_bit(j) : 0u;
 		filter[i] = word;
 	}
 }
@@ -212,7 +183,7 @@ int ntc_cbloom_insert_device(int32_t device, void* stream, void* d_counters, uin
 {
 	if (int rc = check_counters("ntc_cbloom_insert_device", d_counters, m, n_hash, k)) return rc;
 	if (int rc = check_input("ntc_cbloom_insert_device", strand, d_bases, offsets, n_seqs)) return rc;
-	const IncAct act{static_cast<uint32_t*>(d_counters), bloom_hashes(m, n_hash, k)};
+	const InsertAct<CountersView> act{counters_view(d_counters, m, n_hash, k)};
 	return walk_total("ntc_cbloom_insert_device", device, stream, act, k, strand, d_bases, offsets, n_seqs, n_windows);
 }
 
@@ -231,55 +202,26 @@ int ntc_cbloom_profile_device(int32_t device, void* stream, const void* d_counte
 {
 	if (int rc = check_counters("ntc_cbloom_profile_device", d_counters, m, n_hash, k)) return rc;
 	if (int rc = check_input("ntc_cbloom_profile_device", strand, d_bases, offsets, n_seqs)) return rc;
-	const uint64_t n = offsets[n_seqs] - offsets[0];
-	if (n && !d_counts_u8) return fail(NTC_ERR_ARG, "ntc_cbloom_profile_device: null output");
-	if (n == 0) return 0;
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
-	DevBuf<uint64_t> d_off; // (scratch of this call: freed on every way out)
-	if (!d_off.reserve((n_seqs + 1) * 8)) return fail(NTC_ERR_MEMORY, "ntc_cbloom_profile_device: cannot allocate %llu B of scratch on device", (unsigned long long)((n_seqs + 1) * 8));
-	HIP_TRY(hipMemcpyAsync(d_off, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-	BloomWalk a;
-	fill_walk(a, k, strand, d_bases, offsets, n_seqs, d_off);
-	a.profile = static_cast<unsigned char*>(d_counts_u8);
 	const CountAct act{static_cast<const unsigned char*>(d_counters), bloom_hashes(m, n_hash, k)};
-	// every POSITION has a lane, not only every window start: the last k - 1 positions, and all of an input shorter than k, get their zeros from the kernel
-	const uint64_t blocks = (n + kBlock - 1) / kBlock;
-	hipLaunchKernelGGL(bloom_walk_kernel<CountAct>, dim3((unsigned)blocks), dim3(256), 0, st, a, act);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return walk_profile("ntc_cbloom_profile_device", device, stream, act, k, strand, d_bases, offsets, n_seqs, d_counts_u8);
 }
 
 int ntc_cbloom_insert_hashes_device(int32_t device, void* stream, void* d_counters, uint64_t m, uint32_t n_hash, uint32_t k, const void* d_h0_u64, uint64_t n)
 {
 	if (int rc = check_counters("ntc_cbloom_insert_hashes_device", d_counters, m, n_hash, k)) return rc;
-	if (n && !d_h0_u64) return fail(NTC_ERR_ARG, "ntc_cbloom_insert_hashes_device: null hashes");
-	if ((uintptr_t)d_h0_u64 & 7u) return fail(NTC_ERR_ARG, "ntc_cbloom_insert_hashes_device: the hashes are not 8-byte aligned");
+	if (int rc = check_hashes("ntc_cbloom_insert_hashes_device", d_h0_u64, n)) return rc;
 	if (n == 0) return 0;
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(cbloom_insert_hashes_kernel, dim3(stride_grid(n)), dim3(256), 0, st, static_cast<uint32_t*>(d_counters), bloom_hashes(m, n_hash, k),
-	                   static_cast<const uint64_t*>(d_h0_u64), n);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return launch_strided(device, stream, insert_hashes_kernel<CountersView>, n, counters_view(d_counters, m, n_hash, k), static_cast<const uint64_t*>(d_h0_u64), n);
 }
 
 int ntc_cbloom_query_hashes_device(int32_t device, void* stream, const void* d_counters, uint64_t m, uint32_t n_hash, uint32_t k, const void* d_h0_u64, uint64_t n,
                                    void* d_counts_u8)
 {
 	if (int rc = check_counters("ntc_cbloom_query_hashes_device", d_counters, m, n_hash, k)) return rc;
-	if (n && (!d_h0_u64 || !d_counts_u8)) return fail(NTC_ERR_ARG, "ntc_cbloom_query_hashes_device: null hashes or counts");
-	if ((uintptr_t)d_h0_u64 & 7u) return fail(NTC_ERR_ARG, "ntc_cbloom_query_hashes_device: the hashes are not 8-byte aligned");
+	if (int rc = check_hashes("ntc_cbloom_query_hashes_device", d_h0_u64, n, "hashes or counts", d_counts_u8 != nullptr)) return rc;
 	if (n == 0) return 0;
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(cbloom_query_hashes_kernel, dim3(stride_grid(n)), dim3(256), 0, st, static_cast<const unsigned char*>(d_counters), bloom_hashes(m, n_hash, k),
-	                   static_cast<const uint64_t*>(d_h0_u64), n, static_cast<unsigned char*>(d_counts_u8));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return launch_strided(device, stream, query_hashes_kernel<CountersView>, n, counters_view(d_counters, m, n_hash, k), static_cast<const uint64_t*>(d_h0_u64), n,
+	                      static_cast<unsigned char*>(d_counts_u8));
 }
 
 int ntc_cbloom_threshold_device(int32_t device, void* stream, const void* d_counters, uint64_t m, uint32_t min_count, void* d_filter)
@@ -287,14 +229,9 @@ int ntc_cbloom_threshold_device(int32_t device, void* stream, const void* d_coun
 	if (int rc = check_counters("ntc_cbloom_threshold_device", d_counters, m, 1, 1)) return rc;
 	if (int rc = check_min_count("ntc_cbloom_threshold_device", min_count)) return rc;
 	if (int rc = check_filter("ntc_cbloom_threshold_device", d_filter, m, 1, 1)) return rc;
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
 	const uint64_t n_words = filter_words(m);
-	hipLaunchKernelGGL(cbloom_threshold_kernel, dim3(stride_grid(n_words)), dim3(256), 0, st, static_cast<const uint32_t*>(d_counters), counter_dwords(m),
-	                   ((uintptr_t)d_counters & 15u) == 0 ? 1u : 0u, min_count, static_cast<uint32_t*>(d_filter), n_words);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return launch_strided(device, stream, cbloom_threshold_kernel, n_words, static_cast<const uint32_t*>(d_counters), counter_dwords(m),
+	                      ((uintptr_t)d_counters & 15u) == 0 ? 1u : 0u, min_count, static_cast<uint32_t*>(d_filter), n_words);
 }
 
 int ntc_bloom_insert_solid_device(int32_t device, void* stream, void* d_filter, uint64_t m_bits, uint32_t n_hash, const void* d_counters, uint64_t m, uint32_t c_n_hash,
@@ -304,7 +241,7 @@ int ntc_bloom_insert_solid_device(int32_t device, void* stream, void* d_filter, 
 	if (int rc = check_counters("ntc_bloom_insert_solid_device", d_counters, m, c_n_hash, k)) return rc;
 	if (int rc = check_min_count("ntc_bloom_insert_solid_device", min_count)) return rc;
 	if (int rc = check_input("ntc_bloom_insert_solid_device", strand, d_bases, offsets, n_seqs)) return rc;
-	const SolidAct act{static_cast<const unsigned char*>(d_counters), bloom_hashes(m, c_n_hash, k), min_count, static_cast<uint32_t*>(d_filter), bloom_hashes(m_bits, n_hash, k)};
+	const SolidAct<BitsView> act{static_cast<const unsigned char*>(d_counters), bloom_hashes(m, c_n_hash, k), min_count, bits_view(d_filter, m_bits, n_hash, k)};
 	return walk_total("ntc_bloom_insert_solid_device", device, stream, act, k, strand, d_bases, offsets, n_seqs, n_windows);
 }
 
@@ -315,7 +252,7 @@ int ntc_bbloom_insert_solid_device(int32_t device, void* stream, void* d_filter,
 	if (int rc = check_counters("ntc_bbloom_insert_solid_device", d_counters, m, c_n_hash, k)) return rc;
 	if (int rc = check_min_count("ntc_bbloom_insert_solid_device", min_count)) return rc;
 	if (int rc = check_input("ntc_bbloom_insert_solid_device", strand, d_bases, offsets, n_seqs)) return rc;
-	const BlockedSolidAct act{static_cast<const unsigned char*>(d_counters), bloom_hashes(m, c_n_hash, k), min_count, static_cast<uint32_t*>(d_filter), bbloom_hashes(m_bits, n_hash, k)};
+	const SolidAct<BlockedView> act{static_cast<const unsigned char*>(d_counters), bloom_hashes(m, c_n_hash, k), min_count, blocked_view(d_filter, m_bits, n_hash, k)};
 	return walk_total("ntc_bbloom_insert_solid_device", device, stream, act, k, strand, d_bases, offsets, n_seqs, n_windows);
 }
 
@@ -324,13 +261,8 @@ int ntc_cbloom_add_device(int32_t device, void* stream, void* d_dst, const void*
 	if (int rc = check_counters("ntc_cbloom_add_device", d_dst, m, 1, 1)) return rc;
 	if (int rc = check_counters("ntc_cbloom_add_device", d_src, m, 1, 1)) return rc;
 	if (d_dst == d_src) return fail(NTC_ERR_ARG, "ntc_cbloom_add_device: dst and src are the same array");
-	HIP_TRY(hipSetDevice(device));
-	hipStream_t st = (hipStream_t)stream;
 	const uint64_t n_dwords = counter_dwords(m);
-	hipLaunchKernelGGL(cbloom_add_kernel, dim3(stride_grid(n_dwords)), dim3(256), 0, st, static_cast<uint32_t*>(d_dst), static_cast<const uint32_t*>(d_src), n_dwords);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
+	return launch_strided(device, stream, cbloom_add_kernel, n_dwords, static_cast<uint32_t*>(d_dst), static_cast<const uint32_t*>(d_src), n_dwords);
 }
 
 int ntc_cbloom_hist_device(int32_t device, void* stream, const void* d_counters, uint64_t m, uint64_t* hist_u64)

@@ -1,5 +1,5 @@
 """What the tests share, host side: paths, read and mask generators, ntComp (ntcard.cpp:132-145), the row-slot and tiled layouts, the comparison with the
-oracle, the command-line runner and the helpers of the C-ABI tests.  One definition each; tests/test_support.py pins them to tests/orc.py and to
+oracle, the command-line runner, the helpers of the Bloom filters' tests and the helpers of the C-ABI tests.  One definition each; tests/test_support.py pins them to tests/orc.py and to
 ntcard_amd.tile_reads.  numpy, ctypes and the oracle only: torch is never imported here (tests/gpu_support.py holds what needs a device)."""
 import ctypes as C
 import gzip
@@ -15,10 +15,14 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 NTCARD = os.path.join(ROOT, "ntcard_amd", "bin", "ntcard")
 NTHLL = os.path.join(ROOT, "ntcard_amd", "bin", "nthll")
 NTSIG = os.path.join(ROOT, "ntcard_amd", "bin", "ntsig")
+NTBLOOM = os.path.join(ROOT, "ntcard_amd", "bin", "ntbloom")
 
 ALPHA = np.frombuffer(b"ACGTacgtUuNnRYKM.-*", dtype=np.uint8)  # random_reads: the first four are the clean draw, the rest the non-base one
 TILE = 2048
 ERR_ARG, ERR_DEVICE = -1, -2
+FAKE = 0x10000  # a pointer that is never followed: every call that gets it is refused before it could be
+LETTERS = b"ACGTUacgtu"  # rand_seq: the bases, and what it draws instead of one
+BAD = b"NNNnRYKM"
 
 
 # ---- reads ----
@@ -45,6 +49,11 @@ def rseq(rng, n, pn=0.0, plow=0.1, bad="NnRY-"):
 
 def rseq_acgt(rng, n):
     return bytes(rng.choice(b"ACGT") for _ in range(n))
+
+
+def rand_seq(rng, n, pn=0.0):
+    """n bytes from a random.Random: a byte of BAD with probability pn, else one of LETTERS (one draw per byte where pn is 0)"""
+    return bytes(rng.choice(BAD) if pn and rng.random() < pn else rng.choice(LETTERS) for _ in range(n))
 
 
 def random_reads(rng, n, L, p_bad, alpha=ALPHA):
@@ -210,6 +219,46 @@ def assert_same_sketch(got, want, what, nonempty=False, hist_r_bits=None):
 def run_cli(binary, args, cwd=None, timeout=60, text=False):
     """binary + args with both streams captured; text: str instead of bytes"""
     return subprocess.run([binary] + [str(a) for a in args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, text=text)
+
+
+# ---- ntbloom (the Bloom filters' command-line tests) ----
+def run(args, cwd):
+    return run_cli(NTBLOOM, args, cwd=cwd, timeout=120)
+
+
+def swap(args, flag, value):
+    out = list(args)
+    out[out.index(flag) + 1] = value
+    return out
+
+
+def without(args, flag):
+    i = args.index(flag)
+    return args[:i] + args[i + 2:]
+
+
+def fastq(seqs, prefix=b"q"):
+    return b"".join(b"@%s%d\n%s\n+\n%s\n" % (prefix, i, s, b"I" * len(s)) for i, s in enumerate(seqs))
+
+
+def rows_of(stdout):
+    lines = stdout.decode().splitlines()
+    assert lines[0] == "name\tlength\twindows\thits\tfraction"
+    return [line.split("\t") for line in lines[1:]]
+
+
+# ---- the C ABI ----
+def L():
+    from ntcard_amd import _abi
+    return _abi.lib()
+
+
+def offs(*v):
+    return np.array(v, dtype=np.uint64)
+
+
+def ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
 
 
 # ---- the C ABI's create calls ----

@@ -11,10 +11,9 @@ import bbloom_model as bb
 import bloom_model as bm
 import cbloom_model as cm
 import strand_model as sm
-from support import NTCARD, ROOT, rseq, run_cli, small_reads
+from support import NTBLOOM, NTCARD, fastq, rows_of, rseq, run_cli, small_reads
 
 pytestmark = pytest.mark.gpu
-NTBLOOM = os.path.join(ROOT, "ntcard_amd", "bin", "ntbloom")
 K, H = 32, 3
 
 
@@ -22,10 +21,6 @@ def run(binary, args, cwd):
     r = run_cli(binary, args, cwd=cwd, timeout=600)
     assert r.returncode == 0, r.stderr
     return r
-
-
-def fastq(seqs, prefix=b"q"):
-    return b"".join(b"@%s%d\n%s\n+\n%s\n" % (prefix, i, s, b"I" * len(s)) for i, s in enumerate(seqs))
 
 
 @pytest.fixture(scope="module")
@@ -42,12 +37,6 @@ def work(tmp_path_factory):
 
 def hist_lines(path):
     return dict(line.split("\t") for line in open(path).read().splitlines())
-
-
-def rows_of(stdout):
-    lines = stdout.decode().splitlines()
-    assert lines[0] == "name\tlength\twindows\thits\tfraction"
-    return [line.split("\t") for line in lines[1:]]
 
 
 def test_hist_to_blocked_filter_to_query_to_info(work):

@@ -13,20 +13,14 @@ import bloom_model as bm
 import cbloom_model as cm
 import strand_model as sm
 from gpu_support import dev, nt  # noqa: F401  (nt: the fixture)
-from support import offsets_of
+from support import offsets_of, rand_seq
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 B = 4096  # NTC_BLOOM_BLOCK: the window starts of one workgroup
-LETTERS = b"ACGTUacgtu"
-BAD = b"NNNnRYKM"
 STRANDS = ["canonical", "forward", "reverse"]
 GUARD = 256  # bytes in front of and behind a guarded filter
-
-
-def rand_seq(rng, n, pn=0.0):
-    return bytes(rng.choice(BAD) if pn and rng.random() < pn else rng.choice(LETTERS) for _ in range(n))
 
 
 def guarded(nt, m_bits, n_hash, k, strand="canonical", shift=0):

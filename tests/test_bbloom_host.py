@@ -12,23 +12,10 @@ import pytest
 import bbloom_model as bb
 import bloom_model as bm
 from ntcard_amd import _abi
-from support import ERR_ARG, GOLD
+from support import ERR_ARG, FAKE, GOLD, L, offs, ptr
 
-FAKE = 0x10000  # a pointer that is never followed: every call below is refused before it could be
 M, H, K = 1000 * 512, 3, 32
 CM = (1 << 20) + 7  # a counting filter's counters
-
-
-def L():
-    return _abi.lib()
-
-
-def offs(*v):
-    return np.array(v, dtype=np.uint64)
-
-
-def ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 NAMES = ["ntc_bbloom_fpr", "ntc_bbloom_size", "ntc_bbloom_insert_device", "ntc_bbloom_query_device", "ntc_bbloom_insert_hashes_device",

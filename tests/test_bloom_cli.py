@@ -7,25 +7,9 @@ import numpy as np
 import pytest
 
 from ntcard_amd import _abi
-from support import ROOT, run_cli
+from support import run, swap, without
 
-NTBLOOM = os.path.join(ROOT, "ntcard_amd", "bin", "ntbloom")
 GOOD = ["-k", "32", "-m", "4096", "-o", "out.bf", "reads.fa"]
-
-
-def run(args, cwd):
-    return run_cli(NTBLOOM, args, cwd=cwd, timeout=120)
-
-
-def swap(args, flag, value):
-    out = list(args)
-    out[out.index(flag) + 1] = value
-    return out
-
-
-def without(args, flag):
-    i = args.index(flag)
-    return args[:i] + args[i + 2:]
 
 
 REFUSALS = [

@@ -10,10 +10,9 @@ import pytest
 
 import bloom_model as bm
 import strand_model as sm
-from support import GOLD, NTCARD, ROOT, rseq, run_cli, small_reads
+from support import GOLD, NTBLOOM, NTCARD, fastq, rows_of, rseq, run_cli, small_reads
 
 pytestmark = pytest.mark.gpu
-NTBLOOM = os.path.join(ROOT, "ntcard_amd", "bin", "ntbloom")
 K, H = 32, 3
 
 
@@ -25,10 +24,6 @@ def run(binary, args, cwd):
 
 def fasta(seqs, prefix=b"c"):  # wrapped at 60 columns: the k-mers cross the line breaks
     return b"".join(b">%s%d some text\n" % (prefix, i) + b"".join(s[j:j + 60] + b"\n" for j in range(0, len(s), 60)) for i, s in enumerate(seqs))
-
-
-def fastq(seqs, prefix=b"q"):
-    return b"".join(b"@%s%d\n%s\n+\n%s\n" % (prefix, i, s, b"I" * len(s)) for i, s in enumerate(seqs))
 
 
 @pytest.fixture(scope="module")
@@ -48,12 +43,6 @@ def work(tmp_path_factory):
 def hist_f0(path):
     lines = dict(line.split("\t") for line in open(path).read().splitlines()[:2])
     return int(lines["F0"])
-
-
-def rows_of(stdout):
-    lines = stdout.decode().splitlines()
-    assert lines[0] == "name\tlength\twindows\thits\tfraction"
-    return [line.split("\t") for line in lines[1:]]
 
 
 def test_hist_to_filter_to_query(work):

@@ -12,20 +12,14 @@ import pytest
 import bloom_model as bm
 import strand_model as sm
 from gpu_support import dev, nt  # noqa: F401  (nt: the fixture)
-from support import offsets_of
+from support import offsets_of, rand_seq
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 B = 4096  # NTC_BLOOM_BLOCK (asserted below)
 M = (1 << 20) + 7
-LETTERS = b"ACGTUacgtu"
-BAD = b"NNNnRYKM"
 STRANDS = ["canonical", "forward", "reverse"]
-
-
-def rand_seq(rng, n, pn=0.0):
-    return bytes(rng.choice(BAD) if pn and rng.random() < pn else rng.choice(LETTERS) for _ in range(n))
 
 
 @functools.lru_cache(maxsize=None)

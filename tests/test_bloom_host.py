@@ -17,22 +17,9 @@ import bloom_model as bm
 import orc
 import strand_model as sm
 from ntcard_amd import _abi
-from support import ERR_ARG, GOLD, rseq
+from support import ERR_ARG, FAKE, GOLD, L, offs, ptr, rseq
 
-FAKE = 0x10000  # a pointer that is never followed: every call below is refused before it could be
 M, H, K = (1 << 20) + 7, 3, 32
-
-
-def L():
-    return _abi.lib()
-
-
-def offs(*v):
-    return np.array(v, dtype=np.uint64)
-
-
-def ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def test_symbols_are_declared_and_exported():

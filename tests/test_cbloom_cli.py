@@ -7,26 +7,10 @@ import numpy as np
 import pytest
 
 from ntcard_amd import _abi
-from support import ROOT, run_cli
+from support import run, swap, without
 
-NTBLOOM = os.path.join(ROOT, "ntcard_amd", "bin", "ntbloom")
 COUNT = ["-k", "32", "-m", "4096", "-o", "out.cbf", "reads.fa"]
 SOLID = ["--min-count", "2", "--hist", "s.hist", "--fpr", "0.01", "-o", "out.bf", "in.cbf", "reads.fa"]
-
-
-def run(args, cwd):
-    return run_cli(NTBLOOM, args, cwd=cwd, timeout=120)
-
-
-def swap(args, flag, value):
-    out = list(args)
-    out[out.index(flag) + 1] = value
-    return out
-
-
-def without(args, flag):
-    i = args.index(flag)
-    return args[:i] + args[i + 2:]
 
 
 def write_filter(path, counting, m=77, k=21, h=4, strand=2, inserted=9, first=0x81):

@@ -10,10 +10,9 @@ import pytest
 import bloom_model as bm
 import cbloom_model as cm
 import strand_model as sm
-from support import ROOT, rseq_acgt, run_cli
+from support import NTBLOOM, fastq, rows_of, rseq_acgt, run_cli
 
 pytestmark = pytest.mark.gpu
-NTBLOOM = os.path.join(ROOT, "ntcard_amd", "bin", "ntbloom")
 K, H, C_MIN = 32, 3, 2
 
 
@@ -21,16 +20,6 @@ def run(args, cwd):
     r = run_cli(NTBLOOM, args, cwd=cwd, timeout=600)
     assert r.returncode == 0, r.stderr
     return r
-
-
-def fastq(seqs, prefix=b"q"):
-    return b"".join(b"@%s%d\n%s\n+\n%s\n" % (prefix, i, s, b"I" * len(s)) for i, s in enumerate(seqs))
-
-
-def rows_of(stdout):
-    lines = stdout.decode().splitlines()
-    assert lines[0] == "name\tlength\twindows\thits\tfraction"
-    return [line.split("\t") for line in lines[1:]]
 
 
 @pytest.fixture(scope="module")

@@ -12,24 +12,11 @@ import bloom_model as bm
 import cbloom_model as cm
 import strand_model as sm
 from ntcard_amd import _abi
-from support import ERR_ARG, GOLD, rseq
+from support import ERR_ARG, FAKE, GOLD, L, offs, ptr, rseq
 
-FAKE = 0x10000  # a pointer that is never followed: every call below is refused before it could be
 M, H, K = (1 << 20) + 7, 3, 32
 NAMES = ["ntc_cbloom_insert_device", "ntc_cbloom_query_device", "ntc_cbloom_profile_device", "ntc_cbloom_insert_hashes_device", "ntc_cbloom_query_hashes_device",
          "ntc_cbloom_threshold_device", "ntc_bloom_insert_solid_device", "ntc_cbloom_add_device", "ntc_cbloom_hist_device", "ntc_cbloom_write", "ntc_cbloom_read"]
-
-
-def L():
-    return _abi.lib()
-
-
-def offs(*v):
-    return np.array(v, dtype=np.uint64)
-
-
-def ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def test_symbols_are_declared_and_exported():
