@@ -5,6 +5,8 @@ it is one) through strand_model.pick.  h_i = orc_multihash(h_0, i, k) (nthash.hp
 positions h_i % m in exact integer arithmetic; the byte image by the reference's bit rule, bit 7 - loc % 8 of byte loc / 8
 (vendor/ntHash/lib/BloomFilter.hpp:56-66).  tests/test_bloom_host.py pins the array forms to orc_multihash, to Python integers, to
 strand_model.window_values and to the reference tool's recorded rows."""
+import functools
+
 import numpy as np
 
 import orc
@@ -13,19 +15,22 @@ import strand_model as sm
 MULTI_SEED = 0x90B45D39FB6DA1FA  # nthash.hpp:381-390
 
 
+@functools.lru_cache(maxsize=1 << 14)
+def _strand_windows(seq, k):
+    """(fs, rs) of every window of ONE sequence, in window order, read-only: strand_model's array form over the sequence alone.  Kept: the models of a
+    test ask for the windows of the same sequences once per call, and at k = 600 one pass costs k table look-ups per position"""
+    fs, rs, ok = sm.array_window_values(sm.pad_reads([seq], max(len(seq), 1)), "1" * k)
+    out = (fs[0][ok[0]], rs[0][ok[0]]) if fs.shape[1] else (np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint64))
+    for a in out:
+        a.flags.writeable = False
+    return out
+
+
 def h0_values(seqs, k, strand=0):
     """[uint64 array per sequence]: the value of every window of k bases, in window order"""
     if strand == sm.CANONICAL:
         return [orc.hash_read(s, k)[0] for s in seqs]
-    if not seqs:
-        return []
-    L = max(max(len(s) for s in seqs), 1)
-    arr = sm.pad_reads(seqs, L)
-    fs, rs, ok = sm.array_window_values(arr, "1" * k)
-    if fs.shape[1] == 0:
-        return [np.zeros(0, dtype=np.uint64) for _ in seqs]
-    v = sm.pick(fs, rs, strand)
-    return [v[i][ok[i]] for i in range(len(seqs))]
+    return [sm.pick(*_strand_windows(bytes(s), k), strand) for s in seqs]
 
 
 def multihash(h0, n_hash, k):
